@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: points/sec, forward + backward, PointNet++ SemSeg, B=16 x 4096 x (3+6) per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload msg|ssg|sa] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload msg|ssg|sa] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
 
 One "step" = one pass of the hot path over one batch of synthetic KITTI-shaped clouds already resident in
 HBM: forward (SA/FP stack + head), nll_loss over all B*N points (reference semseg.py:141-143), backward,
@@ -11,10 +11,13 @@ Train mode (BatchNorm batch statistics), fp32, dropout as in the reference (p = 
 For N > 1 the driver launches one rank per GPU through torch.distributed.run; every rank owns its own 16
 clouds (weak scaling, global batch 16*N) and the only collective is the gradient all-reduce.
 
-Rank 0 prints ONE JSON line.  ``roofline`` describes the kernel family that takes the most device time,
-timed live with HIP events around every C-ABI launch in an instrumented pass after the timed region;
-``cpu_baseline`` is the oracle (torch-CPU port of the reference path, oracle/) timed on this host's cores on
-a bounded sample of the same workload.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times exactly K steps and prints the headline
+(``value``, ``ms_per_step``).  ``--dump-outputs DIR`` also writes what the last timed step returned (loss and log-probs,
+or the SA module's outputs; bit-identical run to run) as DIR/<name>.npy.  ``--full`` adds everything that takes runs of
+its own: ``roofline`` / ``kernels`` (the kernel family that takes the most device time, timed live with HIP events
+around every C-ABI launch in an instrumented pass after the timed region), ``cpu_baseline`` (the oracle, a torch-CPU
+port of the reference path in oracle/, timed on this host's cores on a bounded sample of the same workload) and, for
+the default configuration, ``other_configs`` (the other BASELINE.json configurations, each a child run of this script).
 """
 import argparse
 import json
@@ -203,18 +206,22 @@ def make_step(workload, net, pts, labels, bucket, prefetch=True):
         getattr(net, fork_at[:3]).register_forward_hook(_hook_out)
 
     def step():
+        """-> {name: tensor} of what a caller of the step receives besides the gradients (static tensors when captured)."""
         bucket.wait_reduced()                     # comm stream: the previous step's all-reduce (an event-wait node when captured)
         bucket.zero()
         if workload == "sa":
-            _, feat = net(pts[:, :3, :], pts[:, 3:, :])
+            new_xyz, feat = net(pts[:, :3, :], pts[:, 3:, :])
             loss = feat.sum()
+            out = {"new_xyz": new_xyz, "features": feat}
         else:
             lp = net(pts)
             loss = nll_loss(lp.reshape(-1, lp.shape[-1]), labels.reshape(-1))
+            out = {"log_probs": lp}
         if late_fork and fork_at == "loss":
             _graph.fork_point()                   # a captured step starts the next batch's geometry branch here
         loss.backward()
-        return loss
+        out["loss"] = loss
+        return out
     step.fork_in_step = late_fork                 # (GraphedStep: this step function calls graph.fork_point() itself)
     return step
 
@@ -453,6 +460,32 @@ def timed_protocol(step, all_reduce, fence, steps, warmup, world, dist, torch, d
     return elapsed, info
 
 
+DUMP_LIMIT_BYTES = 60 << 20      # --dump-outputs: array data in all (the .npy headers stay well inside 64 MB)
+
+
+def dump_outputs(out_dir, arrays):
+    """{name: tensor} -> out_dir/<name>.npy in float32 (float64 stays float64).  When the whole would pass DUMP_LIMIT_BYTES, an
+    array larger than its even share of what is left is written as a fixed, seeded sample of its flattened elements (sorted
+    positions, the same on every run of the same arguments); stderr says which."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    left = DUMP_LIMIT_BYTES
+    order = sorted(host, key=lambda n: (host[n].nbytes, n))
+    for i, name in enumerate(order):
+        a = host[name]
+        share = left // (len(order) - i)
+        if a.nbytes > share:
+            k = share // a.itemsize
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))]
+            print("bench: %s.npy holds a seeded sample of %d of its %d elements" % (name, k, host[name].size), file=sys.stderr)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+
+
 def dry_run(args, dist, torch):
     """The benchmark's rank protocol on CPU with gloo ranks and no GPU: the same ``timed_protocol`` as the real run around a toy
     conv + BatchNorm network (plain torch; nothing of oracle/ -- that is for the cpu_baseline legs only) accumulating into the
@@ -522,7 +555,7 @@ def other_configs():
     import subprocess
     out = {}
     for name, extra in OTHER_CONFIGS:
-        cmd = [sys.executable, os.path.abspath(__file__)] + extra + ["--no-cpu-baseline", "--no-other-configs"]
+        cmd = [sys.executable, os.path.abspath(__file__)] + extra + ["--full", "--no-cpu-baseline", "--no-other-configs"]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
             doc = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -559,9 +592,14 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="clouds per GPU (default 16; 8 for --workload sa)")
     ap.add_argument("--points", type=int, default=4096, help="points per cloud (cfg5 of BASELINE.json: 65536)")
     ap.add_argument("--npoint-scale", type=int, default=1, help="MSG only: multiply sa1/sa2 npoint (cfg5: 16)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--detail", action="store_true", help="per-launch table of the instrumented pass on stderr")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the instrumented roofline pass, the CPU baseline and (default configuration) the "
+                         "other BASELINE.json configurations; a plain run does none of them")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned (loss and log-probs, or the SA module's outputs) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the instrumented roofline pass")
+    ap.add_argument("--detail", action="store_true", help="with --full: per-launch table of the instrumented pass on stderr")
     ap.add_argument("--no-comm-stream", action="store_true", help="issue the gradient all-reduce on the step's own stream")
     ap.add_argument("--no-two-bucket", action="store_true",
                     help="one all-reduce of the whole bucket behind the step instead of early (under sa1's backward) + late")
@@ -569,7 +607,7 @@ def main():
     ap.add_argument("--no-prefetch", action="store_true",
                     help="compute each batch's FPS/ball-query/3-NN inside its own step instead of one step ahead")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="headline run only: skip the short runs of the other BASELINE.json configurations (other_configs)")
+                    help="with --full: skip the short runs of the other BASELINE.json configurations (other_configs)")
     ap.add_argument("--same-device", action="store_true",
                     help="testing only: every rank uses GPU 0 (a one-GPU box exercising the N > 1 RCCL path, if RCCL accepts two ranks "
                          "on one device)")
@@ -680,16 +718,28 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    last = {}
+
+    def timed_step():
+        last["out"] = graphed()              # (the two alternating graphs own different output tensors: keep this replay's)
+
     torch.manual_seed(1234)                  # FPS start draws
     # one step = the graph replay, then the only collective of the path (no-op on one GPU), issued right behind it
-    elapsed, rank_info = timed_protocol(graphed, bucket.all_reduce_timed, fence, args.steps, args.warmup, world if use_dist else 1,
+    elapsed, rank_info = timed_protocol(timed_step, bucket.all_reduce_timed, fence, args.steps, args.warmup, world if use_dist else 1,
                                         dist, torch, dev)
     ms_per_step = elapsed / args.steps * 1e3
     value = batch * world * n_points * args.steps / elapsed
 
+    if rank == 0 and args.dump_outputs:
+        # the last timed step as its caller receives it: what the step returns (loss, log-probs / SA outputs), bit-identical run to
+        # run.  The parameter gradients are not written: the backward's fp32 atomics ("What is reproducible run to
+        # run") make them differ between runs of the same build, and those whose exact value is zero (a bias in front of a
+        # training-mode BatchNorm) hold rounding residue only -- no two runs could be compared on them.
+        dump_outputs(args.dump_outputs, last["out"])
+
     roofline = None
     kernels = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # instrumented pass: HIP events around every C-ABI launch, on the stream the kernel runs on.  The launches
         # are issued one after the other here (no parallel MSG scale streams), so a launch's duration
         # is its own and not that of whatever shared the chip with it in the timed, overlapped step above.
@@ -792,7 +842,7 @@ def main():
         roofline["device_ms_all_kernels_per_step"] = round(sum(x["ms"] for x in agg.values()) / prof_steps, 3)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         if n_points == 4096:
             cpu = cpu_baseline(args.workload, batch)
         elif args.workload in ("msg", "ssg"):
@@ -854,12 +904,12 @@ def main():
                          "mfma_frac_reference_formulation the reference's 6 x forward MACs"}
         if cpu:
             line["gpu_over_cpu"] = round(value / cpu["value"], 1)
-        if (world == 1 and not use_dist and args.workload == "msg" and n_points == 4096 and args.npoint_scale == 1
+        if (args.full and world == 1 and not use_dist and args.workload == "msg" and n_points == 4096 and args.npoint_scale == 1
                 and not args.no_other_configs and not args.no_graph and not args.no_cpu_baseline and not args.no_roofline):
             # every other configuration of BASELINE.json under the same clock as the headline: after the timed
             # region and outside it, a few graph replays each in a child process of its own, no CPU baseline.  Only the full
             # default run does this (the tools' --no-cpu-baseline / --no-roofline / rocprofv3 runs stay single-process)
-            del graphed, compute, net, bucket
+            del graphed, compute, net, bucket, last
             torch.cuda.empty_cache()
             line["other_configs"] = other_configs()
         print(json.dumps(line))

@@ -84,3 +84,30 @@ def test_make_step_flag_matrix_without_a_geometry_branch():
             finally:
                 os.environ.clear()
                 os.environ.update(env)
+
+
+def test_dump_outputs_stays_inside_its_budget_with_a_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: arrays as <name>.npy (float32, float64 kept); past the byte budget a large array becomes a fixed sample of its
+    own elements, the same on every run."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    outs = {"loss": torch.tensor(2.5), "log_probs": torch.randn(4, 256, 13, generator=torch.Generator().manual_seed(1)),
+            "grad.w": torch.randn(32, 9, dtype=torch.float64, generator=torch.Generator().manual_seed(2))}
+    bench.dump_outputs(str(tmp_path / "whole"), outs)
+    for n, t in outs.items():
+        a = np.load(tmp_path / "whole" / (n + ".npy"))
+        assert a.dtype == (np.float64 if t.dtype == torch.float64 else np.float32) and np.array_equal(a, t.numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 8192)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), outs)
+    total = 0
+    for n in outs:
+        a, b = np.load(tmp_path / "s1" / (n + ".npy")), np.load(tmp_path / "s2" / (n + ".npy"))
+        assert np.array_equal(a, b)
+        total += a.nbytes
+    assert total <= 8192
+    s = np.load(tmp_path / "s1" / "log_probs.npy")
+    assert s.ndim == 1 and 0 < s.size < outs["log_probs"].numel() and np.isin(s, outs["log_probs"].numpy()).all()
+    assert np.array_equal(np.load(tmp_path / "s1" / "grad.w.npy"), outs["grad.w"].numpy())      # small arrays stay whole

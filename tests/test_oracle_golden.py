@@ -198,21 +198,43 @@ def test_aten_geometry_equals_c_restatement():
     assert float((outs[0] - outs[1]).abs().max()) <= 1e-5
 
 
-def test_shipped_checkpoint_eval_golden():
-    """G7: the reference's shipped KITTI checkpoint in eval mode.  The fixture holds the input cloud, the
-    REFERENCE's log-probabilities and the checkpoint's sha256; the weights themselves never enter the repo, so this runs only
-    where the reference tree is mounted (the development container) and is skipped on the GPU box.  It pins, against the
-    reference's own numbers: the 156 `module.`-prefixed keys loading into the oracle net AND into this package's net class
-    (the state_dict contract of SURVEY.md 8(b)), and the oracle's eval-mode arithmetic (running statistics, no dropout)."""
-    import os
-    path = os.path.join(os.environ.get("PN2_REFERENCE", "/root/reference"), "checkpoints", "pointnet2-inview-0.55884-0001.pth")
-    if not os.path.exists(path):
-        pytest.skip("reference checkpoint not mounted (GPU box): the fixture's input/output pair needs its weights")
-    g = golden("g7_checkpoint_eval.npz")
-    assert hashlib.sha256(open(path, "rb").read()).hexdigest() == str(g["sha256"])
-    sd = torch.load(path, map_location="cpu")
-    assert len(sd) == int(g["n_keys"]) == 156 and all(k.startswith("module.") for k in sd)
-    sd = {k[len("module."):]: v for k, v in sd.items()}
+def stand_in_running_stats(net, seed):
+    """tools/make_golden.py stand_in_running_stats: seeded BatchNorm running statistics, in state_dict order."""
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for k, v in net.state_dict().items():
+            if k.endswith("running_mean"):
+                v.copy_(torch.randn(v.shape, generator=g) * 0.1)
+            elif k.endswith("running_var"):
+                v.copy_(torch.rand(v.shape, generator=g) + 0.5)
+
+
+def state_sha256(net):
+    """tools/make_golden.py state_digest: sha256 over every state_dict key and the bytes of its tensor."""
+    h = hashlib.sha256()
+    for k, v in net.state_dict().items():
+        h.update(k.encode())
+        h.update(v.detach().numpy().tobytes())
+    return h.hexdigest()
+
+
+def test_checkpoint_state_contract_and_eval_golden():
+    """G7S: the reference's shipped KITTI checkpoint as a contract, and eval mode against the reference.  The
+    fixture holds the checkpoint's key names, shapes and dtypes (not its weights) and the REFERENCE's log-probabilities of
+    PointNet2SemSeg(19, 1) in eval mode on seeded stand-in weights (seeded init + seeded running statistics).  It pins: the 156
+    `module.`-prefixed keys loading strictly into the oracle net AND into this package's net class (the state_dict contract of
+    SURVEY.md 8(b)), and the oracle's eval-mode arithmetic (running statistics, no dropout) against the reference's numbers."""
+    g = golden("g7_state_eval.npz")
+    keys = [str(k) for k in g["keys"]]
+    assert len(keys) == 156 and all(k.startswith("module.") for k in keys)
+    torch.manual_seed(int(g["init_seed"]))
+    stand_in = T.RefSSGSemSeg(19, 1)
+    stand_in_running_stats(stand_in, int(g["stats_seed"]))
+    assert state_sha256(stand_in) == str(g["state_sha256"])          # the very weights the reference evaluated
+    ckpt = dict(zip(keys, stand_in.state_dict().values()))           # laid out as the checkpoint: DataParallel prefix on every key
+    assert ["x".join(map(str, v.shape)) for v in ckpt.values()] == [str(s) for s in g["shapes"]]
+    assert [str(v.dtype) for v in ckpt.values()] == [str(d) for d in g["dtypes"]]
+    sd = {k[len("module."):]: v for k, v in ckpt.items()}
     orc = T.RefSSGSemSeg(19, 1)
     orc.load_state_dict(sd)                      # strict: every key and shape of the reference's SA / FP / head modules
     orc.eval()
@@ -220,7 +242,7 @@ def test_shipped_checkpoint_eval_golden():
     net = M.PointNet2SemSeg(19, 1)
     assert net.load_state_dict(sd, strict=True) is not None
     with torch.no_grad():
-        torch.manual_seed(int(g["seed"]))
+        torch.manual_seed(int(g["fwd_seed"]))
         mine = orc(torch.from_numpy(g["points"])).numpy()
     assert mine.shape == g["log_probs"].shape == (1, 2048, 19)
     assert np.abs(mine - g["log_probs"]).max() <= 2e-5

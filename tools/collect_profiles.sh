@@ -22,7 +22,7 @@ pmc() {   # pmc <name> <bench args...>: FETCH_SIZE / WRITE_SIZE passes of 3 + 2 
 }
 stats() { # stats <name> <env or empty> <bench args...>: rocprofv3 --kernel-trace --stats -> $O/prof_<name>_kernel_stats.csv
   local name=$1; shift
-  ( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$name -o t -- python3 $R/bench.py "$@" --no-cpu-baseline > /dev/null 2> $O/prof_$name.err )
+  ( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$name -o t -- python3 $R/bench.py "$@" --full --no-cpu-baseline > /dev/null 2> $O/prof_$name.err )
   f=$(find $O/prof_$name -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp $f $O/prof_${name}_kernel_stats.csv
   rm -rf $O/prof_$name
@@ -37,12 +37,12 @@ pmc msg_n65536 $CFG5_MSG
 mkdir -p $R/profiles
 for k in msg ssg sa ssg_n65536 msg_n65536; do cp $O/pmc_traffic_$k.json $R/profiles/${TAG}_pmc_traffic_$k.json; done
 
-# 2. the bench lines (default command first: exactly what the driver runs)
-python3 bench.py > $O/bench_msg.json 2> $O/bench_msg.err
-python3 bench.py --workload ssg > $O/bench_ssg.json 2> $O/bench_ssg.err
-python3 bench.py --workload sa > $O/bench_sa.json 2> $O/bench_sa.err
-python3 bench.py $CFG5_MSG --steps 5 --warmup 2 > $O/cfg5_msg.json 2> $O/cfg5_msg.err
-python3 bench.py $CFG5_SSG --steps 10 --warmup 3 > $O/cfg5_ssg.json 2> $O/cfg5_ssg.err
+# 2. the bench lines with --full (headline + roofline, CPU baseline; the default configuration adds the other configurations)
+python3 bench.py --full > $O/bench_msg.json 2> $O/bench_msg.err
+python3 bench.py --full --workload ssg > $O/bench_ssg.json 2> $O/bench_ssg.err
+python3 bench.py --full --workload sa > $O/bench_sa.json 2> $O/bench_sa.err
+python3 bench.py --full $CFG5_MSG --steps 5 --warmup 2 > $O/cfg5_msg.json 2> $O/cfg5_msg.err
+python3 bench.py --full $CFG5_SSG --steps 10 --warmup 3 > $O/cfg5_ssg.json 2> $O/cfg5_ssg.err
 
 # 3. rocprofv3 --kernel-trace --stats of the same commands (graph replay; serial launches; the stand-alone BatchNorm launches for A/B)
 stats msg

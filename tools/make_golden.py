@@ -574,11 +574,70 @@ def g7_checkpoint():
          n_keys=np.int64(len(sd)), sha256=np.array(hashlib.sha256(open(path, "rb").read()).hexdigest()))
 
 
+def stand_in_running_stats(net, seed):
+    """Seeded running statistics for every BatchNorm of ``net``, in state_dict order (eval mode then normalises with
+    non-trivial statistics).  tests/test_reference_state_cpu.py repeats this fill."""
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for k, v in net.state_dict().items():
+            if k.endswith("running_mean"):
+                v.copy_(torch.randn(v.shape, generator=g) * 0.1)
+            elif k.endswith("running_var"):
+                v.copy_(torch.rand(v.shape, generator=g) + 0.5)
+
+
+def g7_state():
+    """The shipped checkpoint's state_dict contract without its weights: key names (with the DataParallel `module.` prefix),
+    shapes and dtypes; plus the REFERENCE's eval-mode log-probabilities of PointNet2SemSeg(19, 1) on seeded stand-in weights
+    (seeded init + stand_in_running_stats), so that the oracle's eval arithmetic is pinned by a self-contained fixture."""
+    print("G7S checkpoint state_dict contract + eval mode on stand-in weights")
+    path = os.path.join(REF, "checkpoints", "pointnet2-inview-0.55884-0001.pth")
+    sd = torch.load(path, map_location="cpu")
+    torch.manual_seed(71)
+    ref = R2.PointNet2SemSeg(19, 1)
+    stand_in_running_stats(ref, 72)
+    torch.manual_seed(71)
+    orc = T.RefSSGSemSeg(19, 1)
+    stand_in_running_stats(orc, 72)
+    check(state_digest(ref) == state_digest(orc), "stand-in state of the oracle net equals the reference net's")
+    ref.eval()
+    orc.eval()
+    pts = torch.from_numpy(syn.kitti_batch(300, 1, 2048, channels=4)[0])
+    with torch.no_grad():
+        torch.manual_seed(99)
+        a = ref(pts).numpy()
+        torch.manual_seed(99)
+        b = orc(pts).numpy()
+    check(np.abs(a - b).max() <= 2e-5, "stand-in eval: oracle within 2e-5 (%.2e)" % np.abs(a - b).max())
+    save("g7_state_eval.npz", keys=np.array(list(sd)), shapes=np.array(["x".join(map(str, v.shape)) for v in sd.values()]),
+         dtypes=np.array([str(v.dtype) for v in sd.values()]), points=pts.numpy(), log_probs=a, init_seed=np.int64(71),
+         stats_seed=np.int64(72), fwd_seed=np.int64(99), state_sha256=np.array(state_digest(ref)))
+
+
+def g12_zoo_state():
+    """The five networks of the reference's model/pointnet2.py on its own pointnet_util, seed 0: state_dict keys (in order),
+    shapes, dtypes and the sha256 of the seeded initial values -- what a drop-in build of the same networks must reproduce."""
+    print("G12 zoo state_dicts")
+    out = {}
+    for name, args in (("PointNet2ClsMsg", ()), ("PointNet2ClsSsg", ()), ("PointNet2PartSegSsg", (50,)),
+                       ("PointNet2PartSegMsg_one_hot", (50,)), ("PointNet2SemSeg", (19, 1))):
+        torch.manual_seed(0)
+        net = getattr(R2, name)(*args)
+        sd = net.state_dict()
+        out[name + "/args"] = np.array(args, np.int64)
+        out[name + "/keys"] = np.array(list(sd))
+        out[name + "/shapes"] = np.array(["x".join(map(str, v.shape)) for v in sd.values()])
+        out[name + "/dtypes"] = np.array([str(v.dtype) for v in sd.values()])
+        out[name + "/sha256"] = np.array(state_digest(net))
+        print("  %s: %d tensors" % (name, len(sd)))
+    save("g12_zoo_state.npz", **out)
+
+
 if __name__ == "__main__":
     torch.set_num_threads(8)
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g6n", "g7", "g10", "g10n"]
-    table = dict(g1=g1_fps, g2=g2_ball, g3=g3_sqdist, g4=g4_interp, g5=g5_modules, g6=g6_nets, g7=g7_checkpoint, g10=g10_zoo, g6n=g6_noise,
-                 g10n=g10_noise)
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g6n", "g7", "g7s", "g10", "g10n", "g12"]
+    table = dict(g1=g1_fps, g2=g2_ball, g3=g3_sqdist, g4=g4_interp, g5=g5_modules, g6=g6_nets, g7=g7_checkpoint, g7s=g7_state, g10=g10_zoo,
+                 g6n=g6_noise, g10n=g10_noise, g12=g12_zoo_state)
     for w in which:
         table[w]()
     print("all oracle checks passed")
