@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PN2_ABI_VERSION 11
+#define PN2_ABI_VERSION 12
 
 /* Per-channel fp64 reduction buffers ("stats", "red") are PN2_STAT_REPLICAS interleaved copies of
  * double[2*C] (sum, then second moment): workgroups add into copy (workgroup index % replicas) so the
@@ -543,6 +543,43 @@ int pn2_adam_step(float *param, float *grad, float *exp_avg, float *exp_avg_sq, 
 int pn2_prepare_clouds(const float *raw, const int64_t *row_begin, const int64_t *row_count, const int32_t *raw_label,
                        const float *noise, const int64_t *noise_begin, const int64_t *choice, int B, int N,
                        float *points, int64_t *labels, int *bad_index, pn2_stream_t stream);
+
+/* ---- PointNet v1 (model/pointnet.py: STN3d / STNkd / PointNetEncoder / PointNetSeg), ABI 12 -----------------------------
+ * Per-cloud transform, torch.bmm(x, trans) of PointNetEncoder.forward: out[b*N + n, j] = sum_i X[b*N + n, i] * T[b, i, j].
+ * T [B, k, k] row-major (as torch holds `trans`), k <= 128; X / out position-major rows of pitch ldx / ldo (multiples of 4,
+ * >= round4(k)); X's pad columns must be zero, out's pad columns [k, round4(k)) are written as zeros.  Any N. */
+int pn2_point_transform(const float *X, int ldx, const float *T, int B, int N, int k, float *out, int ldo, pn2_stream_t stream);
+/* Its backward: dX = dOut * T_b^T (dX != NULL, pitch lddx, pad columns written as zeros) and dT_b = sum_n X_n^T dOut_n
+ * (dT != NULL: [B, k, k], STORED; X required).  dT is summed per 256-row slab into `workspace`
+ * (pn2_point_transform_workspace_bytes(B, N, k) bytes, 4-byte aligned, contents irrelevant) and the slabs are added in a fixed
+ * order by a second launch: run-to-run identical, no atomics.  dOut pitch ldd (multiple of 4, >= round4(k), pad columns zero). */
+int64_t pn2_point_transform_workspace_bytes(int B, int N, int k);
+int pn2_point_transform_bwd(const float *dOut, int ldd, const float *X, int ldx, const float *T, int B, int N, int k, float *dX, int lddx,
+                            float *dT, void *workspace, pn2_stream_t stream);
+/* pn2_bn_relu_max WITHOUT the ReLU (the encoder's bn3(conv3(x)) then torch.max over all points): out[g,c] = max_k bn(Y[g*K+k, c]),
+ * bn(y) = fma(y - mean, scale, beta) from the affine block; arg[g,c] = the first k attaining it (a negative gamma selects the
+ * smallest y; a zero gamma gives beta everywhere and names row 0).  Pitches as pn2_bn_relu_max; pad columns are written (0).
+ * Any K. */
+int pn2_bn_max(const float *Y, int ldy, const float *affine, int64_t G, int K, int C, float *out, int ldo, int32_t *arg,
+               pn2_stream_t stream);
+/* Its backward: dZp[g,c] = dOut[g,c] (pitch ldo like arg, pad lanes zero; dOut at any pitch ld_dout >= C), red (replicated,
+ * caller zeroes) += sum_g dOut and sum_g dOut * yhat with yhat = (Y[g*K + arg[g,c], c] - mean) * invstd.  The pooled
+ * pn2_conv1x1_dgrad / _wgrad (dZ == NULL, dZp / arg / Kpool = K) then serve the layer. */
+int pn2_pool_bwd_reduce_noact(const float *dOut, int ld_dout, const int32_t *arg, int ldo, const float *Y, int ldy, const float *affine,
+                              int64_t G, int K, int C, float *dZp, double *red, pn2_stream_t stream);
+/* The broadcast-concat layer of PointNetSeg.conv1 (conv over cat([global.repeat(N), pointfeat])), factorised:
+ *   Y[p, c] = (X W^T)[p, c] + bias[c] + gbias[p / rows_per_group, c]
+ * with X the per-point columns (pointfeat), W their columns of the conv weight (pitch ldw: it may point into the full weight)
+ * and gbias [P / rows_per_group, ldg] the per-cloud term W_g g_b.  pn2_conv1x1_fwd, then one pass that adds gbias and takes
+ * the BatchNorm statistics (stats: replicated double[2*N] as pn2_conv1x1_fwd, caller zeroes; NULL: none). */
+int pn2_conv1x1_fwd_gbias(const float *X, int ldx, const float *W, int ldw, const float *bias, const float *gbias, int ldg,
+                          int64_t rows_per_group, float *Y, int ldy, int64_t P, int K, int N, double *stats, pn2_stream_t stream);
+/* Its per-cloud gradient: s[g, c] = sum over the rows p of group g of dY[p, c], dY = c0*dZ + q1*(y - mean) + q0 (coef as from
+ * pn2_bn_bwd_coef).  s [P / rows_per_group, lds] is STORED (pad columns up to min(lds, round4(C)) as zeros); per-slab sums
+ * in `workspace` (pn2_group_colsum_workspace_bytes bytes) added in a fixed order: run-to-run identical. */
+int64_t pn2_group_colsum_workspace_bytes(int64_t P, int64_t rows_per_group, int C);
+int pn2_group_colsum(const float *dZ, int ldz, const float *Y, int ldy, const float *coef, int64_t P, int64_t rows_per_group, int C,
+                     float *s, int lds, void *workspace, pn2_stream_t stream);
 
 #ifdef __cplusplus
 }

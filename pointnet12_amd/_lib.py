@@ -81,10 +81,18 @@ SIGNATURES = {
     "pn2_log_softmax_bwd": (_i, [_vp, _i, _vp, _i, _i64, _i, _vp, _i, _vp]),
     "pn2_adam_step": (_i, [_vp, _vp, _vp, _vp, _i64, _d, _d, _d, _d, _d, _i64, _vp, _vp, _i, _vp]),
     "pn2_prepare_clouds": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "pn2_point_transform": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _vp]),
+    "pn2_point_transform_workspace_bytes": (_i64, [_i, _i, _i]),
+    "pn2_point_transform_bwd": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "pn2_bn_max": (_i, [_vp, _i, _vp, _i64, _i, _i, _vp, _i, _vp, _vp]),
+    "pn2_pool_bwd_reduce_noact": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i64, _i, _i, _vp, _vp, _vp]),
+    "pn2_conv1x1_fwd_gbias": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i64, _vp, _i, _i64, _i, _i, _vp, _vp]),
+    "pn2_group_colsum_workspace_bytes": (_i64, [_i64, _i64, _i]),
+    "pn2_group_colsum": (_i, [_vp, _i, _vp, _i, _vp, _i64, _i64, _i, _vp, _i, _vp, _vp]),
 }
 
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 PN2_EUNSUPPORTED = -3            # include/pn2.h
 PN2_OK_SPLIT = 1                 # pn2_conv1x1_bwd_pair: done as two launches
 DWX_REPLICAS = 32        # PN2_DWX_REPLICAS of include/pn2.h
@@ -145,7 +153,8 @@ class _Timed:
         if not name.startswith("pn2_") or name in ("pn2_version", "pn2_error_string", "pn2_set_option", "pn2_get_option", "pn2_option_name", "pn2_fps_workspace_bytes",
                                                    "pn2_nll_loss_workspace_bytes", "pn2_res_supported", "pn2_bwd_res_supported", "pn2_conv1x1_wgrad_workspace_bytes",
                                                    "pn2_conv1x1_wgrad_cf_scratch_bytes", "pn2_conv1x1_bwd_cf_supported", "pn2_conv1x1_bwd_first_supported", "pn2_conv1x1_bwd_cf_scratch_bytes", "pn2_last_kernel", "pn2_clear_last_kernel",
-                                                   "pn2_ball_query_workspace_bytes"):
+                                                   "pn2_ball_query_workspace_bytes", "pn2_point_transform_workspace_bytes",
+                                                   "pn2_group_colsum_workspace_bytes"):
             return fn
 
         def timed(*args):
