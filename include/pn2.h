@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PN2_ABI_VERSION 12
+#define PN2_ABI_VERSION 13
 
 /* Per-channel fp64 reduction buffers ("stats", "red") are PN2_STAT_REPLICAS interleaved copies of
  * double[2*C] (sum, then second moment): workgroups add into copy (workgroup index % replicas) so the
@@ -580,6 +580,40 @@ int pn2_conv1x1_fwd_gbias(const float *X, int ldx, const float *W, int ldw, cons
 int64_t pn2_group_colsum_workspace_bytes(int64_t P, int64_t rows_per_group, int C);
 int pn2_group_colsum(const float *dZ, int ldz, const float *Y, int ldy, const float *coef, int64_t P, int64_t rows_per_group, int C,
                      float *s, int lds, void *workspace, pn2_stream_t stream);
+
+/* ---- PointNet v1 part segmentation (model/pointnet.py:153-228, PointNetDenseCls of partseg.py), ABI 13 -----------------------
+ * convs1 (:178, :217-220) is a 1x1 conv over cat([expand, out1, out2, out3, out4, out5]) with 2064 per-cloud and 2880 per-point
+ * columns.  The per-point part is ONE GEMM whose operand is the virtual concatenation of up to 8 sources, each read in place. */
+typedef struct pn2_src {        /* one per-point source of a K-concatenated operand (host struct; the table is passed by pointer) */
+    const float *X; int ldx;    /* [P, ldx] position-major rows, ldx % 4 == 0, ldx >= K */
+    int K;                      /* its columns, K % 4 == 0 */
+    const float *affine;        /* NULL: X as stored; else the affine block (float[4*K]) of the layer that produced X */
+    int relu;                   /* with affine: 1 = relu(bn(x)), 0 = bn(x), both fmaf(x - mean, scale, beta) as pn2_bn_max */
+} pn2_src;
+/* Y[p,c] = sum_i act_i(X_i)[p,:] . W[c, k_i : k_i + K_i] + bias[c] + gbias[p / rows_per_group, c],  k_i = K_0 + .. + K_{i-1}.
+ * W [N rows, pitch ldw >= sum K_i] may point into a wider weight at any column offset (one that is not a multiple of 4 floats
+ * takes guarded scalar weight loads); gbias [P / rows_per_group, ldg] (ldg % 4 == 0, >= round4(N), 16-byte aligned) may be
+ * NULL.  stats as pn2_conv1x1_fwd (replicated double[2*N], caller zeroes; NULL: none), taken on the final y in the same pass.
+ * Y pitch ldy % 4 == 0, >= round4(N), pad columns written as 0.  1 <= nsrc <= 8, P < 2^31. */
+int pn2_conv1x1_fwd_multi(const pn2_src *src, int nsrc, const float *W, int ldw, const float *bias, const float *gbias, int ldg,
+                          int64_t rows_per_group, float *Y, int ldy, int64_t P, int N, double *stats, pn2_stream_t stream);
+/* dW[m, k_i + j] += sum_p dY[p,m] act_i(X_i)[p,j] with dY = c0*dZ + q1*(y - mean) + q0 (coef of pn2_bn_bwd_coef), dense dZ, in ONE
+ * launch over the virtual concatenation (fp32 atomics: dW is accumulated, the caller zeroes it).  dW pitch lddw >= sum K_i, any
+ * column offset; dbias (may be NULL) += sum_p dY[p,m]. */
+int pn2_conv1x1_wgrad_multi(const float *dZ, int ldz, const float *Y, int ldy, const float *coef, const pn2_src *src, int nsrc,
+                            float *dW, int lddw, float *dbias, int64_t P, int M, pn2_stream_t stream);
+/* dX_i = dY W[:, k_i : k_i + K_i] (k_i = K_0 + .. + K_{i-1}; unmasked, stored) into per-source outputs dX[i] of pitch lddx[i]
+ * (% 4 == 0, >= K[i]; columns past K[i] are not written).  dX, lddx and K are host arrays of nsrc (1..8) entries.  One launch
+ * of the pn2_conv1x1_dgrad core per source. */
+int pn2_conv1x1_dgrad_multi(const float *dZ, int ldz, const float *Y, int ldy, const float *coef, const float *W, int ldw,
+                            float *const *dX, const int *lddx, const int *K, int nsrc, int64_t P, int M, pn2_stream_t stream);
+/* BatchNorm output without a ReLU consumed twice (out5 = bn5(conv5(.)) of :207-208, :219): densely (convs1) and by a max over
+ * the K rows of each group (out_max, arg as from pn2_bn_max):
+ *   dZ[g*K + k, c] = dDense[g*K + k, c] + (k == arg[g,c] ? dPool[g,c] : 0);  red (replicated, caller zeroes) += sum dZ, sum dZ * yhat,
+ * yhat = (Y - mean) * invstd.  Every pitch % 4 == 0 and >= round4(C); pad columns of dZ written as 0.  dDense may alias dZ. */
+int pn2_bn_bwd_reduce_noact_dense(const float *dDense, int ldd, const float *dPool, int ldp, const int32_t *arg, int lda,
+                                  const float *Y, int ldy, const float *affine, int64_t G, int K, int C, float *dZ, int ldz,
+                                  double *red, pn2_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -89,10 +89,14 @@ SIGNATURES = {
     "pn2_conv1x1_fwd_gbias": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i64, _vp, _i, _i64, _i, _i, _vp, _vp]),
     "pn2_group_colsum_workspace_bytes": (_i64, [_i64, _i64, _i]),
     "pn2_group_colsum": (_i, [_vp, _i, _vp, _i, _vp, _i64, _i64, _i, _vp, _i, _vp, _vp]),
+    "pn2_conv1x1_fwd_multi": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i64, _vp, _i, _i64, _i, _vp, _vp]),
+    "pn2_conv1x1_wgrad_multi": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i64, _i, _vp]),
+    "pn2_conv1x1_dgrad_multi": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i64, _i, _vp]),
+    "pn2_bn_bwd_reduce_noact_dense": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i64, _i, _i, _vp, _i, _vp, _vp]),
 }
 
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 PN2_EUNSUPPORTED = -3            # include/pn2.h
 PN2_OK_SPLIT = 1                 # pn2_conv1x1_bwd_pair: done as two launches
 DWX_REPLICAS = 32        # PN2_DWX_REPLICAS of include/pn2.h
@@ -125,6 +129,16 @@ class BnCoefLazy(ctypes.Structure):
 class EvalLayer(ctypes.Structure):
     """pn2_eval_layer of include/pn2.h."""
     _fields_ = [("W", _vp), ("bias", _vp), ("K", _i), ("N", _i), ("ldw", _i)]
+
+
+class Src(ctypes.Structure):
+    """pn2_src of include/pn2.h: one per-point source of a K-concatenated operand."""
+    _fields_ = [("X", _vp), ("ldx", _i), ("K", _i), ("affine", _vp), ("relu", _i)]
+
+
+def src_table(entries):
+    """[(X ptr, ldx, K, affine ptr or None, relu)] -> a ctypes pn2_src[n] (pass it as the table pointer)."""
+    return (Src * len(entries))(*[Src(x, ldx, k, aff, relu) for x, ldx, k, aff, relu in entries])
 
 
 class Pn2Error(RuntimeError):

@@ -59,6 +59,42 @@ struct EpiFwd {             // y = acc + bias -> Y; per-channel sum(y), sum(y*y)
     }
 };
 
+// EpiFwd plus a per-group row (ABI 13, pn2_conv1x1_fwd_multi): y = acc + bias + gbias[m / rpg] -> Y, statistics of that final y.
+// The gbias row is requested before the tile is staged through LDS (as EpiDgradMask does with prevY).  gb == nullptr: no term.
+struct EpiFwdG {
+    float *Y; int ldy; const float *bias; const float *gb; int ldg; int rpg; int rshift; double *stats; const float *zp;
+    static constexpr bool kHasStats = true;
+    __host__ __device__ __forceinline__ unsigned *ticket() const { return nullptr; }
+    __device__ __forceinline__ void tail(int) const {}
+    __device__ __forceinline__ bool want_stats() const { return stats != nullptr; }
+    __device__ __forceinline__ void prep(int n, int N, float4 (&c)[4]) const { c[0] = ld4_guard(bias, n, N); }
+    struct Pre { float4 g; };
+    __device__ __forceinline__ void pre_issue(Pre &q, int64_t m, int n, bool valid) const {
+        const unsigned g = rshift >= 0 ? (unsigned)m >> rshift : (unsigned)m / (unsigned)rpg;     // m < 2^31 (host check)
+        q.g = ld4(valid && gb != nullptr ? gb + row_off(g, ldg) + n : zp);                        // (ldg % 4 == 0, >= round4(N))
+    }
+    __device__ __forceinline__ void apply(int64_t m, int n, int N, float4 acc, const float4 (&c)[4], const Pre &q, float4 &s0,
+                                          float4 &s1) const {
+        float4 y;
+        y.x = acc.x + c[0].x + q.g.x; y.y = acc.y + c[0].y + q.g.y; y.z = acc.z + c[0].z + q.g.z; y.w = acc.w + c[0].w + q.g.w;
+        if (n + 3 >= N) {
+            if (n >= N) y.x = 0.f;
+            if (n + 1 >= N) y.y = 0.f;
+            if (n + 2 >= N) y.z = 0.f;
+            y.w = 0.f;
+        }
+        *reinterpret_cast<float4 *>(Y + row_off(m, ldy) + n) = y;
+        s0.x += y.x; s0.y += y.y; s0.z += y.z; s0.w += y.w;
+        s1.x = __builtin_fmaf(y.x, y.x, s1.x); s1.y = __builtin_fmaf(y.y, y.y, s1.y);
+        s1.z = __builtin_fmaf(y.z, y.z, s1.z); s1.w = __builtin_fmaf(y.w, y.w, s1.w);
+    }
+    __device__ __forceinline__ void flush(int n, int N, double a0, double a1) const {
+        double *rep = stats + (size_t)(blockIdx.x % PN2_STAT_REPLICAS) * 2 * N;
+        atomicAdd(rep + n, a0);
+        atomicAdd(rep + N + n, a1);
+    }
+};
+
 struct EpiDgradMask {       // dZprev = acc * relu'(prev) -> dXout; sum(dZprev), sum(dZprev*yhat_prev) -> red
     float *dX; int ldx; const float *prevY; int ldp; const float *aff; int lda; double *red; CoefTail ct; const float *zp;
     static constexpr bool kHasStats = true;
@@ -1795,9 +1831,61 @@ __global__ __launch_bounds__(256) void wgrad_first_cf_kernel(const float *__rest
     if (t == 0) *ticket = 0;
 }
 
+// ----------------------------------------------------------------------------- K-concatenated sources (ABI 13)
+// pn2_conv1x1_fwd_multi / _wgrad_multi: the streamed-weight NT / TN cores above with a LoadMulti operand (mlp_loaders.h).
+// Tiles: the persistent 64 x 128 x 16 core (32 x 64 x 32 when that leaves CUs idle); an unaligned weight window (W at a column
+// offset that is not a multiple of 4 floats) takes the guarded-scalar weight tile.  UNI needs every source boundary to be a
+// multiple of the k-step (16 / 32); PointNetDenseCls's are multiples of 64.
+template <bool UNI>
+int dispatch_multi_nt(const LoadMulti<UNI> &ld, BMat bm, int64_t P, int K4, int N, EpiFwdG epi, hipStream_t s) {
+    // (register budget: the source pick and the gbias row spill at three or four 64 x 128 workgroups per CU, not at two)
+    if (!bm.vec) return launch_nt<64, 128, 16, 2, 2, 2, 1, false, false>(ld, bm, P, K4, N, epi, s);
+    if (N > 32 && pn2_cdiv(P, 64) * pn2_cdiv(N, 128) * 2 <= pn2_num_cus())
+        return launch_nt<32, 64, 32, 1, 2, 3, 1, false, true>(ld, bm, P, K4, N, epi, s);
+    return launch_nt<64, 128, 16, 2, 2, 2, 1, false, true>(ld, bm, P, K4, N, epi, s);
+}
+
 }  // namespace
 
 extern "C" {
+
+int pn2_conv1x1_fwd_multi(const pn2_src *src, int nsrc, const float *W, int ldw, const float *bias, const float *gbias, int ldg,
+                          int64_t rows_per_group, float *Y, int ldy, int64_t P, int N, double *stats, pn2_stream_t stream) {
+    LoadMulti<false> lv{};
+    int K = 0, align = 0;
+    PN2_CHECK_ARG(make_multi(src, nsrc, lv, &K, &align));
+    PN2_CHECK_ARG(W && bias && Y && P > 0 && P < (1LL << 31) && N > 0 && ldw >= K && ldy % 4 == 0 && ldy >= round4(N));
+    PN2_CHECK_ARG(gbias == nullptr || (rows_per_group > 0 && P % rows_per_group == 0 && ldg % 4 == 0 && ldg >= round4(N) &&
+                                       (reinterpret_cast<uintptr_t>(gbias) & 15) == 0));
+    const int rpg = gbias ? (int)rows_per_group : 1;                  // <= P < 2^31
+    const EpiFwdG epi{Y, ldy, bias, gbias, ldg, rpg, pow2_shift(rpg), stats, zero_page_dev()};
+    const BMat bm = make_bmat(W, ldw, K, K);
+    hipStream_t s = pn2_s(stream);
+    // the k-step of the tile dispatch_multi_nt picks: 16, or 32 on the few-row tile
+    const bool fewrow = bm.vec && N > 32 && pn2_cdiv(P, 64) * pn2_cdiv(N, 128) * 2 <= pn2_num_cus();
+    if (align >= (fewrow ? 32 : 16)) {
+        LoadMulti<true> lu{};
+        for (int i = 0; i < PN2_MULTI_MAX; ++i) lu.e[i] = lv.e[i];
+        lu.nsrc = lv.nsrc;
+        lu.zp = lv.zp;
+        return dispatch_multi_nt<true>(lu, bm, P, K, N, epi, s);
+    }
+    return dispatch_multi_nt<false>(lv, bm, P, K, N, epi, s);
+}
+
+int pn2_conv1x1_wgrad_multi(const float *dZ, int ldz, const float *Y, int ldy, const float *coef, const pn2_src *src, int nsrc, float *dW,
+                            int lddw, float *dbias, int64_t P, int M, pn2_stream_t stream) {
+    LoadMulti<false> lx{};
+    int K = 0, align = 0;
+    PN2_CHECK_ARG(make_multi(src, nsrc, lx, &K, &align));
+    PN2_CHECK_ARG(dZ && Y && coef && dW && P > 0 && P < (1LL << 31) && M > 0 && lddw >= K);
+    PN2_CHECK_ARG(ldz % 4 == 0 && ldz >= round4(M) && ldy % 4 == 0 && ldy >= round4(M));
+    const LoadDyDense dy{dZ, ldz, Y, ldy, coef, round4(M), zero_page_dev(), LazyCoef{}};
+    hipStream_t s = pn2_s(stream);
+    // one launch over the whole virtual concatenation: a thread's column quad (and so its source) is fixed for the launch
+    if (M <= 64) return launch_tn<64, 128, 32, 2, 2, 2>(dy, lx, P, M, K, dW, lddw, dbias, s);
+    return launch_tn<128, 128, 16, 2, 2, 2>(dy, lx, P, M, K, dW, lddw, dbias, s);
+}
 
 int pn2_conv1x1_fwd(const float *X, int ldx, const float *in_affine, const float *W, int ldw, const float *bias, float *Y,
                     int ldy, int64_t P, int K, int N, double *stats, const pn2_bn_finalize_tail *fin, const pn2_bn_lazy *in_lazy,

@@ -163,6 +163,91 @@ struct LoadBnReluFixed {
     }
 };
 
+// A K-concatenated operand read from up to PN2_MULTI_MAX per-point sources in place (ABI 13, PointNetDenseCls.convs1): column
+// k of the virtual row is column k - k0 of the source whose window [k0, k0 + K) holds k, transformed by that source's activation.
+// Every K is a multiple of 4, so a loader quad never straddles two sources: the source is picked once per issue, never per
+// element.  UNI: every boundary k0 is a multiple of the launch's k-step, so all lanes of a wave (all at the same k-step of the
+// NT core) pick the same source -- the pick runs on the scalar unit from lane 0's column.  The table travels in the kernel
+// arguments; an entry is picked by unrolled compares (no indexed private array).
+constexpr int PN2_MULTI_MAX = 8;
+struct MultiEnt {
+    const float *X; const float *aff;       // aff: the producer's affine block (pitch K), nullptr for an identity source
+    int ldx, k0, K, mode;                   // mode: 0 = x as stored, 1 = bn(x), 2 = relu(bn(x))
+};
+
+template <bool UNI>
+struct LoadMulti {
+    MultiEnt e[PN2_MULTI_MAX]; int nsrc; const float *zp;
+    static constexpr int kRegs = 4;
+    static constexpr int kTab = 0;
+    __device__ __forceinline__ const float *tab_src() const { return nullptr; }
+    __device__ __forceinline__ void prologue() const {}
+    LoadMulti without_lazy() const { return *this; }
+    template <int IT> struct Raw { float4 x[IT]; float4 mu, sc, be; int mode; };
+    struct Params {};
+    __device__ __forceinline__ MultiEnt pick(int k) const {
+        const int key = UNI ? __builtin_amdgcn_readfirstlane(k) : k;
+        MultiEnt s = e[0];
+#pragma unroll
+        for (int j = 1; j < PN2_MULTI_MAX; ++j)
+            if (j < nsrc && key >= e[j].k0) s = e[j];
+        return s;
+    }
+    template <int IT>
+    __device__ __forceinline__ void issue(Raw<IT> &r, int64_t m, int stride, int k, int64_t rows, bool kvalid) const {
+        const MultiEnt s = pick(k);
+        const int kl = k - s.k0;
+        const bool act = kvalid && s.mode != 0;
+        r.mu = ld4(act ? s.aff + kl : zp);
+        r.sc = ld4(act ? s.aff + s.K + kl : zp);
+        r.be = ld4(act ? s.aff + 2 * s.K + kl : zp);
+        r.mode = s.mode;
+#pragma unroll
+        for (int i = 0; i < IT; ++i) {
+            const int64_t mi = m + (int64_t)i * stride;
+            r.x[i] = ld4((kvalid && mi < rows) ? s.X + row_off(mi, s.ldx) + kl : zp);
+        }
+    }
+    __device__ __forceinline__ Params params(int, bool) const { return Params(); }
+    __device__ __forceinline__ Params params_tab(const float *, int, int, bool) const { return Params(); }
+    template <int IT>
+    __device__ __forceinline__ float4 finish(const Raw<IT> &r, int i, bool valid, const Params &) const {
+        const float4 x = r.x[i];
+        float4 b;
+        b.x = bn_act(x.x, r.mu.x, r.sc.x, r.be.x);
+        b.y = bn_act(x.y, r.mu.y, r.sc.y, r.be.y);
+        b.z = bn_act(x.z, r.mu.z, r.sc.z, r.be.z);
+        b.w = bn_act(x.w, r.mu.w, r.sc.w, r.be.w);
+        if (r.mode == 2) { b.x = fmaxf(b.x, 0.f); b.y = fmaxf(b.y, 0.f); b.z = fmaxf(b.z, 0.f); b.w = fmaxf(b.w, 0.f); }
+        const float4 o = r.mode != 0 ? b : x;
+        return valid ? o : kZero4;
+    }
+};
+
+// The host side of a source table: checks every entry (include/pn2.h, pn2_src) and lays the table out for LoadMulti.
+// *Ktot = the virtual operand's width; *min_align = the largest power of two (<= 64) that divides every boundary k0.
+template <bool UNI>
+static inline bool make_multi(const pn2_src *src, int nsrc, LoadMulti<UNI> &ld, int *Ktot, int *min_align) {
+    if (src == nullptr || nsrc < 1 || nsrc > PN2_MULTI_MAX) return false;
+    int64_t k0 = 0;
+    int align = 64;
+    for (int i = 0; i < PN2_MULTI_MAX; ++i) ld.e[i] = MultiEnt{nullptr, nullptr, 0, 0, 0, 0};
+    for (int i = 0; i < nsrc; ++i) {
+        const pn2_src &s = src[i];
+        if (s.X == nullptr || s.K <= 0 || s.K % 4 || s.ldx % 4 || s.ldx < s.K || (s.relu != 0 && s.relu != 1)) return false;
+        if (s.relu && s.affine == nullptr) return false;
+        while (k0 % align) align >>= 1;
+        ld.e[i] = MultiEnt{s.X, s.affine, s.ldx, (int)k0, s.K, s.affine == nullptr ? 0 : (s.relu ? 2 : 1)};
+        k0 += s.K;
+        if (k0 >= (1LL << 30)) return false;
+    }
+    ld.nsrc = nsrc;
+    ld.zp = zero_page_dev();
+    *Ktot = (int)k0;
+    *min_align = align;
+    return true;
+}
+
 struct DyParams { float4 c0, q1, q0, mu; };
 
 __device__ __forceinline__ DyParams dy_params(const float *coef, int ldc, int k, bool kvalid, const float *zp) {

@@ -1,8 +1,9 @@
 """MI355X-native counterpart of the reference's ``model/pointnet.py`` (PointNet v1).
 
 Same class names, constructor arguments, attribute names and registration order as the reference (``STN3d``, ``STNkd``,
-``PointNetEncoder``, ``PointNetCls``, ``PointNetSeg``, ``feature_transform_reguliarzer``), so ``state_dict`` keys, shapes and
-seeded initial values are the reference's and its checkpoints load with ``pointnet2.load_reference_state``.
+``PointNetEncoder``, ``PointNetCls``, ``PointNetSeg``, ``PointNetDenseCls``, ``PointNetLoss``, ``feature_transform_reguliarzer``), so
+``state_dict`` keys, shapes and seeded initial values are the reference's and its checkpoints load with
+``pointnet2.load_reference_state``.
 
 Every per-point operation runs on the HIP library: the conv + BatchNorm + ReLU stacks (the STN stacks pooled over the whole
 cloud included) through ``shared_mlp``, ``torch.bmm(x, trans)`` through ``pn2_point_transform``, the encoder's conv3 + bn3 + max
@@ -10,12 +11,15 @@ cloud included) through ``shared_mlp``, ``torch.bmm(x, trans)`` through ``pn2_po
 ``W_p pointfeat_p + b + W_g g_b`` -- the [B*N, 1088] concatenation never exists.  Work on [B, .] vectors (the STN fully
 connected layers, the classification head, the regulariser) stays stock PyTorch, as the PointNet++ classification head does.
 """
+import ctypes
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
 from ._lib import check as _check, ptr as _p
+from .loss import nll_loss
 from .pointnet_util import (_REPL, _channel_last, _contig_weight, _empty_rows, _gpu_f32, _ident_coef, _r4, _zeros_small,
                             bump_param_generation, conv1x1, log_softmax_rows, shared_mlp)
 
@@ -391,6 +395,251 @@ class PointNetSeg(nn.Module):
         h = shared_mlp(h, 512, [self.conv2, self.conv3], [self.bn2, self.bn3], 0, self.training)
         logits = conv1x1(h, self.conv4, padded=True)
         return log_softmax_rows(logits, self.k).view(B, N, self.k), trans_feat
+
+
+class _DenseSegHead(torch.autograd.Function):
+    """PointNetDenseCls from out4 on: conv5 + bn5 (no ReLU) + max over the cloud -> out_max, and
+    relu(bns1(convs1(cat([cat([out_max, label]).repeat(N), out1, out2, out3, out4, out5])))) as rows.
+
+    The [B*N, 4944] concatenation and bn5's per-point output are never built.  convs1 is W_g g_b (one [B]-row GEMM,
+    g = [out_max | label]) added in the epilogue of ONE per-point GEMM over the five sources read in place
+    (pn2_conv1x1_fwd_multi); out5 is bn5 applied by that GEMM's loader to the saved pre-BN conv5 output.  Backward: convs1's
+    weight gradient in one launch over the sources (pn2_conv1x1_wgrad_multi), its per-cloud part from the column sums of dY,
+    the data gradients per source (pn2_conv1x1_dgrad_multi); bn5 sees the dense gradient from convs1 plus, at the arg-max rows,
+    the pooled gradient from both heads (pn2_bn_bwd_reduce_noact_dense); conv5's data gradient is added to out4's."""
+
+    @staticmethod
+    def forward(ctx, o1, o2, o3, o4, label, N, training, cfg5, cfgs1, w5, b5, g5, be5, rm5, rv5, nbt5, ws1, bs1, gs1, bes1, rms1, rvs1,
+                nbts1):
+        lib, st = _lib.load(), _lib.stream()
+        dev = o4.device
+        P = o4.shape[0]
+        B = P // N
+        c5, ci5 = w5.shape[0], w5.shape[1]
+        co, ct = ws1.shape[0], ws1.shape[1]
+        cg = c5 + label.shape[1]
+        srcs = (o1, o2, o3, o4)
+        zb = _zeros_small(8 * _REPL * 2 * (c5 + co) + 16 * (_r4(c5) + _r4(co)) + 4 * co, dev)
+        o = 0
+        stats5 = zb[o:o + 8 * _REPL * 2 * c5].view(torch.float64); o += 8 * _REPL * 2 * c5
+        stats1 = zb[o:o + 8 * _REPL * 2 * co].view(torch.float64); o += 8 * _REPL * 2 * co
+        aff5 = zb[o:o + 16 * _r4(c5)].view(torch.float32); o += 16 * _r4(c5)
+        aff1 = zb[o:o + 16 * _r4(co)].view(torch.float32); o += 16 * _r4(co)
+        zero_bias = zb[o:].view(torch.float32)
+        # conv5 + bn5 + max over the cloud (the pre-BN output is kept: bn5 is applied by its consumers)
+        y5 = _empty_rows(P, c5, dev)
+        _check(lib.pn2_conv1x1_fwd(_p(o4), o4.shape[1], None, _p(_contig_weight(w5)), ci5, _p(b5), _p(y5), y5.shape[1], P, ci5, c5,
+                                   _p(stats5) if training else None, None, None, st), "pn2_conv1x1_fwd")
+        eps, mom = cfg5
+        _check(lib.pn2_bn_finalize(_p(stats5), P, c5, _p(g5), _p(be5), eps, mom, int(training), _p(rm5), _p(rv5), _p(nbt5), _p(aff5), st),
+               "pn2_bn_finalize")
+        omax = _empty_rows(B, c5, dev)
+        arg = torch.empty(B, omax.shape[1], device=dev, dtype=torch.int32)
+        _check(lib.pn2_bn_max(_p(y5), y5.shape[1], _p(aff5), B, N, c5, _p(omax), omax.shape[1], _p(arg), st), "pn2_bn_max")
+        # convs1: W_g g_b per cloud, then one GEMM over out1 .. out5 with that term and the statistics in its epilogue
+        g = torch.cat([omax[:, :c5], label], 1)
+        if cg % 4:
+            g = F.pad(g, (0, _r4(cg) - cg))
+        wc = _contig_weight(ws1)
+        gterm = _empty_rows(B, co, dev)
+        _check(lib.pn2_conv1x1_fwd(_p(g), g.shape[1], None, _p(wc), ct, _p(zero_bias), _p(gterm), gterm.shape[1], B, cg, co, None, None, None,
+                                   st), "pn2_conv1x1_fwd")
+        table = _lib.src_table([(_p(s), s.shape[1], s.shape[1], None, 0) for s in srcs] + [(_p(y5), y5.shape[1], c5, _p(aff5), 0)])
+        y1 = _empty_rows(P, co, dev)
+        _check(lib.pn2_conv1x1_fwd_multi(table, len(table), wc.data_ptr() + 4 * cg, ct, _p(bs1), _p(gterm), gterm.shape[1], N, _p(y1),
+                                         y1.shape[1], P, co, _p(stats1) if training else None, st), "pn2_conv1x1_fwd_multi")
+        eps, mom = cfgs1
+        _check(lib.pn2_bn_finalize(_p(stats1), P, co, _p(gs1), _p(bes1), eps, mom, int(training), _p(rms1), _p(rvs1), _p(nbts1), _p(aff1),
+                                   st), "pn2_bn_finalize")
+        z = _empty_rows(P, co, dev)
+        _check(lib.pn2_bn_relu_max(_p(y1), y1.shape[1], _p(aff1), P, 1, co, _p(z), z.shape[1], None, None, st), "pn2_bn_relu_max")
+        if training:
+            bump_param_generation()             # running statistics were written through raw pointers
+        ctx.save_for_backward(o1, o2, o3, o4, g, y5, aff5, arg, y1, z, aff1, w5, g5, ws1, gs1)
+        ctx.meta = (N, bool(training), P, B, c5, ci5, co, ct, cg)
+        return (omax[:, :c5] if omax.shape[1] != c5 else omax), (z[:, :co] if z.shape[1] != co else z)
+
+    @staticmethod
+    def backward(ctx, g_max, g_seg):
+        lib, st = _lib.load(), _lib.stream()
+        o1, o2, o3, o4, g, y5, aff5, arg, y1, z, aff1, w5, g5, ws1, gs1 = ctx.saved_tensors
+        N, training, P, B, c5, ci5, co, ct, cg = ctx.meta
+        dev = o4.device
+        srcs = (o1, o2, o3, o4)
+        ld1, ld5 = y1.shape[1], y5.shape[1]
+        g_seg = g_seg.contiguous().float()
+        if g_seg.shape[1] != ld1:
+            g_seg = F.pad(g_seg, (0, ld1 - g_seg.shape[1]))
+        zb = _zeros_small(8 * _REPL * 2 * (co + c5) + 16 * (_r4(co) + _r4(c5)) + 4 * (co * ct + co + c5 * ci5 + c5), dev)
+        o = 0
+        red1 = zb[o:o + 8 * _REPL * 2 * co].view(torch.float64); o += 8 * _REPL * 2 * co
+        red5 = zb[o:o + 8 * _REPL * 2 * c5].view(torch.float64); o += 8 * _REPL * 2 * c5
+        rest = zb[o:].view(torch.float32)
+        o = 0
+        coef1 = rest[o:o + 4 * _r4(co)]; o += 4 * _r4(co)
+        coef5 = rest[o:o + 4 * _r4(c5)]; o += 4 * _r4(c5)
+        dW1 = rest[o:o + co * ct].view(co, ct); o += co * ct
+        db1 = rest[o:o + co]; o += co
+        dW5 = rest[o:o + c5 * ci5].view(c5, ci5); o += c5 * ci5
+        db5 = rest[o:o + c5]
+        # bns1 + ReLU backward
+        dZ1 = _empty_rows(P, co, dev)
+        _check(lib.pn2_relu_bwd_reduce(_p(g_seg), ld1, _p(z), _p(y1), ld1, _p(aff1), P, co, _p(dZ1), dZ1.shape[1], _p(red1), None, st),
+               "pn2_relu_bwd_reduce")
+        dgs1 = torch.empty(co, device=dev, dtype=torch.float32)
+        dbes1 = torch.empty(co, device=dev, dtype=torch.float32)
+        _check(lib.pn2_bn_bwd_coef(_p(red1), P, co, _p(gs1), _p(aff1), int(training), _p(coef1), _p(dgs1), _p(dbes1), 0, st),
+               "pn2_bn_bwd_coef")
+        table = _lib.src_table([(_p(s), s.shape[1], s.shape[1], None, 0) for s in srcs] + [(_p(y5), ld5, c5, _p(aff5), 0)])
+        wc = _contig_weight(ws1)
+        # convs1, per-point part: one weight-gradient launch over the five sources, data gradients per source
+        _check(lib.pn2_conv1x1_wgrad_multi(_p(dZ1), dZ1.shape[1], _p(y1), ld1, _p(coef1), table, len(table), dW1.data_ptr() + 4 * cg, ct, None,
+                                           P, co, st), "pn2_conv1x1_wgrad_multi")
+        dsrc = [torch.empty(P, s.shape[1], device=dev, dtype=torch.float32) for s in srcs] + [_empty_rows(P, c5, dev)]
+        ptrs = (ctypes.c_void_p * 5)(*[_p(d) for d in dsrc])
+        lds = (ctypes.c_int * 5)(*[d.shape[1] for d in dsrc])
+        ks = (ctypes.c_int * 5)(*([s.shape[1] for s in srcs] + [c5]))
+        _check(lib.pn2_conv1x1_dgrad_multi(_p(dZ1), dZ1.shape[1], _p(y1), ld1, _p(coef1), wc.data_ptr() + 4 * cg, ct, ptrs, lds, ks, 5, P, co,
+                                           st), "pn2_conv1x1_dgrad_multi")
+        # convs1, per-cloud part: s_b = sum_{p in b} dY_p; dW_g += s^T g, db = sum_b s_b, dg = s W_g
+        s = _empty_rows(B, co, dev)
+        ws = torch.empty(int(lib.pn2_group_colsum_workspace_bytes(P, N, co)), device=dev, dtype=torch.uint8)
+        _check(lib.pn2_group_colsum(_p(dZ1), dZ1.shape[1], _p(y1), ld1, _p(coef1), P, N, co, _p(s), s.shape[1], _p(ws), st),
+               "pn2_group_colsum")
+        ident = _ident_coef(co, dev)
+        _check(lib.pn2_conv1x1_wgrad(_p(s), s.shape[1], None, 0, None, 0, _p(s), s.shape[1], _p(ident), _p(g), g.shape[1], None, _p(dW1), ct,
+                                     _p(db1), B, co, cg, None, st), "pn2_conv1x1_wgrad")
+        dg = torch.empty(B, g.shape[1], device=dev, dtype=torch.float32)
+        _check(lib.pn2_conv1x1_dgrad(_p(s), s.shape[1], None, 0, None, 0, _p(s), s.shape[1], _p(ident), _p(wc), ct, None, 0, None, _p(dg),
+                                     dg.shape[1], None, B, co, cg, None, None, st), "pn2_conv1x1_dgrad")
+        # bn5: the dense gradient from convs1 plus the pooled one (classification head + per-cloud part of convs1) at the arg-max rows
+        dpool = dg[:, :c5]
+        if g_max is not None:
+            dpool = dpool + g_max.float()
+        dpool = dpool.contiguous()
+        if dpool.shape[1] != ld5:
+            dpool = F.pad(dpool, (0, ld5 - dpool.shape[1]))
+        d5 = dsrc[4]
+        _check(lib.pn2_bn_bwd_reduce_noact_dense(_p(d5), ld5, _p(dpool), dpool.shape[1], _p(arg), arg.shape[1], _p(y5), ld5, _p(aff5), B, N,
+                                                 c5, _p(d5), ld5, _p(red5), st), "pn2_bn_bwd_reduce_noact_dense")
+        dg5 = torch.empty(c5, device=dev, dtype=torch.float32)
+        dbe5 = torch.empty(c5, device=dev, dtype=torch.float32)
+        _check(lib.pn2_bn_bwd_coef(_p(red5), P, c5, _p(g5), _p(aff5), int(training), _p(coef5), _p(dg5), _p(dbe5), 0, st), "pn2_bn_bwd_coef")
+        _check(lib.pn2_conv1x1_wgrad(_p(d5), ld5, None, 0, None, 0, _p(y5), ld5, _p(coef5), _p(o4), o4.shape[1], None, _p(dW5), ci5,
+                                     None if training else _p(db5), P, c5, ci5, None, st), "pn2_conv1x1_wgrad")
+        d4 = torch.empty(P, o4.shape[1], device=dev, dtype=torch.float32)
+        _check(lib.pn2_conv1x1_dgrad(_p(d5), ld5, None, 0, None, 0, _p(y5), ld5, _p(coef5), _p(_contig_weight(w5)), ci5, None, 0, None, _p(d4),
+                                     d4.shape[1], None, P, c5, ci5, None, None, st), "pn2_conv1x1_dgrad")
+        d4 += dsrc[3]
+        dlabel = dg[:, c5:cg] if ctx.needs_input_grad[4] else None
+        return (dsrc[0], dsrc[1], dsrc[2], d4, dlabel, None, None, None, None, dW5.view_as(w5), db5, dg5, dbe5, None, None, None,
+                dW1.view_as(ws1), db1, dgs1, dbes1, None, None, None)
+
+
+def dense_seg_head(out1, out2, out3, out4, label, net, N, training):
+    """(out_max [B, 2048], relu(bns1(convs1(concat))) rows [B*N, 256]) of a PointNetDenseCls ``net`` (HIP)."""
+    rows = [_gpu_f32(t, "rows") for t in (out1, out2, out3, out4)]
+    label = _gpu_f32(label, "label")
+    for r, conv in zip(rows, (net.conv1, net.conv2, net.conv3, net.conv4)):
+        if r.shape != (rows[0].shape[0], conv.out_channels) or conv.out_channels % 4:
+            raise RuntimeError("dense_seg_head: rows must be [B*N, C_out] of conv1 .. conv4")
+    if rows[0].shape[0] % N or label.shape[0] != rows[0].shape[0] // N:
+        raise RuntimeError("dense_seg_head: label must be [B, cat_num]")
+    return _DenseSegHead.apply(rows[0], rows[1], rows[2], rows[3], label, N, bool(training), _bn_cfg(net.bn5), _bn_cfg(net.bns1),
+                               net.conv5.weight, net.conv5.bias, net.bn5.weight, net.bn5.bias, net.bn5.running_mean, net.bn5.running_var,
+                               net.bn5.num_batches_tracked, net.convs1.weight, net.convs1.bias, net.bns1.weight, net.bns1.bias,
+                               net.bns1.running_mean, net.bns1.running_var, net.bns1.num_batches_tracked)
+
+
+class PointNetDenseCls(nn.Module):
+    """model/pointnet.py PointNetDenseCls (ShapeNet part segmentation, partseg.py): forward(point_cloud [B, 3, N], label [B, cat_num]
+    one-hot float) returns (net [B, cat_num], net2 [B, N, part_num], trans_feat [B, 128, 128]).
+
+    The reference's quirks are kept: ``net`` is raw logits (not log-softmaxed; PointNetLoss applies nll_loss to them as they are);
+    the classification head applies dropout BEFORE bnc2; ``out3`` in the concatenation is the UN-transformed
+    relu(bn3(conv3(.))) -- the feature transform feeds conv4 only; ``out5`` is bn5(conv5(.)) without a ReLU, and the max and convs1
+    both see that same value.  convs1 takes 4944 channels, which is 2048 + cat_num + 2880 only for cat_num = 16: with any other
+    cat_num the reference constructs the network but its forward fails, and so does this one (with a RuntimeError saying why).
+
+    Per-point work runs on the HIP library: shared_mlp for conv1 .. conv4 (one layer per call, so that each output is a convs1
+    source), point_transform for both transforms, and conv5 .. convs1 in dense_seg_head (csrc/pointnet_dense.hip, mlp.hip).  The
+    [B, .] classification head stays stock PyTorch, as in PointNetCls."""
+
+    def __init__(self, cat_num=16, part_num=50):
+        super().__init__()
+        self.cat_num = cat_num
+        self.part_num = part_num
+        self.stn = STN3d()
+        self.conv1 = torch.nn.Conv1d(3, 64, 1)
+        self.conv2 = torch.nn.Conv1d(64, 128, 1)
+        self.conv3 = torch.nn.Conv1d(128, 128, 1)
+        self.conv4 = torch.nn.Conv1d(128, 512, 1)
+        self.conv5 = torch.nn.Conv1d(512, 2048, 1)
+        self.bn1 = nn.BatchNorm1d(64)
+        self.bn2 = nn.BatchNorm1d(128)
+        self.bn3 = nn.BatchNorm1d(128)
+        self.bn4 = nn.BatchNorm1d(512)
+        self.bn5 = nn.BatchNorm1d(2048)
+        self.fstn = STNkd(k=128)
+        # classification network
+        self.fc1 = nn.Linear(2048, 256)
+        self.fc2 = nn.Linear(256, 256)
+        self.fc3 = nn.Linear(256, cat_num)
+        self.dropout = nn.Dropout(p=0.3)
+        self.bnc1 = nn.BatchNorm1d(256)
+        self.bnc2 = nn.BatchNorm1d(256)
+        # segmentation network
+        self.convs1 = torch.nn.Conv1d(4944, 256, 1)
+        self.convs2 = torch.nn.Conv1d(256, 256, 1)
+        self.convs3 = torch.nn.Conv1d(256, 128, 1)
+        self.convs4 = torch.nn.Conv1d(128, part_num, 1)
+        self.bns1 = nn.BatchNorm1d(256)
+        self.bns2 = nn.BatchNorm1d(256)
+        self.bns3 = nn.BatchNorm1d(128)
+
+    def forward(self, point_cloud, label):
+        B, C, N = point_cloud.shape
+        if C != 3:
+            raise RuntimeError("PointNetDenseCls: point_cloud must be [B, 3, N]")
+        if label.dim() != 2 or label.shape[0] != B or 2048 + label.shape[1] + 2880 != self.convs1.in_channels:
+            raise RuntimeError("PointNetDenseCls: label must be [B, %d] (convs1 takes %d = 2048 + cat_num + 2880 channels)"
+                               % (self.convs1.in_channels - 4928, self.convs1.in_channels))
+        rows = _rows(point_cloud)
+        trans = _stn_from_rows(self.stn, rows, B, N, 3)
+        h = point_transform(rows, trans, B, N, 3)
+        out1 = shared_mlp(h, 3, [self.conv1], [self.bn1], 0, self.training)
+        out2 = shared_mlp(out1, 64, [self.conv2], [self.bn2], 0, self.training)
+        out3 = shared_mlp(out2, 128, [self.conv3], [self.bn3], 0, self.training)
+        trans_feat = _stn_from_rows(self.fstn, out3, B, N, 128)
+        out4 = shared_mlp(point_transform(out3, trans_feat, B, N, 128), 128, [self.conv4], [self.bn4], 0, self.training)
+        out_max, h = dense_seg_head(out1, out2, out3, out4, label, self, N, self.training)
+        # classification network ([B, .]: stock PyTorch; dropout before bnc2, no log_softmax -- as the reference)
+        net = F.relu(self.bnc1(self.fc1(out_max)))
+        net = F.relu(self.bnc2(self.dropout(self.fc2(net))))
+        net = self.fc3(net)
+        # segmentation network
+        h = shared_mlp(h, 256, [self.convs2, self.convs3], [self.bns2, self.bns3], 0, self.training)
+        logits = conv1x1(h, self.convs4, padded=True)
+        return net, log_softmax_rows(logits, self.part_num).view(B, N, self.part_num), trans_feat
+
+
+class PointNetLoss(torch.nn.Module):
+    """model/pointnet.py PointNetLoss: (loss, seg_loss, label_loss) with
+    loss = weight * seg_loss + (1 - weight) * label_loss + mat_diff_loss_scale * feature_transform_reguliarzer(trans_feat), where
+    seg_loss = nll_loss(seg_pred, seg) and label_loss = nll_loss(labels_pred, label) on the RAW logits of PointNetDenseCls's
+    ``net``, exactly as the reference computes it.  seg_loss of GPU tensors runs on the HIP library (pointnet12_amd.loss)."""
+
+    def __init__(self, weight=1, mat_diff_loss_scale=0.001):
+        super().__init__()
+        self.mat_diff_loss_scale = mat_diff_loss_scale
+        self.weight = weight
+
+    def forward(self, labels_pred, label, seg_pred, seg, trans_feat):
+        seg_loss = nll_loss(seg_pred, seg) if seg_pred.is_cuda else F.nll_loss(seg_pred, seg)
+        mat_diff_loss = feature_transform_reguliarzer(trans_feat)
+        label_loss = F.nll_loss(labels_pred, label)
+        loss = self.weight * seg_loss + (1 - self.weight) * label_loss + mat_diff_loss * self.mat_diff_loss_scale
+        return loss, seg_loss, label_loss
 
 
 def feature_transform_reguliarzer(trans):
