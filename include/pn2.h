@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PN2_ABI_VERSION 13
+#define PN2_ABI_VERSION 14
 
 /* Per-channel fp64 reduction buffers ("stats", "red") are PN2_STAT_REPLICAS interleaved copies of
  * double[2*C] (sum, then second moment): workgroups add into copy (workgroup index % replicas) so the
@@ -614,6 +614,24 @@ int pn2_conv1x1_dgrad_multi(const float *dZ, int ldz, const float *Y, int ldy, c
 int pn2_bn_bwd_reduce_noact_dense(const float *dDense, int ldd, const float *dPool, int ldp, const int32_t *arg, int lda,
                                   const float *Y, int ldy, const float *affine, int64_t G, int K, int C, float *dZ, int ldz,
                                   double *red, pn2_stream_t stream);
+
+/* ---- Chamfer distance (model/chamfer.py), ABI 14 ---------------------------------------------------------------------------------
+ * Nearest candidate of every query point: p1 [B,N,D] queries, p2 [B,M,D] candidates, 1 <= D <= 16 (larger: PN2_EUNSUPPORTED).
+ *   d2(n,m) = fp32, DIFFERENCE form: t_k = p1[n,k] - p2[m,k]; d2 = t_0*t_0; d2 = fmaf(t_k, t_k, d2), k = 1 .. D-1 in order;
+ *   idx[b,n] = the m of the smallest d2, the LOWEST m on equal d2;  dist[b,n] = sqrt(d2) (correctly rounded, once per query);
+ *   sum (may be NULL) = (sum_b sum_n dist[b,n]) / B, added in a fixed order (fp64 partials per workgroup, then in index order).
+ * dist, idx and sum are bit-identical from run to run; nothing of size N x M is written.  workspace:
+ * pn2_chamfer_nn_workspace_bytes(B, N, M, D) bytes (host-only query, never 0 for a valid shape), 256-byte aligned, need not
+ * be cleared.  B <= 65535, B*N < 2^31. */
+int64_t pn2_chamfer_nn_workspace_bytes(int B, int N, int M, int D);
+int pn2_chamfer_nn(const float *p1, const float *p2, int B, int N, int M, int D, float *dist, int64_t *idx, float *sum,
+                   void *workspace, pn2_stream_t stream);
+/* Backward of `sum` above for the upstream scalar *g (a DEVICE pointer: nothing is read back, the call can be captured):
+ *   dp1[b,n,:] = (g / B) (p1[b,n,:] - p2[b,idx[b,n],:]) / dist[b,n], a zero row where dist == 0;
+ *   dp2[b,idx[b,n],:] -= dp1[b,n,:] (fp32 atomics: the caller zeroes dp2; the order of the additions is not fixed).
+ * Either output may be NULL. */
+int pn2_chamfer_bwd(const float *p1, const float *p2, const float *dist, const int64_t *idx, const float *g, int B, int N, int M,
+                    int D, float *dp1, float *dp2, pn2_stream_t stream);
 
 #ifdef __cplusplus
 }

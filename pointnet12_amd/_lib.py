@@ -93,10 +93,13 @@ SIGNATURES = {
     "pn2_conv1x1_wgrad_multi": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i64, _i, _vp]),
     "pn2_conv1x1_dgrad_multi": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i64, _i, _vp]),
     "pn2_bn_bwd_reduce_noact_dense": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i64, _i, _i, _vp, _i, _vp, _vp]),
+    "pn2_chamfer_nn_workspace_bytes": (_i64, [_i, _i, _i, _i]),
+    "pn2_chamfer_nn": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "pn2_chamfer_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
 }
 
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 PN2_EUNSUPPORTED = -3            # include/pn2.h
 PN2_OK_SPLIT = 1                 # pn2_conv1x1_bwd_pair: done as two launches
 DWX_REPLICAS = 32        # PN2_DWX_REPLICAS of include/pn2.h
@@ -168,7 +171,7 @@ class _Timed:
                                                    "pn2_nll_loss_workspace_bytes", "pn2_res_supported", "pn2_bwd_res_supported", "pn2_conv1x1_wgrad_workspace_bytes",
                                                    "pn2_conv1x1_wgrad_cf_scratch_bytes", "pn2_conv1x1_bwd_cf_supported", "pn2_conv1x1_bwd_first_supported", "pn2_conv1x1_bwd_cf_scratch_bytes", "pn2_last_kernel", "pn2_clear_last_kernel",
                                                    "pn2_ball_query_workspace_bytes", "pn2_point_transform_workspace_bytes",
-                                                   "pn2_group_colsum_workspace_bytes"):
+                                                   "pn2_group_colsum_workspace_bytes", "pn2_chamfer_nn_workspace_bytes"):
             return fn
 
         def timed(*args):
