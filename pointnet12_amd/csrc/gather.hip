@@ -117,8 +117,13 @@ __global__ __launch_bounds__(256) void three_interp_kernel(const float *__restri
         float *o = out + (int64_t)r * ld;
         if (points1)
             for (int c = lane; c < col0; c += 64) o[c] = points1[(int64_t)r * col0 + c];
-        for (int c = lane; c < D; c += 64)
-            o[col0 + c] = __fadd_rn(__fadd_rn(__fmul_rn(p0[c], w0), __fmul_rn(p1[c], w1)), __fmul_rn(p2[c], w2));
+        for (int c = lane; c < D; c += 64) {
+            // every product and sum rounded on its own, as the reference evaluates it: hipcc's __fmul_rn / __fadd_rn are plain
+            // `*` and `+`, which this file's default contraction fused into fmas (tests/test_scatter_gpu.py checks the bits)
+#pragma clang fp contract(off)
+            const float t0 = p0[c] * w0, t1 = p1[c] * w1, t2 = p2[c] * w2;
+            o[col0 + c] = (t0 + t1) + t2;
+        }
         if (zero_tail)
             for (int c = col0 + D + lane; c < ld; c += 64) o[c] = 0.f;
     }

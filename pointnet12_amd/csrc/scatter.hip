@@ -392,6 +392,7 @@ int pn2_invert_index(const int64_t *idx, int B, int M, int T, int32_t *members, 
     pn2_fill_u32(counts, 0u, (int64_t)B * T, s);
     // out-of-range entries are dropped: their slots at the end of a cloud's member array must read "no member"
     pn2_fill_u32(members, 0xFFFFFFFFu, (int64_t)B * M, s);
+    pn2_fill_u32(owners, 0xFFFFFFFFu, (int64_t)B * M, s);          // (the consumers read own[e1] / own[e0 - 1] there)
     const dim3 grid((unsigned)pn2_cdiv(M, 256), (unsigned)B);
     hipLaunchKernelGGL(invert_count_kernel, grid, dim3(256), 0, s, idx, M, T, counts);
     hipLaunchKernelGGL(invert_scan_kernel, dim3((unsigned)B), dim3(1024), 0, s, counts, T, offsets);
