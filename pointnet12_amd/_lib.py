@@ -33,24 +33,24 @@ SIGNATURES = {
     "pn2_gather_rows_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "pn2_group": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "pn2_group_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "pn2_group_affine_fwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "pn2_group_affine_fwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     "pn2_group_affine_bwd": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
     "pn2_three_interp": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp]),
     "pn2_three_interp_bwd": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "pn2_copy_cols": (_i, [_vp, _i, _i, _vp, _i, _i, _i64, _i, _vp]),
-    "pn2_conv1x1_fwd": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, _vp]),
+    "pn2_conv1x1_fwd": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp, _vp, _vp]),
     "pn2_group_conv_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
     "pn2_conv1x1_fwd_pool": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "pn2_bn_pool_select": (_i, [_vp, _vp, _i64, _i, _vp, _i, _vp, _vp, _vp]),
     "pn2_bn_finalize": (_i, [_vp, _i64, _i, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _vp]),
     "pn2_bn_relu_max": (_i, [_vp, _i, _vp, _i64, _i, _i, _vp, _i, _vp, _vp, _vp]),
-    "pn2_pool_bwd_reduce": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp]),
-    "pn2_pool_bwd_reduce_ld": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp]),
+    "pn2_pool_bwd_reduce": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i64, _i, _i, _vp, _vp, _vp]),
+    "pn2_pool_bwd_reduce_ld": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i64, _i, _i, _vp, _vp, _vp]),
     "pn2_pool_bwd_reduce_rec": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp]),
-    "pn2_relu_bwd_reduce": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i64, _i, _vp, _i, _vp, _vp, _vp]),
+    "pn2_relu_bwd_reduce": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i64, _i, _vp, _i, _vp, _vp]),
     "pn2_bn_bwd_coef": (_i, [_vp, _i64, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp]),
     "pn2_conv1x1_dgrad": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp,
-                               _i64, _i, _i, _vp, _vp, _vp]),
+                               _i64, _i, _i, _vp, _vp]),
     "pn2_conv1x1_wgrad": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp,
                                _i64, _i, _i, _vp, _vp]),
     "pn2_conv1x1_wgrad_workspace_bytes": (_i64, [_i64, _i, _i, _i]),
@@ -99,22 +99,10 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 PN2_EUNSUPPORTED = -3            # include/pn2.h
 PN2_OK_SPLIT = 1                 # pn2_conv1x1_bwd_pair: done as two launches
 DWX_REPLICAS = 32        # PN2_DWX_REPLICAS of include/pn2.h
-
-
-class BnFinalizeTail(ctypes.Structure):
-    """pn2_bn_finalize_tail of include/pn2.h."""
-    _fields_ = [("ticket", _vp), ("gamma", _vp), ("beta", _vp), ("eps", _f), ("momentum", _f), ("running_mean", _vp),
-                ("running_var", _vp), ("num_batches_tracked", _vp), ("affine", _vp)]
-
-
-class BnCoefTail(ctypes.Structure):
-    """pn2_bn_coef_tail of include/pn2.h."""
-    _fields_ = [("ticket", _vp), ("gamma", _vp), ("affine", _vp), ("use_batch_stats", _i), ("coef", _vp), ("dgamma", _vp),
-                ("dbeta", _vp), ("accumulate", _i)]
 
 
 class BnLazy(ctypes.Structure):

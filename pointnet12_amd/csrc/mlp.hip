@@ -24,11 +24,9 @@ __device__ __forceinline__ float4 ld4_guard(const float *p, int n, int N) {
     return r;
 }
 
-struct EpiFwd {             // y = acc + bias -> Y; per-channel sum(y), sum(y*y) -> stats (-> affine block, fused tail)
-    float *Y; int ldy; const float *bias; double *stats; FinTail fin;
+struct EpiFwd {             // y = acc + bias -> Y; per-channel sum(y), sum(y*y) -> stats
+    float *Y; int ldy; const float *bias; double *stats;
     static constexpr bool kHasStats = true;
-    __host__ __device__ __forceinline__ unsigned *ticket() const { return fin.ticket; }
-    __device__ __forceinline__ void tail(int N) const { run_fin_tail(fin, stats, N, NTHREADS); }
     __device__ __forceinline__ bool want_stats() const { return stats != nullptr; }
     __device__ __forceinline__ void prep(int n, int N, float4 (&c)[4]) const { c[0] = ld4_guard(bias, n, N); }
     struct Pre {};
@@ -64,8 +62,6 @@ struct EpiFwd {             // y = acc + bias -> Y; per-channel sum(y), sum(y*y)
 struct EpiFwdG {
     float *Y; int ldy; const float *bias; const float *gb; int ldg; int rpg; int rshift; double *stats; const float *zp;
     static constexpr bool kHasStats = true;
-    __host__ __device__ __forceinline__ unsigned *ticket() const { return nullptr; }
-    __device__ __forceinline__ void tail(int) const {}
     __device__ __forceinline__ bool want_stats() const { return stats != nullptr; }
     __device__ __forceinline__ void prep(int n, int N, float4 (&c)[4]) const { c[0] = ld4_guard(bias, n, N); }
     struct Pre { float4 g; };
@@ -96,10 +92,8 @@ struct EpiFwdG {
 };
 
 struct EpiDgradMask {       // dZprev = acc * relu'(prev) -> dXout; sum(dZprev), sum(dZprev*yhat_prev) -> red
-    float *dX; int ldx; const float *prevY; int ldp; const float *aff; int lda; double *red; CoefTail ct; const float *zp;
+    float *dX; int ldx; const float *prevY; int ldp; const float *aff; int lda; double *red; const float *zp;
     static constexpr bool kHasStats = true;
-    __host__ __device__ __forceinline__ unsigned *ticket() const { return ct.ticket; }
-    __device__ __forceinline__ void tail(int N) const { run_coef_tail(ct, red, N, NTHREADS); }
     __device__ __forceinline__ bool want_stats() const { return red != nullptr; }
     __device__ __forceinline__ void prep(int n, int N, float4 (&c)[4]) const {
         Affine a(aff, lda);     // affine blocks are padded to a multiple of 4 with zeros
@@ -141,8 +135,6 @@ struct EpiDgradMask {       // dZprev = acc * relu'(prev) -> dXout; sum(dZprev),
 struct EpiStore {           // first layer: dX0 = acc (pad lanes are exact zeros: weight columns n >= N are never fetched)
     float *dX; int ldx;
     static constexpr bool kHasStats = false;
-    __host__ __device__ __forceinline__ unsigned *ticket() const { return nullptr; }
-    __device__ __forceinline__ void tail(int) const {}
     __device__ __forceinline__ bool want_stats() const { return false; }
     __device__ __forceinline__ void prep(int, int, float4 (&)[4]) const {}
     struct Pre {};
@@ -256,7 +248,7 @@ __device__ __forceinline__ void gemm_nt_body(ALoad aload, BMat bm, int64_t P, in
     const int l31 = lane & 31, lh = lane >> 5;
     const int n0 = n_lo + bid.y * BN;           // n_lo > 0: this launch covers the output columns from n_lo on
     const int64_t tiles_m = (P + BM - 1) / BM;
-    aload.prologue();                                 // consumer-side BatchNorm: fill the block this loader reads (bn_tail.h)
+    aload.prologue();                                 // consumer-side BatchNorm: fill the block this loader reads (bn_affine.h)
     if (ALoad::kTab > 0) {                            // per-channel loader constants: global -> LDS once
         const float *src = aload.tab_src();
         for (int i = t * 4; i < ALoad::kTab * K4; i += NTHREADS * 4)
@@ -511,7 +503,6 @@ __device__ __forceinline__ void gemm_nt_body(ALoad aload, BMat bm, int64_t P, in
             }
             if (n0 + t < N) epi.flush(n0 + t, N, a0, a1);
         }
-        if (epi.ticket() != nullptr && tail_is_last_block(epi.ticket(), bid.gx * bid.gy)) epi.tail(N);
     }
 }
 
@@ -588,7 +579,7 @@ int launch_nt(ALoad aload, BMat bm, int64_t P, int K4, int N, Epi epi, hipStream
 //  * addresses are running pointers (32-bit offsets from per-lane bases), no predicates: P % 32, N % 64 and K % 32 must be 0
 //    (every few-row layer of the four networks except the 515- and 137-column ones, which stay on the core above);
 //  * the four partial tiles are summed in LDS in a fixed order (deterministic) and leave through the same epilogue
-//    functors as the core (bias / ReLU mask, per-channel reductions, fused BatchNorm tails).
+//    functors as the core (bias / ReLU mask, per-channel reductions).
 template <class T, class U> struct fr_same { static constexpr bool v = false; };
 template <class T> struct fr_same<T, T> { static constexpr bool v = true; };
 
@@ -612,7 +603,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void fewrow_nt_kernel(ALoad aload, BMa
     const int tiles_n = N >> 6;
     const int tile = blockIdx.x * NT + wave / KS, ks = wave % KS;
     const int m0 = (tile / tiles_n) * BM, n0 = (tile % tiles_n) * BN;
-    aload.prologue();                                 // consumer-side BatchNorm (bn_tail.h)
+    aload.prologue();                                 // consumer-side BatchNorm (bn_affine.h)
     if constexpr (kTabRows > 0) {
         const float *src;
         int pitch;
@@ -800,7 +791,6 @@ __global__ __launch_bounds__(NTHREADS, 1) void fewrow_nt_kernel(ALoad aload, BMa
                 epi.flush(((blockIdx.x * NT + tl) % tiles_n) * BN + t, N, a0, a1);
             }
         }
-        if (epi.ticket() != nullptr && tail_is_last_block(epi.ticket(), gridDim.x)) epi.tail(N);
     }
 }
 
@@ -869,9 +859,8 @@ int dispatch_nt_vec(ALoad aload, BMat bm, int64_t P, int K4, int N, Epi epi, hip
     }
     // 129..224 output channels (128->196, 256->196 of MSG sa2): 128 columns on the 64x128 tile and the remainder on the
     // narrowest tile that holds it, as a second launch, instead of a second 128-wide tile that is 47 % padding at 196.
-    // (Not with a fused BatchNorm tail: its ticket counts the workgroups of ONE launch.)
     const int nsplit = pn2_opt(PN2_OPT_NT_NSPLIT);
-    if (nsplit && N > 128 && N <= 224 && epi.ticket() == nullptr) {
+    if (nsplit && N > 128 && N <= 224) {
         int rc;
         if constexpr (ALoad::kRegs >= 8) rc = launch_nt<64, 128, 16, 2, 2, 3, 1, BNN, true>(aload, bm, P, K4, N, epi, s, 0, 128);
         else rc = launch_nt<64, 128, 16, 2, 2, 4, 1, BNN, true>(aload, bm, P, K4, N, epi, s, 0, 128);
@@ -1101,7 +1090,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_skinny_kernel(const float *__res
                                                               float *__restrict__ dbias, LazyCoef lc) {
     constexpr int NA = NQ * 4;                                // accumulators per channel (+1 for the bias sum)
     __shared__ float red[4 * 64 * 4 * (NA + 1)];              // [wave][column group (<= 64)][4 channels][NA + 1]
-    lazy_coef_prologue(lc);                                   // consumer-side BatchNorm backward (bn_tail.h)
+    lazy_coef_prologue(lc);                                   // consumer-side BatchNorm backward (bn_affine.h)
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int CG = 1 << cg_log2, RS = 256 >> cg_log2;         // float4 column groups per row; rows per workgroup pass
     const int cq = t & (CG - 1), slot = t >> cg_log2;
@@ -1426,8 +1415,7 @@ __global__ __launch_bounds__(256) void pool_bwd_reduce_kernel(const float *__res
                                                               const int32_t *__restrict__ arg,
                                                               const float *__restrict__ Y, int ldy,
                                                               const float *__restrict__ aff, int lda, int64_t G, int K,
-                                                              int C, float *__restrict__ dZp, double *__restrict__ red,
-                                                              CoefTail ct) {
+                                                              int C, float *__restrict__ dZp, double *__restrict__ red) {
     __shared__ double sh[2][4][64];
     const int cl = threadIdx.x & 63, gl = threadIdx.x >> 6;
     const int c = blockIdx.x * 64 + cl;
@@ -1486,7 +1474,6 @@ __global__ __launch_bounds__(256) void pool_bwd_reduce_kernel(const float *__res
         atomicAdd(rep + c, a0);
         atomicAdd(rep + C + c, a1);
     }
-    if (ct.ticket != nullptr && tail_is_last_block(ct.ticket, gridDim.x * gridDim.y)) run_coef_tail(ct, red, C, 256);
 }
 
 // The same for a pooled last layer whose pre-BN output was never written (pn2_conv1x1_fwd_pool with Y = NULL): the value at the
@@ -1551,8 +1538,7 @@ __global__ __launch_bounds__(256) void relu_bwd_reduce_kernel(const float *__res
                                                               const float *__restrict__ out,
                                                               const float *__restrict__ Y, int ldy,
                                                               const float *__restrict__ aff, int lda, int64_t P, int C,
-                                                              float *__restrict__ dZ, int ldz, double *__restrict__ red,
-                                                              CoefTail ct) {
+                                                              float *__restrict__ dZ, int ldz, double *__restrict__ red) {
     __shared__ double sh[2][4][64];
     const int cl = threadIdx.x & 63, gl = threadIdx.x >> 6;
     const int c = blockIdx.x * 64 + cl;
@@ -1613,7 +1599,6 @@ __global__ __launch_bounds__(256) void relu_bwd_reduce_kernel(const float *__res
         atomicAdd(rep + c, a0);
         atomicAdd(rep + C + c, a1);
     }
-    if (ct.ticket != nullptr && tail_is_last_block(ct.ticket, gridDim.x * gridDim.y)) run_coef_tail(ct, red, C, 256);
 }
 
 __global__ void bn_bwd_coef_kernel(const double *__restrict__ red, double inv_p, int C, int ld,
@@ -1637,39 +1622,6 @@ extern "C" int pn2_debug_stamps(unsigned long long *host_out, int n) {
     return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(pn2_stamp_buf), sizeof(unsigned long long) * (size_t)n) == hipSuccess ? 0 : -2;
 }
 #endif
-
-namespace {
-
-FinTail make_fin_tail(const pn2_bn_finalize_tail *t, int64_t P) {
-    FinTail f{};
-    if (t == nullptr) return f;
-    f.ticket = t->ticket;
-    f.gamma = t->gamma; f.beta = t->beta; f.eps = t->eps; f.momentum = t->momentum;
-    f.rmean = t->running_mean; f.rvar = t->running_var; f.nbt = t->num_batches_tracked; f.affine = t->affine;
-    f.inv_p = 1.0 / (double)P;
-    f.unbias = P > 1 ? (double)P / (double)(P - 1) : 1.0;
-    return f;
-}
-
-CoefTail make_coef_tail(const pn2_bn_coef_tail *t, int64_t P) {
-    CoefTail c{};
-    if (t == nullptr) return c;
-    c.ticket = t->ticket;
-    c.gamma = t->gamma; c.aff = t->affine; c.use_batch = t->use_batch_stats;
-    c.coef = t->coef; c.dgamma = t->dgamma; c.dbeta = t->dbeta; c.accumulate = t->accumulate;
-    c.inv_p = 1.0 / (double)P;
-    return c;
-}
-
-bool fin_tail_ok(const pn2_bn_finalize_tail *t, const double *stats) {
-    return t == nullptr || (stats && t->ticket && t->gamma && t->beta && t->affine);
-}
-
-bool coef_tail_ok(const pn2_bn_coef_tail *t, const double *red) {
-    return t == nullptr || (red && t->ticket && t->gamma && t->affine && t->coef);
-}
-
-}  // namespace
 
 int pn2_fwd_res(const float *X, int ldx, const float *in_affine, const float *W, int ldw, const float *bias, float *Y, int ldy,
                 int64_t P, int K, int N, double *stats, LazyBn lz, hipStream_t s);      // mlp_res.hip
@@ -1710,7 +1662,7 @@ __global__ __launch_bounds__(256) void wgrad_first_cf_kernel(const float *__rest
     constexpr int M = 16 * NB;
     __shared__ float fold[4][NB][256];                            // [wave][block][lane * 4 + r]
     __shared__ double sfold[4][256];
-    lazy_coef_prologue(lc);                                       // consumer-side BatchNorm backward (bn_tail.h)
+    lazy_coef_prologue(lc);                                       // consumer-side BatchNorm backward (bn_affine.h)
     // dZ == NULL (round 6): `part` already holds sum_p dZ[p, c] x[p, j] -- the NEXT layer's fused backward added it straight from
     // its dX tiles (split_bwd_res_kernel, FUSE0: dZ never reached memory) -- and this launch only takes the input's moments
     const bool have_dz = dZ != nullptr;                           // (uniform)
@@ -1888,13 +1840,12 @@ int pn2_conv1x1_wgrad_multi(const float *dZ, int ldz, const float *Y, int ldy, c
 }
 
 int pn2_conv1x1_fwd(const float *X, int ldx, const float *in_affine, const float *W, int ldw, const float *bias, float *Y,
-                    int ldy, int64_t P, int K, int N, double *stats, const pn2_bn_finalize_tail *fin, const pn2_bn_lazy *in_lazy,
-                    pn2_stream_t stream) {
-    PN2_CHECK_ARG(X && W && bias && Y && P > 0 && P < (1LL << 31) && K > 0 && N > 0 && fin_tail_ok(fin, stats));
+                    int ldy, int64_t P, int K, int N, double *stats, const pn2_bn_lazy *in_lazy, pn2_stream_t stream) {
+    PN2_CHECK_ARG(X && W && bias && Y && P > 0 && P < (1LL << 31) && K > 0 && N > 0);
     PN2_CHECK_ARG(ldx % 4 == 0 && ldx >= round4(K) && ldw >= K && ldy % 4 == 0 && ldy >= round4(N));
     PN2_CHECK_ARG(lazy_bn_ok(in_lazy, in_affine, K) && (in_lazy == nullptr || in_affine != nullptr));
     LazyBn lz = make_lazy_bn(in_lazy);                                  // realised by the FIRST launch below; later ones read the block
-    if (fin == nullptr) {                                               // wide layer: W stays in registers (mlp_wide.hip)
+    {                                                                   // wide layer: W stays in registers (mlp_wide.hip)
         int64_t done = 0;
         const int rc = pn2_wide_fwd(X, ldx, in_affine, W, ldw, bias, Y, ldy, P, K, N, stats, lz, pn2_s(stream), &done);
         if (rc != PN2_EUNSUPPORTED) {
@@ -1903,7 +1854,7 @@ int pn2_conv1x1_fwd(const float *X, int ldx, const float *in_affine, const float
             lz = LazyBn{};
         }
     }
-    if (fin == nullptr && pn2_res_supported(P, N, K) && ldy >= N) {      // narrow, long layer: W stays in LDS (mlp_res.hip)
+    if (pn2_res_supported(P, N, K) && ldy >= N) {                        // narrow, long layer: W stays in LDS (mlp_res.hip)
         const int64_t P_full = P & ~(int64_t)31;                        // whole 32-row slabs there, a ragged tail below
         const int rc = pn2_fwd_res(X, ldx, in_affine, W, ldw, bias, Y, ldy, P_full, K, N, stats, lz, pn2_s(stream));
         if (rc != PN2_EUNSUPPORTED) {                                   // (unsupported: W plus eight staging buffers exceed LDS)
@@ -1913,7 +1864,7 @@ int pn2_conv1x1_fwd(const float *X, int ldx, const float *in_affine, const float
         }
     }
     const int K4 = round4(K);
-    EpiFwd epi{Y, ldy, bias, stats, make_fin_tail(fin, P)};
+    EpiFwd epi{Y, ldy, bias, stats};
     const BMat bm = make_bmat(W, ldw, K, K);
     if (in_affine) return dispatch_nt<false>(LoadBnRelu{X, ldx, in_affine, zero_page_dev(), lz}, bm, P, K4, N, epi, pn2_s(stream));
     return dispatch_nt<false>(LoadPlain{X, ldx, zero_page_dev()}, bm, P, K4, N, epi, pn2_s(stream));
@@ -1965,14 +1916,12 @@ int pn2_bn_relu_max(const float *Y, int ldy, const float *affine, int64_t G, int
 }
 
 int pn2_pool_bwd_reduce_ld(const float *dOut, int ld_dout, const float *out, int ldo, const int32_t *arg, const float *Y, int ldy,
-                           const float *affine, int64_t G, int K, int C, float *dZp, double *red, const pn2_bn_coef_tail *tail,
-                           pn2_stream_t stream) {
-    PN2_CHECK_ARG(dOut && out && arg && Y && affine && dZp && red && G > 0 && K > 0 && C > 0 && ldo >= ((C + 3) & ~3) && ld_dout >= C &&
-                  coef_tail_ok(tail, red));
+                           const float *affine, int64_t G, int K, int C, float *dZp, double *red, pn2_stream_t stream) {
+    PN2_CHECK_ARG(dOut && out && arg && Y && affine && dZp && red && G > 0 && K > 0 && C > 0 && ldo >= ((C + 3) & ~3) && ld_dout >= C);
     int64_t gy = pn2_cdiv(G, 4 * 4);                    // one trip of four groups per thread where the grid allows
     if (gy > 1024) gy = 1024;                           // (x 8 reduction replicas: same-address queues of <= 128)
     hipLaunchKernelGGL(pool_bwd_reduce_kernel, dim3((unsigned)pn2_cdiv((C + 3) & ~3, 64), (unsigned)gy), dim3(256), 0, pn2_s(stream), dOut,
-                       ld_dout, ldo, out, arg, Y, ldy, affine, (C + 3) & ~3, G, K, C, dZp, red, make_coef_tail(tail, G * K));
+                       ld_dout, ldo, out, arg, Y, ldy, affine, (C + 3) & ~3, G, K, C, dZp, red);
     return pn2_launch_status();
 }
 
@@ -1990,18 +1939,17 @@ int pn2_pool_bwd_reduce_rec(const float *dOut, int ld_dout, const float *out, in
 }
 
 int pn2_pool_bwd_reduce(const float *dOut, int ldo, const float *out, const int32_t *arg, const float *Y, int ldy,
-                        const float *affine, int64_t G, int K, int C, float *dZp, double *red, const pn2_bn_coef_tail *tail,
-                        pn2_stream_t stream) {
-    return pn2_pool_bwd_reduce_ld(dOut, ldo, out, ldo, arg, Y, ldy, affine, G, K, C, dZp, red, tail, stream);
+                        const float *affine, int64_t G, int K, int C, float *dZp, double *red, pn2_stream_t stream) {
+    return pn2_pool_bwd_reduce_ld(dOut, ldo, out, ldo, arg, Y, ldy, affine, G, K, C, dZp, red, stream);
 }
 
 int pn2_relu_bwd_reduce(const float *dOut, int ldo, const float *out, const float *Y, int ldy, const float *affine,
-                        int64_t P, int C, float *dZ, int ldz, double *red, const pn2_bn_coef_tail *tail, pn2_stream_t stream) {
-    PN2_CHECK_ARG(dOut && out && Y && affine && dZ && red && P > 0 && C > 0 && coef_tail_ok(tail, red));
+                        int64_t P, int C, float *dZ, int ldz, double *red, pn2_stream_t stream) {
+    PN2_CHECK_ARG(dOut && out && Y && affine && dZ && red && P > 0 && C > 0);
     int64_t gy = pn2_cdiv(P, 4 * 16);
     if (gy > 512) gy = 512;
     hipLaunchKernelGGL(relu_bwd_reduce_kernel, dim3((unsigned)pn2_cdiv(C, 64), (unsigned)gy), dim3(256), 0, pn2_s(stream), dOut,
-                       ldo, out, Y, ldy, affine, (C + 3) & ~3, P, C, dZ, ldz, red, make_coef_tail(tail, P));
+                       ldo, out, Y, ldy, affine, (C + 3) & ~3, P, C, dZ, ldz, red);
     return pn2_launch_status();
 }
 
@@ -2016,19 +1964,16 @@ int pn2_bn_bwd_coef(const double *red, int64_t P, int C, const float *gamma, con
 // `job`: the weight-gradient half pn2_conv1x1_bwd_pair wants to ride in this launch (null for the plain entry point)
 static int conv1x1_dgrad_impl(const float *dZ, int ldz, const float *dZp, int ldo, const int32_t *arg, int Kpool, const float *Y, int ldy, const float *coef, const float *W, int ldw,
                               const float *prev_Y, int ld_prev, const float *prev_affine, float *dXout, int ldxo,
-                              double *prev_red, int64_t P, int K, int N, const pn2_bn_coef_tail *prev_tail, const pn2_bn_coef_lazy *coef_lazy,
-                              pn2_stream_t stream, PairJob *job) {
-    PN2_CHECK_ARG(Y && coef && W && dXout && P > 0 && P < (1LL << 31) && K > 0 && N > 0 && coef_tail_ok(prev_tail, prev_red) &&
-                  (prev_tail == nullptr || prev_Y != nullptr) && lazy_coef_ok(coef_lazy, coef, K));
+                              double *prev_red, int64_t P, int K, int N, const pn2_bn_coef_lazy *coef_lazy, pn2_stream_t stream, PairJob *job) {
+    PN2_CHECK_ARG(Y && coef && W && dXout && P > 0 && P < (1LL << 31) && K > 0 && N > 0 && lazy_coef_ok(coef_lazy, coef, K));
     LazyCoef lc = make_lazy_coef(coef_lazy);                            // realised by the FIRST launch below
-    const CoefTail ct = make_coef_tail(prev_tail, P);
     PN2_CHECK_ARG(dZ != nullptr || (dZp && arg && Kpool > 0 && P < (1LL << 31)));
     PN2_CHECK_ARG(ldw >= N && ldy % 4 == 0 && ldy >= round4(K) && ldxo % 4 == 0 && ldxo >= round4(N));
     const BMat bm = make_bmat(W, ldw, K, N);
     PN2_CHECK_ARG(prev_Y == nullptr || prev_affine != nullptr);
     const int K4 = round4(K), ldc = round4(K);
     hipStream_t s = pn2_s(stream);
-    if (prev_tail == nullptr && prev_Y != nullptr) {                    // wide layer: W stays in registers (mlp_wide.hip)
+    if (prev_Y != nullptr) {                                            // wide layer: W stays in registers (mlp_wide.hip)
         int64_t done = 0;
         const int rc = pn2_wide_dgrad(dZ, ldz, dZp, ldo, arg, Kpool, Y, ldy, coef, W, ldw, prev_Y, ld_prev, prev_affine, dXout, ldxo,
                                       prev_red, P, K, N, lc, s, &done);
@@ -2046,23 +1991,22 @@ static int conv1x1_dgrad_impl(const float *dZ, int ldz, const float *dZp, int ld
         LoadDyDense ld{dZ, ldz, Y, ldy, coef, ldc, zero_page_dev(), lc};
         if (prev_Y)
             return dispatch_nt<true>(ld, bm, P, K4, N,
-                                     EpiDgradMask{dXout, ldxo, prev_Y, ld_prev, prev_affine, round4(N), prev_red, ct, zero_page_dev()}, s, job);
+                                     EpiDgradMask{dXout, ldxo, prev_Y, ld_prev, prev_affine, round4(N), prev_red, zero_page_dev()}, s, job);
         return dispatch_nt<true>(ld, bm, P, K4, N, EpiStore{dXout, ldxo}, s, job);
     }
     PN2_CHECK_ARG(ldo % 4 == 0 && ldo >= K4);
     LoadDyPooled ld{dZp, ldo, arg, Kpool, Y, ldy, coef, ldc, zero_page_dev(), pow2_shift(Kpool), lc};
     if (prev_Y)
         return dispatch_nt<true>(ld, bm, P, K4, N,
-                                 EpiDgradMask{dXout, ldxo, prev_Y, ld_prev, prev_affine, round4(N), prev_red, ct, zero_page_dev()}, s, job);
+                                 EpiDgradMask{dXout, ldxo, prev_Y, ld_prev, prev_affine, round4(N), prev_red, zero_page_dev()}, s, job);
     return dispatch_nt<true>(ld, bm, P, K4, N, EpiStore{dXout, ldxo}, s, job);
 }
 
 int pn2_conv1x1_dgrad(const float *dZ, int ldz, const float *dZp, int ldo, const int32_t *arg, int Kpool, const float *Y, int ldy, const float *coef, const float *W, int ldw,
                       const float *prev_Y, int ld_prev, const float *prev_affine, float *dXout, int ldxo,
-                      double *prev_red, int64_t P, int K, int N, const pn2_bn_coef_tail *prev_tail, const pn2_bn_coef_lazy *coef_lazy,
-                      pn2_stream_t stream) {
+                      double *prev_red, int64_t P, int K, int N, const pn2_bn_coef_lazy *coef_lazy, pn2_stream_t stream) {
     return conv1x1_dgrad_impl(dZ, ldz, dZp, ldo, arg, Kpool, Y, ldy, coef, W, ldw, prev_Y, ld_prev, prev_affine, dXout, ldxo, prev_red, P, K, N,
-                              prev_tail, coef_lazy, stream, nullptr);
+                              coef_lazy, stream, nullptr);
 }
 
 int64_t pn2_conv1x1_wgrad_workspace_bytes(int64_t P, int M, int N, int pooled) { return pn2_wide_wgrad_workspace_bytes(P, M, N, pooled); }
@@ -2156,7 +2100,7 @@ int pn2_conv1x1_bwd_pair(const float *dZ, int ldz, const float *dZp, int ldo, co
                           (P <= small_p || (P <= 2 * (int64_t)small_p && (int64_t)M * N <= 16384));
     PairJob job{on && tn_small, false, X, ldx, x_affine, dW, lddw, M, N};
     const int rc = conv1x1_dgrad_impl(dZ, ldz, dZp, ldo, arg, Kpool, Y, ldy, coef, W, ldw, prev_Y, ld_prev, prev_affine, dXout, ldxo, prev_red, P,
-                                      C_out, C_in, nullptr, coef_lazy, stream, &job);
+                                      C_out, C_in, coef_lazy, stream, &job);
     const bool taken = job.taken;
     if (rc != PN2_OK || taken) return rc;
     const int rc2 = pn2_conv1x1_wgrad(dZ, ldz, dZp, ldo, arg, Kpool, Y, ldy, coef, X, ldx, x_affine, dW, lddw, nullptr, P, C_out, C_in, nullptr,

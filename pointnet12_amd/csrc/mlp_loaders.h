@@ -3,7 +3,7 @@
 // unit gets its own copy.
 #pragma once
 #include "pn2_common.h"
-#include "bn_tail.h"
+#include "bn_affine.h"
 #include <stdlib.h>
 
 namespace {
@@ -92,7 +92,7 @@ struct LoadPlain {          // X as stored
 
 struct LoadBnRelu {         // relu(bn(Y_prev)) formed from the pre-BN tensor
     const float *X; int ldx; const float *aff; const float *zp;
-    LazyBn lz;              // consumer-side BatchNorm: `aff` is filled from the producer's sums by the kernel's prologue (bn_tail.h)
+    LazyBn lz;              // consumer-side BatchNorm: `aff` is filled from the producer's sums by the kernel's prologue (bn_affine.h)
     __device__ __forceinline__ void prologue() const { lazy_bn_prologue(lz); }
     LoadBnRelu without_lazy() const { LoadBnRelu o = *this; o.lz = LazyBn{}; return o; }
     static constexpr int kRegs = 4;

@@ -185,7 +185,7 @@ __global__ __launch_bounds__(NTHR, 2) void bwd_res_kernel(ResDy dy, const float 
     const int G = gridDim.x;
 
     RABS(wave, 0)
-    lazy_coef_prologue(dy.lc);                                     // consumer-side BatchNorm backward (bn_tail.h)
+    lazy_coef_prologue(dy.lc);                                     // consumer-side BatchNorm backward (bn_affine.h)
     // ---- one-time: W^T, coefficient table
     for (int i = t; i < Co * Ci; i += NTHR) {
         const int co = i / Ci, ci = i - co * Ci;
@@ -1487,7 +1487,7 @@ __global__ __launch_bounds__(512, 2) void fwd_res_kernel(const float *__restrict
     float *Ab = atab + 3 * K + wave * (32 * LDA);                  // this wave's staging buffer [32][LDA]
     RABS(wave, 0)
 
-    lazy_bn_prologue(pool.lz);                                     // consumer-side BatchNorm (bn_tail.h)
+    lazy_bn_prologue(pool.lz);                                     // consumer-side BatchNorm (bn_affine.h)
     for (int i = t; i < N * QK; i += blockDim.x) {
         const int n = i / QK, q = i - n * QK;
         const float *src = W + (int64_t)n * ldw + 4 * q;
@@ -1795,7 +1795,7 @@ extern "C" int pn2_bwd_res_supported(int64_t P, int C_out, int C_in, int Kpool, 
     return 0;
 }
 
-// Called by pn2_conv1x1_fwd (mlp.hip) for supported shapes when no fused BatchNorm tail is requested; P % 32 == 0.
+// Called by pn2_conv1x1_fwd (mlp.hip) for supported shapes; P % 32 == 0.
 int pn2_fwd_res(const float *X, int ldx, const float *in_affine, const float *W, int ldw, const float *bias, float *Y, int ldy,
                 int64_t P, int K, int N, double *stats, LazyBn lz, hipStream_t s) {
     ResPool none{};
@@ -1910,7 +1910,7 @@ extern "C" int pn2_conv1x1_bwd(const float *dZ, int ldz, const float *dZp, int l
     const float *dZpt = dZ ? nullptr : dZp + g_off;
     const int32_t *argt = dZ ? nullptr : arg + g_off;
     rc = pn2_conv1x1_dgrad(dZt, ldz, dZpt, ldo, argt, Kpool, Y + P_full * ldy, ldy, coef, W, ldw, prev_affine ? prev_Y + P_full * ld_prev : nullptr,
-                           ld_prev, prev_affine, dXout + P_full * ldxo, ldxo, prev_red, tail, C_out, C_in, nullptr, coef_lazy, stream);
+                           ld_prev, prev_affine, dXout + P_full * ldxo, ldxo, prev_red, tail, C_out, C_in, coef_lazy, stream);
     if (rc != PN2_OK) return rc;
     return pn2_conv1x1_wgrad(dZt, ldz, dZpt, ldo, argt, Kpool, Y + P_full * ldy, ldy, coef, prev_Y + P_full * ld_prev, ld_prev, prev_affine,
                              dW, lddw, nullptr, tail, C_out, C_in, nullptr, stream);

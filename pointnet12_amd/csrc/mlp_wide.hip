@@ -76,7 +76,7 @@ __global__ __launch_bounds__(64 * NCB * RS) void regw_nt_kernel(const RegwArgs g
     const int cb = wave % NCB, rs = wave / NCB;
     const int n = cb * 32 + l31;                                    // this lane's output column
     const int N = g.N, K = g.K;
-    if (MODE == MODE_BNRELU) lazy_bn_prologue(g.lz);                // consumer-side BatchNorm (bn_tail.h): before `tab` is copied
+    if (MODE == MODE_BNRELU) lazy_bn_prologue(g.lz);                // consumer-side BatchNorm (bn_affine.h): before `tab` is copied
     if (DY) lazy_coef_prologue(g.lc);
 
     // ---- one-time: this lane's slice of W, the B operand of every MFMA it issues: w[4 kb + e] = W(n, k = 8 kb + 4 lh + e)

@@ -8,7 +8,7 @@
 // Here: the data gradient into per-source outputs, and the backward reduction of bn5, whose output feeds both the max over the
 // cloud (out_max) and convs1 (dense).
 #include "pn2_common.h"
-#include "bn_tail.h"
+#include "bn_affine.h"
 #include "mlp_loaders.h"
 
 namespace {
@@ -88,7 +88,7 @@ int pn2_conv1x1_dgrad_multi(const float *dZ, int ldz, const float *Y, int ldy, c
     k0 = 0;
     for (int i = 0; i < nsrc; ++i) {
         const int rc = pn2_conv1x1_dgrad(dZ, ldz, nullptr, 0, nullptr, 0, Y, ldy, coef, W + k0, ldw, nullptr, 0, nullptr, dX[i], lddx[i],
-                                         nullptr, P, M, K[i], nullptr, nullptr, stream);
+                                         nullptr, P, M, K[i], nullptr, stream);
         if (rc != PN2_OK) return rc;
         k0 += K[i];
     }

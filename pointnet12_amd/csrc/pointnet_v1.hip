@@ -7,7 +7,7 @@
 // Everything here streams rows: no MFMA, no fp32 atomics.  Sums that must be run-to-run identical (dT, the column sums) leave as
 // per-workgroup slabs in caller scratch and are added in a fixed order by a second launch.
 #include "pn2_common.h"
-#include "bn_tail.h"
+#include "bn_affine.h"
 #include "mlp_loaders.h"
 
 namespace {
@@ -368,7 +368,7 @@ int pn2_conv1x1_fwd_gbias(const float *X, int ldx, const float *W, int ldw, cons
                           int64_t rows_per_group, float *Y, int ldy, int64_t P, int K, int N, double *stats, pn2_stream_t stream) {
     PN2_CHECK_ARG(X && W && bias && gbias && Y && P > 0 && K > 0 && N > 0 && rows_per_group > 0 && P % rows_per_group == 0);
     PN2_CHECK_ARG(ldg >= N && ldy % 4 == 0 && ldy >= ((N + 3) & ~3));
-    int rc = pn2_conv1x1_fwd(X, ldx, nullptr, W, ldw, bias, Y, ldy, P, K, N, nullptr, nullptr, nullptr, stream);
+    int rc = pn2_conv1x1_fwd(X, ldx, nullptr, W, ldw, bias, Y, ldy, P, K, N, nullptr, nullptr, stream);
     if (rc != PN2_OK) return rc;
     const unsigned gx = (unsigned)pn2_cdiv((N + 3) & ~3, 256);
     int64_t wgs = (int64_t)pn2_num_cus() * 4 / gx;

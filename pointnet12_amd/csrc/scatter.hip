@@ -14,7 +14,7 @@
 // KITTI-shaped cloud has targets with hundreds of members next to targets with none: one-wave-per-target gathers ran
 // 2x SLOWER than the atomics), and ~10x fewer atomics than the element-wise scatter.
 #include "pn2_common.h"
-#include "bn_tail.h"
+#include "bn_affine.h"
 #include <stdlib.h>
 
 namespace {
@@ -259,7 +259,7 @@ __global__ __launch_bounds__(256) void group_affine_bwd_seg_kernel(const float *
                                                                    float *__restrict__ dWx, int ldwx,
                                                                    float *__restrict__ rep, LazyCoef lc) {
     __shared__ float red[256 * 12];
-    lazy_coef_prologue(lc);                            // consumer-side BatchNorm backward (bn_tail.h): `coef` filled here
+    lazy_coef_prologue(lc);                            // consumer-side BatchNorm backward (bn_affine.h): `coef` filled here
     const int t = threadIdx.x, lane = t & 63;
     const int LPR = 1 << lpr_log2, GPW = 64 >> lpr_log2;
     const int sub = lane & (LPR - 1);

@@ -98,7 +98,7 @@ class _ConvBnMax(torch.autograd.Function):
         aff = zb[8 * _REPL * 2 * co:].view(torch.float32)
         y = _empty_rows(P, co, dev)
         _check(lib.pn2_conv1x1_fwd(_p(x), ldx, None, _p(_contig_weight(w)), ci, _p(b), _p(y), y.shape[1], P, ci, co,
-                                   _p(stats) if training else None, None, None, st), "pn2_conv1x1_fwd")
+                                   _p(stats) if training else None, None, st), "pn2_conv1x1_fwd")
         _check(lib.pn2_bn_finalize(_p(stats), P, co, _p(gamma), _p(beta), eps, mom, int(training), _p(rmean), _p(rvar), _p(nbt),
                                    _p(aff), st), "pn2_bn_finalize")
         out = _empty_rows(G, co, dev)
@@ -139,7 +139,7 @@ class _ConvBnMax(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dx = torch.empty(P, x.shape[1], device=dev, dtype=torch.float32)
             _check(lib.pn2_conv1x1_dgrad(None, 0, _p(dzp), ldo, _p(arg), N, _p(y), y.shape[1], _p(coef), _p(_contig_weight(w)), ci,
-                                         None, 0, None, _p(dx), dx.shape[1], None, P, co, ci, None, None, st), "pn2_conv1x1_dgrad")
+                                         None, 0, None, _p(dx), dx.shape[1], None, P, co, ci, None, st), "pn2_conv1x1_dgrad")
         return dx, None, None, None, dW.view_as(w), db, dgamma, dbeta, None, None, None
 
 
@@ -174,7 +174,7 @@ class _GlobalConcatConv(torch.autograd.Function):
         aff = zb[8 * _REPL * 2 * co:8 * _REPL * 2 * co + 16 * _r4(co)].view(torch.float32)
         zero_bias = zb[8 * _REPL * 2 * co + 16 * _r4(co):].view(torch.float32)
         gterm = _empty_rows(B, co, dev)                # W_g g_b: one row per cloud
-        _check(lib.pn2_conv1x1_fwd(_p(g), cg, None, _p(wc), ct, _p(zero_bias), _p(gterm), gterm.shape[1], B, cg, co, None, None, None, st),
+        _check(lib.pn2_conv1x1_fwd(_p(g), cg, None, _p(wc), ct, _p(zero_bias), _p(gterm), gterm.shape[1], B, cg, co, None, None, st),
                "pn2_conv1x1_fwd")
         y = _empty_rows(P, co, dev)
         _check(lib.pn2_conv1x1_fwd_gbias(_p(pf), ldp, wc.data_ptr() + 4 * cg, ct, _p(b), _p(gterm), gterm.shape[1], N, _p(y), y.shape[1],
@@ -207,7 +207,7 @@ class _GlobalConcatConv(torch.autograd.Function):
         dW = rest[4 * _r4(co):4 * _r4(co) + co * ct].view(co, ct)
         db = rest[4 * _r4(co) + co * ct:]
         dZ = _empty_rows(P, co, dev)
-        _check(lib.pn2_relu_bwd_reduce(_p(grad), ldz, _p(z), _p(y), y.shape[1], _p(aff), P, co, _p(dZ), dZ.shape[1], _p(red), None, st),
+        _check(lib.pn2_relu_bwd_reduce(_p(grad), ldz, _p(z), _p(y), y.shape[1], _p(aff), P, co, _p(dZ), dZ.shape[1], _p(red), st),
                "pn2_relu_bwd_reduce")
         dgamma = torch.empty(co, device=dev, dtype=torch.float32)
         dbeta = torch.empty(co, device=dev, dtype=torch.float32)
@@ -221,7 +221,7 @@ class _GlobalConcatConv(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dpf = torch.empty(P, pf.shape[1], device=dev, dtype=torch.float32)
             _check(lib.pn2_conv1x1_dgrad(_p(dZ), dZ.shape[1], None, 0, None, 0, _p(y), ldy, _p(coef), wc.data_ptr() + 4 * cg, ct, None, 0,
-                                         None, _p(dpf), dpf.shape[1], None, P, co, cp, None, None, st), "pn2_conv1x1_dgrad")
+                                         None, _p(dpf), dpf.shape[1], None, P, co, cp, None, st), "pn2_conv1x1_dgrad")
         # per-cloud part: s_b = sum_{p in b} dY_p, then [B]-row GEMMs with the identity coefficients (dY := s)
         s = _empty_rows(B, co, dev)
         ws = torch.empty(int(lib.pn2_group_colsum_workspace_bytes(P, N, co)), device=dev, dtype=torch.uint8)
@@ -233,7 +233,7 @@ class _GlobalConcatConv(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             dg = torch.empty(B, cg, device=dev, dtype=torch.float32)
             _check(lib.pn2_conv1x1_dgrad(_p(s), s.shape[1], None, 0, None, 0, _p(s), s.shape[1], _p(ident), _p(wc), ct, None, 0, None,
-                                         _p(dg), cg, None, B, co, cg, None, None, st), "pn2_conv1x1_dgrad")
+                                         _p(dg), cg, None, B, co, cg, None, st), "pn2_conv1x1_dgrad")
         return dpf, dg, None, None, None, dW.view_as(w), db, dgamma, dbeta, None, None, None
 
 
@@ -429,7 +429,7 @@ class _DenseSegHead(torch.autograd.Function):
         # conv5 + bn5 + max over the cloud (the pre-BN output is kept: bn5 is applied by its consumers)
         y5 = _empty_rows(P, c5, dev)
         _check(lib.pn2_conv1x1_fwd(_p(o4), o4.shape[1], None, _p(_contig_weight(w5)), ci5, _p(b5), _p(y5), y5.shape[1], P, ci5, c5,
-                                   _p(stats5) if training else None, None, None, st), "pn2_conv1x1_fwd")
+                                   _p(stats5) if training else None, None, st), "pn2_conv1x1_fwd")
         eps, mom = cfg5
         _check(lib.pn2_bn_finalize(_p(stats5), P, c5, _p(g5), _p(be5), eps, mom, int(training), _p(rm5), _p(rv5), _p(nbt5), _p(aff5), st),
                "pn2_bn_finalize")
@@ -442,7 +442,7 @@ class _DenseSegHead(torch.autograd.Function):
             g = F.pad(g, (0, _r4(cg) - cg))
         wc = _contig_weight(ws1)
         gterm = _empty_rows(B, co, dev)
-        _check(lib.pn2_conv1x1_fwd(_p(g), g.shape[1], None, _p(wc), ct, _p(zero_bias), _p(gterm), gterm.shape[1], B, cg, co, None, None, None,
+        _check(lib.pn2_conv1x1_fwd(_p(g), g.shape[1], None, _p(wc), ct, _p(zero_bias), _p(gterm), gterm.shape[1], B, cg, co, None, None,
                                    st), "pn2_conv1x1_fwd")
         table = _lib.src_table([(_p(s), s.shape[1], s.shape[1], None, 0) for s in srcs] + [(_p(y5), y5.shape[1], c5, _p(aff5), 0)])
         y1 = _empty_rows(P, co, dev)
@@ -484,7 +484,7 @@ class _DenseSegHead(torch.autograd.Function):
         db5 = rest[o:o + c5]
         # bns1 + ReLU backward
         dZ1 = _empty_rows(P, co, dev)
-        _check(lib.pn2_relu_bwd_reduce(_p(g_seg), ld1, _p(z), _p(y1), ld1, _p(aff1), P, co, _p(dZ1), dZ1.shape[1], _p(red1), None, st),
+        _check(lib.pn2_relu_bwd_reduce(_p(g_seg), ld1, _p(z), _p(y1), ld1, _p(aff1), P, co, _p(dZ1), dZ1.shape[1], _p(red1), st),
                "pn2_relu_bwd_reduce")
         dgs1 = torch.empty(co, device=dev, dtype=torch.float32)
         dbes1 = torch.empty(co, device=dev, dtype=torch.float32)
@@ -511,7 +511,7 @@ class _DenseSegHead(torch.autograd.Function):
                                      _p(db1), B, co, cg, None, st), "pn2_conv1x1_wgrad")
         dg = torch.empty(B, g.shape[1], device=dev, dtype=torch.float32)
         _check(lib.pn2_conv1x1_dgrad(_p(s), s.shape[1], None, 0, None, 0, _p(s), s.shape[1], _p(ident), _p(wc), ct, None, 0, None, _p(dg),
-                                     dg.shape[1], None, B, co, cg, None, None, st), "pn2_conv1x1_dgrad")
+                                     dg.shape[1], None, B, co, cg, None, st), "pn2_conv1x1_dgrad")
         # bn5: the dense gradient from convs1 plus the pooled one (classification head + per-cloud part of convs1) at the arg-max rows
         dpool = dg[:, :c5]
         if g_max is not None:
@@ -529,7 +529,7 @@ class _DenseSegHead(torch.autograd.Function):
                                      None if training else _p(db5), P, c5, ci5, None, st), "pn2_conv1x1_wgrad")
         d4 = torch.empty(P, o4.shape[1], device=dev, dtype=torch.float32)
         _check(lib.pn2_conv1x1_dgrad(_p(d5), ld5, None, 0, None, 0, _p(y5), ld5, _p(coef5), _p(_contig_weight(w5)), ci5, None, 0, None, _p(d4),
-                                     d4.shape[1], None, P, c5, ci5, None, None, st), "pn2_conv1x1_dgrad")
+                                     d4.shape[1], None, P, c5, ci5, None, st), "pn2_conv1x1_dgrad")
         d4 += dsrc[3]
         dlabel = dg[:, c5:cg] if ctx.needs_input_grad[4] else None
         return (dsrc[0], dsrc[1], dsrc[2], d4, dlabel, None, None, None, None, dW5.view_as(w5), db5, dg5, dbe5, None, None, None,

@@ -539,11 +539,6 @@ class _InterpCat(torch.autograd.Function):
 # atomics on the weight gradient, for A/B runs
 DWX_REPLICAS_SCRATCH = os.environ.get("PN2_DWX_REPLICAS", "1") != "0"
 _DIRECT_GRADS = False
-# Statistics -> affine block / backward coefficients inside the kernel that finishes the reduction (the "tails" of
-# include/pn2.h) instead of pn2_bn_finalize / pn2_bn_bwd_coef launches.  Measured on MI355X: no gain (MSG-SemSeg
-# B=16 9.257 vs 9.245 ms, B=1 2.29 vs 2.33 ms; SSG 3.833 vs 3.827 ms) -- the last workgroup's ticket + device-scope
-# reads cost the same ~5 us as the dependent launch they replace -- so the stand-alone launches stay the default.
-FUSED_BN_TAILS = os.environ.get("PN2_FUSED_BN_TAILS", "0") == "1"
 # Consumer-side BatchNorm (round 4, ABI 8): the statistics -> affine block step and the reductions -> coefficients step run as a
 # prologue of the first kernel that READS the block (every workgroup recomputes it from the producer's finished fp64 sums) instead
 # of pn2_bn_finalize / pn2_bn_bwd_coef launches of their own -- 50 hops of ~5 us on the dependency chain of an MSG-SemSeg step, 44
@@ -560,25 +555,9 @@ POOL_IN_EPILOGUE = os.environ.get("PN2_POOL_EPILOGUE", "1") == "1"
 GATHER_CONV = os.environ.get("PN2_GATHER_CONV", "1") == "1"
 # MSG scales write their pooled outputs into column slices of one matrix instead of torch.cat; 0: A/B runs
 MSG_CONCAT_IN_PLACE = os.environ.get("PN2_MSG_CONCAT_IN_PLACE", "1") == "1"
-# Few-row layers (sa3 / fp3 / fp2 of the segmentation nets: P = 2 k .. 8 k rows) put ONE workgroup on a CU and keep its matrix
-# pipe ~30 % busy (csrc/mlp.hip, dispatch_nt_vec); their weight-gradient GEMM feeds nothing downstream, so it is issued on a
-# companion stream and shares the CUs with the data-gradient GEMM of the same layer.  0 = off (A/B); rows up to which it is done.
-WGRAD_SIDE_MAX_ROWS = int(os.environ.get("PN2_WGRAD_SIDE_MAX_ROWS", "0"))
-_wgrad_streams = {}
-
-
-def _wgrad_side_stream(device):
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
-    s = _wgrad_streams.get(key)
-    if s is None:
-        s = _wgrad_streams[key] = torch.cuda.Stream(device=device)
-    return s
-
 
 _REPL = 8                         # PN2_STAT_REPLICAS of include/pn2.h
 _PAIR_RUNS_SPLIT = set()          # (P, C_out, C_in, pooled, masked) shapes pn2_conv1x1_bwd_pair answered with PN2_OK_SPLIT
-_MALL_CHUNK_BYTES = 1 << 62       # row-chunked dgrad+wgrad pairing is OFF: measured 10.9 -> 13.1 ms/step at 96 MiB chunks
-                                  # (per-launch fixed costs beat the Infinity-Cache hits); kept as a tuning knob
 
 
 def set_direct_grad_accumulation(enabled):
@@ -634,18 +613,17 @@ class _SharedMLP(torch.autograd.Function):
         chans = [c_in] + [flat[7 * l].shape[0] for l in range(L)]
         n_stats = _REPL * 2 * sum(chans[1:]) if training else 0
         n_aff = 4 * sum(_r4(c) for c in chans[1:])
-        zero_bytes = _zeros_small(8 * n_stats + 4 * n_aff + 4 * L, dev)
+        zero_bytes = _zeros_small(8 * n_stats + 4 * n_aff, dev)
         stats = zero_bytes[:8 * n_stats].view(torch.float64) if training else None
         Ys, affs = [], []
         aff_all = zero_bytes[8 * n_stats:8 * n_stats + 4 * n_aff].view(torch.float32)
-        tickets = zero_bytes.data_ptr() + 8 * n_stats + 4 * n_aff      # one uint32 per fused BatchNorm tail
         aff_off = 0
         x, ldx, x_aff, off = rows, rows.shape[-1], None, 0
         pool_ws = None
         gather = geom is not None and len(geom) > 5 and bool(geom[5])      # (xyz, new_xyz, idx, xyz_first, None, True)
         gathered = None
         w_pads = {}
-        lazy_on = training and LAZY_BN and not FUSED_BN_TAILS
+        lazy_on = training and LAZY_BN
         lazy_prev = None                   # pn2_bn_lazy of the previous layer's block: realised by the next launch that reads it
         keep = []                          # (ctypes structures must outlive the calls that take their address)
 
@@ -655,7 +633,7 @@ class _SharedMLP(torch.autograd.Function):
             w, b, gamma, beta, rmean, rvar, nbt = flat[7 * l:7 * l + 7]
             co, ci = chans[l + 1], chans[l]
             pooled_last = (l == L - 1 and pool and training and x_aff is not None and POOL_IN_EPILOGUE and P % 32 == 0 and
-                           (pool == 16 or pool % 32 == 0) and co % 32 == 0 and not FUSED_BN_TAILS)
+                           (pool == 16 or pool % 32 == 0) and co % 32 == 0)
             # the pooled last layer of the long sa1 stacks: its pre-BN output is never written -- the backward runs on the layer's
             # input (pn2_conv1x1_bwd_cf) -- where the library has that form (csrc/mlp_res.hip: split_bwd_cf_kernel)
             no_y = bool(pooled_last and lazy_on and lib.pn2_conv1x1_bwd_cf_supported(P, co, ci, pool))
@@ -664,10 +642,6 @@ class _SharedMLP(torch.autograd.Function):
             aff = aff_all[aff_off:aff_off + 4 * _r4(co)]
             aff_off += 4 * _r4(co)
             eps, mom = bn_cfg[l]
-            fin = None
-            if training and FUSED_BN_TAILS:     # the producer of the statistics also turns them into the affine block
-                fin = ctypes.byref(_lib.BnFinalizeTail(tickets + 4 * l, _p(gamma), _p(beta), eps, mom, _p(rmean), _p(rvar),
-                                                       _p(nbt), _p(aff)))
             if l == 0 and gather:
                 # narrow first layer: gather + conv in one launch; the grouped rows are written once, for the backward
                 gathered = _empty_rows(P, ci, dev)
@@ -689,10 +663,10 @@ class _SharedMLP(torch.autograd.Function):
                     feat = torch.nn.functional.pad(feat, (0, ldd - gD))
                 zf = _empty_rows(gB * gN, co, dev)
                 _check(lib.pn2_conv1x1_fwd(_p(feat), ldd, None, wf_ptr, wf_ld, _p(b), _p(zf), zf.shape[1], gB * gN, gD, co,
-                                           None, None, None, st), "pn2_conv1x1_fwd")
+                                           None, None, st), "pn2_conv1x1_fwd")
                 _check(lib.pn2_group_affine_fwd(_p(zf), zf.shape[1], _p(g_xyz), _p(g_new), _p(g_idx), wx_ptr, ci, gB, gN, gS,
-                                                gK, co, _p(y), y.shape[1], _p(st_l), fin, st), "pn2_group_affine_fwd")
-            elif pooled_last and fin is None:
+                                                gK, co, _p(y), y.shape[1], _p(st_l), st), "pn2_group_affine_fwd")
+            elif pooled_last:
                 # last layer of a pooled MLP: the weight-resident kernel also records the per-group extrema of y, so the
                 # pooled output needs no second pass over Y (unsupported shapes: the plain launch + pn2_bn_relu_max below)
                 pool_ws = torch.empty(2 * (P // pool) * co, device=dev, dtype=torch.float32)
@@ -705,7 +679,7 @@ class _SharedMLP(torch.autograd.Function):
                 if rc == _lib.PN2_EUNSUPPORTED:
                     pool_ws = None
                     _check(lib.pn2_conv1x1_fwd(_p(x), ldx, _p(x_aff), _p(_contig_weight(w)), ci, _p(b), _p(y), y.shape[1], P, ci,
-                                               co, _p(st_l), fin, in_lazy(), st), "pn2_conv1x1_fwd")
+                                               co, _p(st_l), in_lazy(), st), "pn2_conv1x1_fwd")
                 else:
                     _check(rc, "pn2_conv1x1_fwd_pool")
             else:
@@ -713,13 +687,13 @@ class _SharedMLP(torch.autograd.Function):
                 if w_ld != ci:
                     w_pads[l] = w_rd                            # the data-gradient GEMM of the backward reads it too
                 _check(lib.pn2_conv1x1_fwd(_p(x), ldx, _p(x_aff), _p(w_rd), w_ld, _p(b), _p(y), y.shape[1], P, ci,
-                                           co, _p(st_l), fin, in_lazy(), st), "pn2_conv1x1_fwd")
+                                           co, _p(st_l), in_lazy(), st), "pn2_conv1x1_fwd")
             lazy_prev = None                                    # (whatever block the launch above read has been filled)
-            if fin is None and lazy_on:
+            if lazy_on:
                 # this layer's statistics become its affine block inside the next launch that reads the block
                 lazy_prev = _lib.BnLazy(_p(st_l), _p(gamma), _p(beta), eps, mom, _p(rmean), _p(rvar), _p(nbt), _p(aff), P, co)
                 keep.append(lazy_prev)
-            elif fin is None:
+            else:
                 _check(lib.pn2_bn_finalize(_p(st_l), P, co, _p(gamma), _p(beta), eps, mom, int(training),
                                            _p(rmean), _p(rvar), _p(nbt), _p(aff), st), "pn2_bn_finalize")
             Ys.append(y)
@@ -786,9 +760,8 @@ class _SharedMLP(torch.autograd.Function):
         n_red = _REPL * 2 * sum(chans[1:])
         direct = _direct_ok([ctx.params[7 * l + j] for l in range(L) for j in (0, 2, 3)])
         sizes = [4 * _r4(chans[l + 1]) + (0 if direct else chans[l + 1] * chans[l] + chans[l + 1]) for l in range(L)]
-        zero_bytes = _zeros_small(8 * n_red + 4 * sum(sizes) + 4 * L, dev)
+        zero_bytes = _zeros_small(8 * n_red + 4 * sum(sizes), dev)
         red = zero_bytes[:8 * n_red].view(torch.float64)
-        tickets = zero_bytes.data_ptr() + 8 * n_red + 4 * sum(sizes)   # one uint32 per fused BatchNorm tail
         offs = np.cumsum([0] + [_REPL * 2 * c for c in chans[1:]])
         K = pool if pool else 1
         G = P // K
@@ -808,15 +781,6 @@ class _SharedMLP(torch.autograd.Function):
                              torch.empty(co, device=dev, dtype=torch.float32),
                              zbuf[z0 + 4 * _r4(co):z0 + 4 * _r4(co) + co * ci].view(co, ci),
                              zbuf[z0 + 4 * _r4(co) + co * ci:z0 + 4 * _r4(co) + co * ci + co]))
-        coef_done = [False] * L
-
-        def coef_tail(l):
-            """The producer of layer l's reductions also turns them into coef_l / dgamma_l / dbeta_l (fused tail)."""
-            if not FUSED_BN_TAILS:
-                return None
-            coef_done[l] = True
-            return ctypes.byref(_lib.BnCoefTail(tickets + 4 * l, _p(gammas[l]), _p(affs[l]), int(training), _p(outs[l][0]),
-                                                _p(outs[l][1]), _p(outs[l][2]), int(direct)))
         dZ = None
         red_L = red[offs[L - 1]:offs[L]]
         dzp = None
@@ -830,25 +794,21 @@ class _SharedMLP(torch.autograd.Function):
         elif pool:
             dzp = torch.empty(G, ldo, device=dev, dtype=torch.float32)    # dOut masked by out > 0: the pooled form of dZ_L the GEMM loaders read (pitch ldo, as arg)
             _check(lib.pn2_pool_bwd_reduce_ld(_p(grad_out), ld_grad, _p(out), ldo, _p(arg), _p(Ys[-1]), Ys[-1].shape[1], _p(affs[-1]),
-                                              G, K, cl, _p(dzp), _p(red_L), coef_tail(L - 1), st), "pn2_pool_bwd_reduce_ld")
+                                              G, K, cl, _p(dzp), _p(red_L), st), "pn2_pool_bwd_reduce_ld")
         else:
             dZ = _empty_rows(P, cl, dev)
             _check(lib.pn2_relu_bwd_reduce(_p(grad_out), ldo, _p(out), _p(Ys[-1]), Ys[-1].shape[1], _p(affs[-1]), P, cl,
-                                           _p(dZ), dZ.shape[1], _p(red_L), coef_tail(L - 1), st), "pn2_relu_bwd_reduce")
+                                           _p(dZ), dZ.shape[1], _p(red_L), st), "pn2_relu_bwd_reduce")
         grads = [None] * (7 * L)
         d_rows = None
         # sa1-style stacks (a first layer on the 48-byte grouped rows, nobody needs d rows): the second layer's fused backward forms
         # the first layer's sum dZ^T x from its dX tiles (pn2_conv1x1_bwd_first) -- dZ1 is never written -- and the first layer's
         # weight gradient finishes from the input's moments (pn2_conv1x1_wgrad_cf with dZ == NULL)
         fuse_first = bool(L >= 3 and ctx.gather is not None and not ctx.needs_input_grad[0] and training and WGRAD_CF and LAZY_BN and
-                          not FUSED_BN_TAILS and chans[0] <= 12 and chans[1] % 16 == 0 and chans[1] <= 128 and rows.shape[1] % 4 == 0 and
+                          chans[0] <= 12 and chans[1] % 16 == 0 and chans[1] <= 128 and rows.shape[1] % 4 == 0 and
                           rows.shape[1] >= 12 and Ys[1] is not None and
                           lib.pn2_conv1x1_bwd_first_supported(P, chans[2], chans[1], chans[0]))
         first_scratch = None
-        side, side_used = None, False
-        if 0 < P <= WGRAD_SIDE_MAX_ROWS:
-            main_stream = torch.cuda.current_stream(dev)
-            side = _wgrad_side_stream(dev)
         for l in range(L - 1, -1, -1):
             co, ci = chans[l + 1], chans[l]
             y, aff = Ys[l], affs[l]
@@ -860,11 +820,11 @@ class _SharedMLP(torch.autograd.Function):
             first_layer_special = l == 0 and ctx.geom is not None and ctx.gather is None
             # (the factorised first layer: its segmented scatter kernel is the consumer; the atomics form is not)
             seg_ok = not first_layer_special or (ctx.geom[4] is not None and co <= 256)
-            if not coef_done[l] and training and LAZY_BN and seg_ok:
+            if training and LAZY_BN and seg_ok:
                 cl_struct = _lib.BnCoefLazy(_p(red[offs[l]:offs[l + 1]]), _p(gammas[l]), _p(aff), _p(coef), _p(dgamma), _p(dbeta),
                                             int(direct), P, co)
                 coef_lazy = ctypes.byref(cl_struct)
-            elif not coef_done[l]:
+            else:
                 _check(lib.pn2_bn_bwd_coef(_p(red[offs[l]:offs[l + 1]]), P, co, _p(gammas[l]), _p(aff), int(training),
                                            _p(coef), _p(dgamma), _p(dbeta), int(direct), st), "pn2_bn_bwd_coef")
             if not direct:
@@ -910,14 +870,15 @@ class _SharedMLP(torch.autograd.Function):
                     grads[7 * l] = dW.view_as(Ws[l])
                 dZ = dx
                 continue
-            if (need_dx and training and not FUSED_BN_TAILS and
+            # the two forms of dZ the kernels take: dense rows, or the pooled pair (dZp, arg) with K rows per group
+            c_dz = (None, 0) if pooled else (_p(dZ), dZ.shape[1])
+            c_pool = (_p(dzp), ldo, _p(arg), K) if pooled else (None, 0, None, 0)
+            if (need_dx and training and
                     lib.pn2_bwd_res_supported(P, co, ci, K if pooled else 0, int(x_aff is not None))):
                 # narrow, long layer: dgrad + wgrad in ONE pass over dZ / Y / Y_prev, weights resident in LDS (mlp_res.hip)
                 dx = _empty_rows(P, ci, dev) if l > 0 else torch.empty(P, ldx, device=dev, dtype=torch.float32)
                 if l == 0:
                     d_rows = dx
-                c_dz = (None, 0) if pooled else (_p(dZ), dZ.shape[1])
-                c_pool = (_p(dzp), ldo, _p(arg), K) if pooled else (None, 0, None, 0)
                 _check(lib.pn2_conv1x1_bwd(*c_dz, *c_pool, _p(y), ldy, _p(coef), _p(_contig_weight(Ws[l])), ci, _p(x), ldx,
                                            _p(x_aff), _p(dx), dx.shape[1], _p(red[offs[l - 1]:offs[l]]) if l > 0 else None,
                                            _p(dW), ci, P, co, ci, coef_lazy, st), "pn2_conv1x1_bwd")
@@ -936,83 +897,49 @@ class _SharedMLP(torch.autograd.Function):
                     dx = _empty_rows(P, ci, dev)
                 else:
                     dx = d_rows = torch.empty(P, ldx, device=dev, dtype=torch.float32)   # pad lanes written (0) by the GEMM
-            # dgrad and wgrad of one layer read the same dZ / Y rows.  Run them back to back on row chunks small
-            # enough to stay in the 256 MiB Infinity Cache, so the second kernel's operand stream is served on-die
-            # instead of from HBM (both only accumulate: fp64 reductions / fp32 weight gradients).
-            row_bytes = 4 * ((1 if pooled else 2) * ldy + 2 * ldx)
-            chunk = P
-            if need_dx and P * row_bytes > _MALL_CHUNK_BYTES:
-                chunk = max(_MALL_CHUNK_BYTES // row_bytes, 1 << 14)
-                chunk -= chunk % (K * 128)                    # whole pooling groups, whole row tiles
-                chunk = max(chunk, K * 128)
-            for r0 in range(0, P, chunk):
-                rn = min(chunk, P - r0)
-                c_dz = (None, 0) if pooled else (dZ.data_ptr() + 4 * r0 * dZ.shape[1], dZ.shape[1])
-                c_pool = (dzp.data_ptr() + 4 * (r0 // K) * ldo, ldo, arg.data_ptr() + 4 * (r0 // K) * ldo, K) if pooled \
-                    else (None, 0, None, 0)
-                c_y = y.data_ptr() + 4 * r0 * ldy
-                c_x = x.data_ptr() + 4 * r0 * ldx
-                pair_key = (P, co, ci, pooled, l > 0)
-                if (need_dx and BWD_PAIR and training and chunk == P and side is None and not FUSED_BN_TAILS and
-                        pair_key not in _PAIR_RUNS_SPLIT):
-                    # data gradient and weight gradient of this layer as ONE call: on the few-row / mid-size layers both kernel
-                    # bodies share one launch (pn2_conv1x1_bwd_pair); elsewhere the library issues the two launches itself
-                    prev = (c_x, ldx, _p(x_aff), dx.data_ptr(), dx.shape[1], _p(red[offs[l - 1]:offs[l]])) if l > 0 else \
-                        (None, 0, None, dx.data_ptr(), ldx, None)
-                    rc = lib.pn2_conv1x1_bwd_pair(*c_dz, *c_pool, c_y, ldy, _p(coef), w_l, w_ld, *prev, c_x, ldx, _p(x_aff), _p(dW), ci,
-                                                  rn, co, ci, coef_lazy, st)
-                    if rc != _lib.PN2_OK_SPLIT:                 # (1: done as two launches -- not an error)
-                        _check(rc, "pn2_conv1x1_bwd_pair")
-                    else:
-                        # the library ran this shape as pn2_conv1x1_dgrad + pn2_conv1x1_wgrad: from now on those two calls are made
-                        # here (same launches, same results) -- a per-launch accounting (bench.py) then sees each kernel by itself
-                        _PAIR_RUNS_SPLIT.add(pair_key)
-                    coef_lazy = None
-                    continue
+            pair_key = (P, co, ci, pooled, l > 0)
+            if need_dx and BWD_PAIR and training and pair_key not in _PAIR_RUNS_SPLIT:
+                # data gradient and weight gradient of this layer as ONE call: on the few-row / mid-size layers both kernel
+                # bodies share one launch (pn2_conv1x1_bwd_pair); elsewhere the library issues the two launches itself
+                prev = (_p(x), ldx, _p(x_aff), _p(dx), dx.shape[1], _p(red[offs[l - 1]:offs[l]])) if l > 0 else \
+                    (None, 0, None, _p(dx), ldx, None)
+                rc = lib.pn2_conv1x1_bwd_pair(*c_dz, *c_pool, _p(y), ldy, _p(coef), w_l, w_ld, *prev, _p(x), ldx, _p(x_aff), _p(dW), ci,
+                                              P, co, ci, coef_lazy, st)
+                if rc != _lib.PN2_OK_SPLIT:                 # (1: done as two launches -- not an error)
+                    _check(rc, "pn2_conv1x1_bwd_pair")
+                else:
+                    # the library ran this shape as pn2_conv1x1_dgrad + pn2_conv1x1_wgrad: from now on those two calls are made
+                    # here (same launches, same results) -- a per-launch accounting (bench.py) then sees each kernel by itself
+                    _PAIR_RUNS_SPLIT.add(pair_key)
+            else:
                 if need_dx:
-                    c_dx = dx.data_ptr() + 4 * r0 * dx.shape[1]
                     if l > 0:
-                        _check(lib.pn2_conv1x1_dgrad(*c_dz, *c_pool, c_y, ldy, _p(coef), w_l, w_ld, c_x, ldx, _p(x_aff), c_dx,
-                                                     dx.shape[1], _p(red[offs[l - 1]:offs[l]]), rn, co, ci,
-                                                     coef_tail(l - 1) if chunk == P else None, coef_lazy, st), "pn2_conv1x1_dgrad")
+                        _check(lib.pn2_conv1x1_dgrad(*c_dz, *c_pool, _p(y), ldy, _p(coef), w_l, w_ld, _p(x), ldx, _p(x_aff), _p(dx),
+                                                     dx.shape[1], _p(red[offs[l - 1]:offs[l]]), P, co, ci, coef_lazy, st), "pn2_conv1x1_dgrad")
                     else:
-                        _check(lib.pn2_conv1x1_dgrad(*c_dz, *c_pool, c_y, ldy, _p(coef), w_l, w_ld, None, 0, None, c_dx,
-                                                     ldx, None, rn, co, ci, None, coef_lazy, st), "pn2_conv1x1_dgrad")
+                        _check(lib.pn2_conv1x1_dgrad(*c_dz, *c_pool, _p(y), ldy, _p(coef), w_l, w_ld, None, 0, None, _p(dx),
+                                                     ldx, None, P, co, ci, coef_lazy, st), "pn2_conv1x1_dgrad")
                     coef_lazy = None                            # filled: the weight gradient below reads it
-                if (WGRAD_CF and l == 0 and training and not need_dx and not pooled and ci <= 15 and co % 16 == 0 and co <= 128
-                        and chunk == P):
+                if WGRAD_CF and l == 0 and training and not need_dx and not pooled and ci <= 15 and co % 16 == 0 and co <= 128:
                     # first layer without a data gradient: the BatchNorm-backward terms of dY in closed form from the input rows'
                     # first and second moments -- the pass reads dZ and the rows, not Y (pn2_conv1x1_wgrad_cf, include/pn2.h)
                     scratch = _zeros_small(int(lib.pn2_conv1x1_wgrad_cf_scratch_bytes()), dev)
-                    _check(lib.pn2_conv1x1_wgrad_cf(c_dz[0], c_dz[1], _p(coef), c_x, ldx, _p(_contig_weight(Ws[l])), ci,
-                                                    _p(flat[7 * l + 1]), _p(scratch), _p(dW), ci, rn, co, ci, coef_lazy, st),
+                    _check(lib.pn2_conv1x1_wgrad_cf(*c_dz, _p(coef), _p(x), ldx, _p(_contig_weight(Ws[l])), ci,
+                                                    _p(flat[7 * l + 1]), _p(scratch), _p(dW), ci, P, co, ci, coef_lazy, st),
                            "pn2_conv1x1_wgrad_cf")
-                    coef_lazy = None
-                    continue
-                if side is not None and chunk == P:
-                    # the weight gradient on the companion stream: ordered behind everything issued so far on this stream (the
-                    # coefficients, dZ), joined once at the end of this backward
-                    side.wait_stream(main_stream)
-                    with torch.cuda.stream(side):
-                        _check(lib.pn2_conv1x1_wgrad(*c_dz, *c_pool, c_y, ldy, _p(coef), c_x, ldx, _p(x_aff), _p(dW), ci,
-                                                     None if training else _p(dbias), rn, co, ci, coef_lazy, _lib.stream()), "pn2_conv1x1_wgrad")
-                    side_used = True
                 else:
-                    ws_bytes = lib.pn2_conv1x1_wgrad_workspace_bytes(rn, co, ci, int(pooled)) if training else 0
+                    ws_bytes = lib.pn2_conv1x1_wgrad_workspace_bytes(P, co, ci, int(pooled)) if training else 0
                     if ws_bytes:                                # two-phase dW flush of the full-tile kernel: caller scratch
                         ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
-                        _check(lib.pn2_conv1x1_wgrad_ws(*c_dz, *c_pool, c_y, ldy, _p(coef), c_x, ldx, _p(x_aff), _p(dW), ci, None, rn, co, ci,
+                        _check(lib.pn2_conv1x1_wgrad_ws(*c_dz, *c_pool, _p(y), ldy, _p(coef), _p(x), ldx, _p(x_aff), _p(dW), ci, None, P, co, ci,
                                                         coef_lazy, _p(ws), st), "pn2_conv1x1_wgrad_ws")
                     else:
-                        _check(lib.pn2_conv1x1_wgrad(*c_dz, *c_pool, c_y, ldy, _p(coef), c_x, ldx, _p(x_aff), _p(dW), ci,
-                                                     None if training else _p(dbias), rn, co, ci, coef_lazy, st), "pn2_conv1x1_wgrad")
-                coef_lazy = None
+                        _check(lib.pn2_conv1x1_wgrad(*c_dz, *c_pool, _p(y), ldy, _p(coef), _p(x), ldx, _p(x_aff), _p(dW), ci,
+                                                     None if training else _p(dbias), P, co, ci, coef_lazy, st), "pn2_conv1x1_wgrad")
             if not direct:
                 grads[7 * l] = dW.view_as(Ws[l])
             if l > 0:
                 dZ = dx
-        if side_used:
-            main_stream.wait_stream(side)
         if ctx.gather is not None and d_rows is not None:          # gradient of the grouped rows -> the gathered source points
             gB, gN, gD = ctx.gather
             g_idx = ctx.geom[2]
@@ -1059,7 +986,7 @@ class _SharedMLP(torch.autograd.Function):
                 wf_ptr, wf_ld = ctx.w_pads["wf"].data_ptr(), ctx.w_pads["wf"].shape[1]
             dF = _empty_rows(B * N, D, dev)
             _check(lib.pn2_conv1x1_dgrad(_p(G), ldc, None, 0, None, 0, _p(G), ldc, _p(ident), wf_ptr, wf_ld, None, 0, None,
-                                         _p(dF), ldd, None, B * N, co, D, None, None, st), "pn2_conv1x1_dgrad")
+                                         _p(dF), ldd, None, B * N, co, D, None, st), "pn2_conv1x1_dgrad")
             d_feats = (dF[:, :D] if ldd != D else dF).reshape(B, N, D)
         return d_feats, (dW.view_as(w) if w_grad is None else None)
 
@@ -1079,7 +1006,7 @@ class _Conv1x1(torch.autograd.Function):
         ci = weight.numel() // co
         y = _empty_rows(P, co, rows.device)
         _check(lib.pn2_conv1x1_fwd(_p(rows), ldx, None, _p(_contig_weight(weight)), ci, _p(bias), _p(y), y.shape[1], P, ci, co,
-                                   None, None, None, st), "pn2_conv1x1_fwd")
+                                   None, None, st), "pn2_conv1x1_fwd")
         ctx.save_for_backward(rows, weight)
         ctx.params = (weight, bias)             # leaf parameters (no grad_fn): no reference cycle
         ctx.dims = (P, ci, co, ldx, y.shape[1])
@@ -1114,7 +1041,7 @@ class _Conv1x1(torch.autograd.Function):
             d_rows = torch.empty(P, ldx, device=dev, dtype=torch.float32)     # pad lanes written (0) by the GEMM
             _check(lib.pn2_conv1x1_dgrad(_p(g), ldy, None, 0, None, 0, _p(g), ldy, _p(ident), _p(_contig_weight(weight)), ci,
                                          None, 0, None,
-                                         _p(d_rows), ldx, None, P, co, ci, None, None, st), "pn2_conv1x1_dgrad")
+                                         _p(d_rows), ldx, None, P, co, ci, None, st), "pn2_conv1x1_dgrad")
         if direct:
             return d_rows, None, None, None
         return d_rows, dW.view_as(weight), db, None
@@ -1314,7 +1241,7 @@ def grouped_mlp(xyz, points, new_xyz, idx, xyz_first, convs, bns, training, inv=
     if _factorised(D, len(convs), training):
         flat, cfg = _flat_params(convs, bns)
         return _SharedMLP.apply(points, 3 + D, K, training, cfg, (xyz, new_xyz, idx, xyz_first, inv), dest, *flat)
-    if (GATHER_CONV and not FUSED_BN_TAILS and 1 <= D <= 9 and convs[0].out_channels in (32, 64) and (B * S * K) % 64 == 0 and new_xyz is not None and
+    if (GATHER_CONV and 1 <= D <= 9 and convs[0].out_channels in (32, 64) and (B * S * K) % 64 == 0 and new_xyz is not None and
             idx is not None):
         # narrow first layer (the sa1 stacks): pn2_group and the first conv are one launch (pn2_group_conv_fwd)
         flat, cfg = _flat_params(convs, bns)

@@ -15,8 +15,19 @@ def header_functions():
     return sorted(set(re.findall(r"\b(pn2_[a-z0-9_]+)\s*\(", text)))
 
 
+def header_parameter_counts():
+    """{name: number of parameters} of every prototype in the header (`(void)` counts as none)."""
+    text = open(os.path.join(ROOT, "include", "pn2.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    protos = re.findall(r"\b(pn2_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text)
+    return {name: 0 if params.strip() in ("", "void") else params.count(",") + 1 for name, params in protos}
+
+
 def test_header_matches_binding_table():
     assert header_functions() == sorted(_lib.SIGNATURES)
+    counts = header_parameter_counts()
+    assert sorted(counts) == sorted(_lib.SIGNATURES)
+    assert counts == {name: len(args) for name, (_, args) in _lib.SIGNATURES.items()}
 
 
 def test_library_exports_every_symbol():

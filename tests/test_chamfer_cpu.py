@@ -86,11 +86,11 @@ def test_fixture_pins_zero_rows_and_ties():
 
 def test_abi_14_entry_points():
     text = open(os.path.join(ROOT, "include", "pn2.h")).read()
-    assert re.search(r"#define\s+PN2_ABI_VERSION\s+14\b", text) and _lib.ABI_VERSION == 14
+    assert re.search(r"#define\s+PN2_ABI_VERSION\s+15\b", text) and _lib.ABI_VERSION == 15
     for name in ("pn2_chamfer_nn", "pn2_chamfer_nn_workspace_bytes", "pn2_chamfer_bwd"):
         assert name in _lib.SIGNATURES and re.search(r"\b%s\s*\(" % name, text), name
     lib = _lib.load()
-    assert lib.pn2_version() == 14
+    assert lib.pn2_version() == 15
     # argument checks and the workspace query are host code: no GPU needed
     assert lib.pn2_chamfer_nn(None, None, 1, 1, 1, 3, None, None, None, None, None) == -1
     assert lib.pn2_chamfer_bwd(None, None, None, None, None, 1, 1, 1, 3, None, None, None) == -1

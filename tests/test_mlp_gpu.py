@@ -690,7 +690,7 @@ def test_wide_dgrad_and_wgrad_kernels_vs_fp64_on_fixed_operands(dev, P, co, ci, 
     red = torch.zeros(8 * 2 * ci, device=dev, dtype=torch.float64)
     dW = torch.zeros(co, ci, device=dev)
     rc = lib.pn2_conv1x1_dgrad(*c["dz_args"], c["Y"].data_ptr(), c["ldc"], c["coef"].data_ptr(), c["W"].data_ptr(), ci, c["Yp"].data_ptr(), c["ldp"],
-                               c["affp"].data_ptr(), dX.data_ptr(), c["ldp"], red.data_ptr(), P, co, ci, None, None, st)
+                               c["affp"].data_ptr(), dX.data_ptr(), c["ldp"], red.data_ptr(), P, co, ci, None, st)
     assert rc == 0
     rc = lib.pn2_conv1x1_wgrad(*c["dz_args"], c["Y"].data_ptr(), c["ldc"], c["coef"].data_ptr(), c["Yp"].data_ptr(), c["ldp"], c["affp"].data_ptr(),
                                dW.data_ptr(), ci, None, P, co, ci, None, st)

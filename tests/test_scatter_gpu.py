@@ -435,7 +435,7 @@ def _affine_fwd(dev, B, N, S, K, C, idx3, xyz, ctr, full_weight, seed):
         Y = sentinel((P, ldy), dev)
         stats = torch.zeros(8 * 2 * C, dtype=torch.float64, device=dev)          # PN2_STAT_REPLICAS copies
         assert lib.pn2_group_affine_fwd(Zf.data_ptr(), ldz, xyz.data_ptr(), ctr.data_ptr(), idx3.data_ptr(), W.data_ptr() + 4 * Dw, 3 + Dw,
-                                        B, N, S, K, C, Y.data_ptr(), ldy, stats.data_ptr() if with_stats else None, None, st) == 0
+                                        B, N, S, K, C, Y.data_ptr(), ldy, stats.data_ptr() if with_stats else None, st) == 0
         outs.append(Y)
         err = (Y[:, :C].double() - Yref).abs()
         tol = 5 * R.U32 * mag                          # one rounded difference and three fmas (shown valid in test_scatter_ref_cpu.py)

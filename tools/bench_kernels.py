@@ -102,7 +102,7 @@ def main():
             aff = affine(K) if K > 12 else None
 
             def fn():
-                rc = lib.pn2_conv1x1_fwd(p(X), r4(K), p(aff), p(W), K, p(bias), p(Y), r4(N), P, K, N, p(stats), None, None, st)
+                rc = lib.pn2_conv1x1_fwd(p(X), r4(K), p(aff), p(W), K, p(bias), p(Y), r4(N), P, K, N, p(stats), None, st)
                 assert rc == 0
             report("fwd", (P, K, N), timeit(fn, args.reps), 2.0 * P * K * N, 4.0 * (P * K + P * N + N * K))
             for Kp in (16, 32, 64):              # the same GEMM with the pooling extrema recorded in its epilogue
@@ -165,7 +165,7 @@ def main():
 
                 def fn():
                     rc = lib.pn2_conv1x1_dgrad(*dz, p(Y), r4(Cl), p(coef), p(Wt), Cp, p(Yp), r4(Cp), p(affp), p(dX), r4(Cp),
-                                               p(red), P, Cl, Cp, None, None, st)
+                                               p(red), P, Cl, Cp, None, st)
                     assert rc == 0
                 report("dgrad", (P, Cl, Cp, Kp), timeit(fn, args.reps), 2.0 * P * Cl * Cp, 4.0 * (dy_bytes + 2 * P * Cp))
             elif which == "pair":              # dgrad + wgrad as one call (one launch where the pair kernel takes the shape)

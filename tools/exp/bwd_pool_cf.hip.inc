@@ -306,7 +306,7 @@ __global__ __launch_bounds__(512, 2) void bwd_pool_cf_kernel(const float *__rest
 // Workgroup j < Ci: row j of G (thread i: column i, W[c, i] coalesced, W[c, j] broadcast); workgroup Ci: h.
 __global__ __launch_bounds__(128) void bwd_pool_cf_prep_kernel(const float *__restrict__ coef, int Co, const float *__restrict__ W, int ldw,
                                                                const float *__restrict__ bias, int Ci, float *__restrict__ Gm, LazyCoef lc) {
-    lazy_coef_prologue(lc);                                        // (every workgroup recomputes the block: bn_tail.h)
+    lazy_coef_prologue(lc);                                        // (every workgroup recomputes the block: bn_affine.h)
     const int j = blockIdx.x, i = threadIdx.x;
     if (i >= Ci) return;
     double v = 0.0;

@@ -38,10 +38,10 @@ def main(trials=120):
         big.mul_(1.0001)
 
     def k_fwd_plain():          # gemm / split forward 64 -> 96, no input BatchNorm
-        assert lib.pn2_conv1x1_fwd(p(X64), 64, None, p(W96), 64, p(b96), p(Y96), 96, P, 64, 96, p(st96), None, None, main_s) == 0
+        assert lib.pn2_conv1x1_fwd(p(X64), 64, None, p(W96), 64, p(b96), p(Y96), 96, P, 64, 96, p(st96), None, main_s) == 0
 
     def k_fwd_bn():             # split_nt forward 64 -> 96 with BN + ReLU in the loader
-        assert lib.pn2_conv1x1_fwd(p(X64), 64, p(aff64), p(W96), 64, p(b96), p(Y96), 96, P, 64, 96, p(st96), None, None, main_s) == 0
+        assert lib.pn2_conv1x1_fwd(p(X64), 64, p(aff64), p(W96), 64, p(b96), p(Y96), 96, P, 64, 96, p(st96), None, main_s) == 0
 
     def k_fwd_pool():           # split_nt pooled forward 96 -> 128 (two four-wave workgroups per CU)
         assert lib.pn2_conv1x1_fwd_pool(p(X96), 96, p(aff96), p(W128), 96, p(b128), p(Y128), 128, P, 96, 128, p(st128), 128, p(b128), p(ws), None, main_s) == 0
@@ -60,7 +60,7 @@ def main(trials=120):
         _lib.set_option("PN2_SPLIT_NARROW", 1)
 
     def k_fwd_96_128_plainepi():  # the same GEMM without the pooling epilogue
-        assert lib.pn2_conv1x1_fwd(p(X96), 96, p(aff96), p(W128), 96, p(b128), p(Y128), 128, P, 96, 128, p(st128), None, None, main_s) == 0
+        assert lib.pn2_conv1x1_fwd(p(X96), 96, p(aff96), p(W128), 96, p(b128), p(Y128), 128, P, 96, 128, p(st128), None, main_s) == 0
 
     A_ = torch.randn(8192, 8192, device=dev)
     B_ = torch.randn(8192, 8192, device=dev)

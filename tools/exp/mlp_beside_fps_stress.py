@@ -42,7 +42,7 @@ def main(trials=100):
     def fwd_dense():
         Y = torch.empty(P, 96, device=dev)
         st = torch.zeros(8 * 2 * 96, device=dev, dtype=torch.float64)
-        assert lib.pn2_conv1x1_fwd(p(X64), 64, p(aff64), p(W96), 64, p(b96), p(Y), 96, P, 64, 96, p(st), None, None, main_s) == 0
+        assert lib.pn2_conv1x1_fwd(p(X64), 64, p(aff64), p(W96), 64, p(b96), p(Y), 96, P, 64, 96, p(st), None, main_s) == 0
         return (Y,)
 
     side = torch.cuda.Stream(device=dev)

@@ -68,11 +68,11 @@ for P, K, N in [(1048576, 96, 128), (1048576, 64, 96)]:
     X = rnd(P, K); W = rnd(N, K); b = rnd(N); Y = torch.empty(P, N, device=dev)
     stats = torch.zeros(16 * N, device=dev, dtype=torch.float64); aff = affine(K)
     for _ in range(3):
-        assert lib.pn2_conv1x1_fwd(p(X), K, p(aff), p(W), K, p(b), p(Y), N, P, K, N, p(stats), None, None, st) == 0
+        assert lib.pn2_conv1x1_fwd(p(X), K, p(aff), p(W), K, p(b), p(Y), N, P, K, N, p(stats), None, st) == 0
     import time
     torch.cuda.synchronize(); t_0 = time.perf_counter()
     for _ in range(20):
-        lib.pn2_conv1x1_fwd(p(X), K, p(aff), p(W), K, p(b), p(Y), N, P, K, N, p(stats), None, None, st)
+        lib.pn2_conv1x1_fwd(p(X), K, p(aff), p(W), K, p(b), p(Y), N, P, K, N, p(stats), None, st)
     torch.cuda.synchronize()
     print("fwd", (P, K, N), "%.1f us per launch, 20 back to back" % ((time.perf_counter() - t_0) / 20 * 1e6))
     dump(["transform", "fetch", "mfma", "epilogue(last)", "epilogue", "", "", ""])

@@ -59,7 +59,7 @@ for P, K, N in [(262144, 196, 256), (131072, 128, 256), (262144, 128, 196), (131
     stats = torch.zeros(8 * 2 * N, device=dev, dtype=torch.float64)
     aff = affine(K)
     for _ in range(5):
-        assert lib.pn2_conv1x1_fwd(p(X), r4(K), p(aff), p(W), K, p(bias), p(Y), r4(N), P, K, N, p(stats), None, None, st) == 0
+        assert lib.pn2_conv1x1_fwd(p(X), r4(K), p(aff), p(W), K, p(bias), p(Y), r4(N), P, K, N, p(stats), None, st) == 0
     torch.cuda.synchronize()
     print("fwd", (P, K, N))
     dump()
@@ -84,8 +84,7 @@ if os.environ.get("PN2_RING") != "1":
         dX = torch.empty(P, r4(Cp), device=dev)
         red = torch.zeros(8 * 2 * Cp, device=dev, dtype=torch.float64)
         for _ in range(5):
-            assert lib.pn2_conv1x1_dgrad(*dz, p(Y), r4(Cl), p(coef), p(Wt), Cp, p(Yp), r4(Cp), p(affp), p(dX), r4(Cp), p(red), P, Cl, Cp,
-                                         None, None, st) == 0
+            assert lib.pn2_conv1x1_dgrad(*dz, p(Y), r4(Cl), p(coef), p(Wt), Cp, p(Yp), r4(Cp), p(affp), p(dX), r4(Cp), p(red), P, Cl, Cp, None, st) == 0
         torch.cuda.synchronize()
         print("dgrad", (P, Cl, Cp, Kp))
         dump()
