@@ -606,6 +606,20 @@ int pn2_chamfer_nn(const float *p1, const float *p2, int B, int N, int M, int D,
 int pn2_chamfer_bwd(const float *p1, const float *p2, const float *dist, const int64_t *idx, const float *g, int B, int N, int M,
                     int D, float *dp1, float *dp2, pn2_stream_t stream);
 
+/* ---- Segmentation metrics (pcd_utils.py:65-210, pcdseg.py:58-97), added within ABI 15 (purely additive: no version change) ----------
+ * Confusion table of B clouds of N rows: logp holds B*N rows of pitch ld >= C whose first C columns are the classes (columns
+ * c >= C -- the pad of a [B*N, round4(C)] buffer -- may hold anything, NaN included: they never influence the result), target
+ * B*N labels.  pred(row) = the index of the row's largest entry, the LOWEST index on equal values; a NaN counts as largest and the
+ * first NaN wins; a row of all -inf predicts 0 (what torch.max(dim)[1] and argmax return).  Cloud b's table is int64 [C + 1, C] at
+ * conf + b * conf_stride: a row with target t in [0, C) adds 1 at [t, pred], any other target adds 1 at [C, pred] (such a point
+ * joins no class's target set but still counts in the union of the class it was predicted as); rows whose target equals
+ * ignore_index are skipped (INT64_MIN: none).  The call ADDS into conf (the caller zeroes it) with 64-bit integer atomics: the
+ * result does not depend on scheduling.  conf_stride = 0 pools the batch into one table, (C + 1) * C gives one table per cloud.
+ * pred (may be NULL) receives the B*N predictions.  1 <= C <= 64 (larger: PN2_EUNSUPPORTED, nothing launched); B*N == 0 is a
+ * no-op returning 0.  Rows are read as float4 quads when ld % 4 == 0 and logp is 16-byte aligned, one float at a time otherwise. */
+int pn2_seg_confusion(const float *logp, int ld, const int64_t *target, int B, int64_t N, int C, int64_t ignore_index, int64_t *conf,
+                      int64_t conf_stride, int64_t *pred, pn2_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -96,6 +96,7 @@ SIGNATURES = {
     "pn2_chamfer_nn_workspace_bytes": (_i64, [_i, _i, _i, _i]),
     "pn2_chamfer_nn": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "pn2_chamfer_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "pn2_seg_confusion": (_i, [_vp, _i, _vp, _i, _i64, _i, _i64, _vp, _i64, _vp, _vp]),
 }
 
 
