@@ -516,6 +516,29 @@ int pn2_adam_step(float *param, float *grad, float *exp_avg, float *exp_avg_sq, 
 int pn2_prepare_clouds(const float *raw, const int64_t *row_begin, const int64_t *row_count, const int32_t *raw_label,
                        const float *noise, const int64_t *noise_begin, const int64_t *choice, int B, int N,
                        float *points, int64_t *labels, int *bad_index, pn2_stream_t stream);
+/* pn2_prepare_shapes (added within ABI 15: purely additive, no version change) is the same gather for rows of any width: it
+ * replaces PartNormalDataset.__getitem__ (data_utils/ShapeNetDataLoader.py:116-126: rotate_point_cloud, jitter_point_cloud,
+ * `pointcloud[choice]`, `seg[choice]`, `normal[choice]`), the augmentation ModelNetDataLoader.__getitem__ intends
+ * (ModelNetDataLoader.py:64-68) and S3DISDataLoader's jitter (S3DISDataLoader.py:71-75), for a batch.
+ *   raw        [rows, C] fp32, 3 <= C <= 16, resident in HBM (4-byte alignment is all that is assumed: rows of 3, 6 or 9
+ *              floats); cloud b is rows [row_begin[b], row_begin[b] + row_count[b]) (int64[B] each, device memory).
+ *   raw_label  int32[rows] class per raw point, or NULL.
+ *   rot        [B, 2] fp64 (cos, sin) of each cloud's angle about the up axis, or NULL.  Columns 0..2 become
+ *              x' = f32(x*c + z*(-s)), y' = y, z' = f32(x*s + z*c) with the products and the sum in fp64, un-fused:
+ *              np.dot(pc_f32, [[c,0,s],[0,1,0],[-s,0,c]]) stored into float32 (augmentation.py:36-44).  Other columns
+ *              (the normals) are not rotated, as in the reference.
+ *   noise      [*, noise_cols] fp64 clipped jitter rows (clip(0.01 * randn, -0.05, 0.05), augmentation.py:80), one per RAW
+ *              point (duplicates share their jitter), cloud b's rows starting at noise_begin[b] (int64[B], device; NULL:
+ *              the same rows as raw); 1 <= noise_cols <= C.  Columns < noise_cols become f32(noise + f64(value)), the
+ *              value being the rotated fp32 one (augmentation.py:81, .astype(float32)); other columns are copied.
+ *              noise == NULL: no jitter, noise_cols ignored.
+ *   choice     int64[B, N] row numbers inside each cloud (np.random.choice(M, N, replace=True)); NULL: row n (needs
+ *              row_count[b] >= N).
+ * Outputs out [B, N, C] fp32 and labels int64[B, N] (or NULL).  A row number outside [0, row_count[b]) sets *bad_index
+ * (device int, caller zeroes, may be NULL) and reads row 0.  Bad arguments return -1 without a launch. */
+int pn2_prepare_shapes(const float *raw, int C, const int64_t *row_begin, const int64_t *row_count, const int32_t *raw_label,
+                       const double *rot, const double *noise, int noise_cols, const int64_t *noise_begin,
+                       const int64_t *choice, int B, int N, float *out, int64_t *labels, int *bad_index, pn2_stream_t stream);
 
 /* ---- PointNet v1 (model/pointnet.py: STN3d / STNkd / PointNetEncoder / PointNetSeg), ABI 12 -----------------------------
  * Per-cloud transform, torch.bmm(x, trans) of PointNetEncoder.forward: out[b*N + n, j] = sum_i X[b*N + n, i] * T[b, i, j].

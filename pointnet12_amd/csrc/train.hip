@@ -5,7 +5,10 @@
 //                         ~10 foreach launches over 150 tensors.
 //   * pn2_prepare_clouds  pcd_normalize + pcd_jitter + the with-replacement resampling of
 //                         data_utils/SemKITTI_Loader.py:17-30,93-113, as one gather over the raw [M,4] scans.
-// Both are HBM-bound streaming kernels: float4 lanes, nothing staged.
+//   * pn2_prepare_shapes  rotate_point_cloud + jitter_point_cloud (data_utils/augmentation.py:25-45,70-82) + the resampling
+//                         of ShapeNetDataLoader.py:116-126, over raw [M,C] rows (ShapeNet-part, ModelNet, S3DIS blocks).
+// All are HBM-bound streaming kernels: nothing staged.  The file is built with -ffp-contract=off: the fp64 forms of
+// pn2_prepare_shapes are numpy's, un-fused.
 #include "pn2_common.h"
 
 namespace {
@@ -143,6 +146,45 @@ __global__ __launch_bounds__(kThreads) void prepare_kernel(const float4 *__restr
     if (labels) labels[i] = raw_label ? (int64_t)raw_label[lo + c] : 0;
 }
 
+// One thread per output ELEMENT (b, n, col): rows of 3, 6, 9 floats are no 16-byte multiples, so the loads and stores are
+// single dwords, consecutive lanes writing consecutive addresses.  The arithmetic is numpy's, in numpy's precision:
+//   rotate_point_cloud   np.dot(pc_f32, R_f64), R = [[c,0,s],[0,1,0],[-s,0,c]], stored into a float32 array:
+//                        x' = f32(x*c + z*(-s)), y' = y, z' = f32(x*s + z*c), products and sum in fp64, un-fused;
+//   jitter_point_cloud   clip(0.01*randn, -0.05, 0.05) (fp64, drawn by the caller) += data, .astype(float32):
+//                        f32(noise_f64 + f64(v_f32)).
+__global__ __launch_bounds__(kThreads) void shapes_kernel(const float *__restrict__ raw, int C, const int64_t *__restrict__ row_begin,
+                                                          const int64_t *__restrict__ row_count,
+                                                          const int32_t *__restrict__ raw_label, const double *__restrict__ rot,
+                                                          const double *__restrict__ noise, int noise_cols,
+                                                          const int64_t *__restrict__ noise_begin,
+                                                          const int64_t *__restrict__ choice, int N, int64_t total,
+                                                          float *__restrict__ out, int64_t *__restrict__ labels,
+                                                          int *__restrict__ bad) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= total) return;
+    const int64_t p = i / C;                                // output point b*N + n
+    const int col = (int)(i - p * C);
+    const int b = (int)(p / N);
+    const int64_t lo = row_begin[b], M = row_count[b];
+    int64_t c = choice ? choice[p] : p - (int64_t)b * N;    // NULL: the identity (ModelNet items, S3DIS blocks)
+    if (c < 0 || c >= M) {                                  // numpy raises IndexError; here: flagged, row 0 used
+        if (bad && col == 0) atomicOr(bad, 1);
+        c = 0;
+        if (M <= 0) { out[i] = 0.f; if (labels && col == 0) labels[p] = 0; return; }
+    }
+    const float *r = raw + (lo + c) * C;
+    float v = r[col];
+    if (rot && (col == 0 || col == 2)) {
+        const double cs = rot[2 * b], sn = rot[2 * b + 1];
+        const double x = (double)r[0], z = (double)r[2];
+        v = col == 0 ? (float)(x * cs + z * (-sn)) : (float)(x * sn + z * cs);
+    }
+    if (noise && col < noise_cols)                          // one noise row per RAW point: duplicates share their jitter
+        v = (float)(noise[((noise_begin ? noise_begin[b] : lo) + c) * noise_cols + col] + (double)v);
+    out[i] = v;
+    if (labels && col == 0) labels[p] = raw_label ? (int64_t)raw_label[lo + c] : 0;
+}
+
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
@@ -176,6 +218,21 @@ int pn2_prepare_clouds(const float *raw, const int64_t *row_begin, const int64_t
     hipLaunchKernelGGL(prepare_kernel, dim3((unsigned)pn2_cdiv((int64_t)B * N, kThreads)), dim3(kThreads), 0, pn2_s(stream),
                        reinterpret_cast<const float4 *>(raw), row_begin, row_count, raw_label, reinterpret_cast<const float4 *>(noise),
                        noise_begin, choice, B, N, reinterpret_cast<float4 *>(points), labels, bad_index);
+    return pn2_launch_status();
+}
+
+int pn2_prepare_shapes(const float *raw, int C, const int64_t *row_begin, const int64_t *row_count, const int32_t *raw_label,
+                       const double *rot, const double *noise, int noise_cols, const int64_t *noise_begin,
+                       const int64_t *choice, int B, int N, float *out, int64_t *labels, int *bad_index, pn2_stream_t stream) {
+    PN2_CHECK_ARG(raw && row_begin && row_count && out && B > 0 && N > 0 && C >= 3 && C <= 16);
+    PN2_CHECK_ARG(!noise || (noise_cols >= 1 && noise_cols <= C));
+    PN2_CHECK_ARG(((reinterpret_cast<uintptr_t>(raw) | reinterpret_cast<uintptr_t>(out)) & 3) == 0);
+    PN2_CHECK_ARG(((reinterpret_cast<uintptr_t>(rot) | reinterpret_cast<uintptr_t>(noise)) & 7) == 0);
+    const int64_t total = (int64_t)B * N * C;
+    const int64_t blocks = pn2_cdiv(total, kThreads);
+    PN2_CHECK_ARG(blocks <= 0x7fffffff);
+    hipLaunchKernelGGL(shapes_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, pn2_s(stream), raw, C, row_begin, row_count,
+                       raw_label, rot, noise, noise_cols, noise_begin, choice, N, total, out, labels, bad_index);
     return pn2_launch_status();
 }
 
