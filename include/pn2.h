@@ -643,6 +643,48 @@ int pn2_chamfer_bwd(const float *p1, const float *p2, const float *dist, const i
 int pn2_seg_confusion(const float *logp, int ld, const int64_t *target, int B, int64_t N, int C, int64_t ignore_index, int64_t *conf,
                       int64_t conf_stride, int64_t *pred, pn2_stream_t stream);
 
+/* ---- The KITTI demo's frame path (pcdvis.py:115-144), added within ABI 15 (purely additive: no version change) ------------------------
+ * Small tables below (group table, calibration, disc rows) are HOST arrays: they are checked on the host and travel inside the
+ * launch.  Everything else is device memory.  No entry point allocates or waits: each call can be captured in a graph.
+ *
+ * pn2_seg_predict replaces `logits[0].argmax(-1)` (pcdvis.py:136) and the class merges of KITTI_2_Common.__call__ /
+ * SemKITTI_2_Common.__call__ (data_utils/kitti_utils.py:41-58, :92-117).  logp: R rows of pitch ld >= C, the first C columns are
+ * the classes (1 <= C <= 64; larger: PN2_EUNSUPPORTED).  G == 0: pred[r] = the row's arg-max exactly as pn2_seg_confusion defines
+ * it (lowest index on ties, the first NaN wins, an all -inf row gives 0).  G > 0 (<= 64): group g consists of the classes
+ * member[group_begin[g] .. group_begin[g + 1]) (host int32; every group non-empty, members in [0, C), at most 256 members in
+ * all); merged[r, g] (pitch ldm >= G) = the largest of its members, NaN if any member is NaN (Tensor.max(dim)), and pred[r] = the
+ * arg-max over the G group values by the same rule.  pred and merged may each be NULL (merged needs G > 0). */
+int pn2_seg_predict(const float *logp, int ld, int64_t R, int C, const int32_t *group_begin, const int32_t *member, int G,
+                    int64_t *pred, float *merged, int ldm, pn2_stream_t stream);
+/* pn2_project_points replaces Semantic_KITTI_Utils.project_3d_to_2d (kitti_utils.py:313-336) with numpy's own arithmetic.  xyz: N
+ * rows of pitch ldx >= 3 floats (the first three columns of [N, 4] scans are read in place); RT host double[12] (3 x 4, row-major:
+ * [R | T]), P host double[9] (3 x 3).  Per point, every operation rounded separately (no fused multiply-add):
+ *   c_k = f32(((RT[k][0]*x + RT[k][1]*y) + RT[k][2]*z) + RT[k][3]*1.0)   in fp64 on the fp32 inputs,
+ *   q_k = f32((P[k][0]*c_0 + P[k][1]*c_1) + P[k][2]*c_2)                 in fp64 on the rounded fp32 c,
+ *   pts_2d[n] = (q_0 / q_2, q_1 / q_2)                                   IEEE fp32 divisions (inf / NaN at the camera plane).
+ * pix (int32 [N, 2], may be NULL; so may pts_2d, not both) = the truncation toward zero that `.astype(np.int32)` performs
+ * (kitti_utils.py:374); a point with a component that is not finite or whose magnitude is >= 2^31 gets INT32_MIN in BOTH (numpy's
+ * cast is undefined there) and is skipped by pn2_splat_discs.
+ * RT == NULL and P == NULL (pts_2d == NULL): the top view's centres instead (kitti_utils.py:387-390), in Python's arithmetic:
+ * X = trunc(-x*800 + 600), Y = trunc(-y*800 + 400) in fp64, pix[n] = (Y, X) as :390 passes them; INT32_MIN in both when either
+ * is not finite or >= 2^31 in magnitude (Python's int() raises there). */
+int pn2_project_points(const float *xyz, int ldx, int64_t N, const double *RT, const double *P, float *pts_2d, int32_t *pix,
+                       pn2_stream_t stream);
+/* pn2_splat_discs + pn2_splat_resolve replace the drawing loops of draw_2d_points / draw_2d_top_view (kitti_utils.py:368-392:
+ * `cv2.circle(image, (x, y), r, c, -1)` per point, so a pixel shows the LAST point that covered it).
+ * pn2_splat_discs clears owner (uint32 [H * W]; the clear is part of the call) and sets owner[y * W + x] = max(i + 1) over the
+ * points i whose disc covers pixel (x, y): integer maxima, the result does not depend on scheduling.  pix int32 [N, 2] centres
+ * (x = column, y = row); a centre with INT32_MIN in either component is skipped; discs are clipped to the image.  The disc is
+ * the host table half_width[2 * radius + 1]: its row dy = j - radius covers dx in [-half_width[j], half_width[j]] (-1: nothing).
+ * radius <= 32 (larger: PN2_EUNSUPPORTED), H * W < 2^31, N < 2^31. */
+int pn2_splat_discs(const int32_t *pix, int64_t N, const int32_t *half_width, int radius, int H, int W, uint32_t *owner,
+                    pn2_stream_t stream);
+/* out (uint8 [H, W, 3]) = colors[label[owner - 1]] where a pixel has an owner, else background (uint8 [H, W, 3]; NULL: zeros).
+ * colors uint8 [C, 3], label int64 [N].  A label outside [0, C) leaves the background and sets *err (device int, caller zeroes,
+ * may be NULL) to 1, as pn2_gather_rows does (the reference's `colors[pred]` raises IndexError). */
+int pn2_splat_resolve(const uint32_t *owner, int H, int W, const int64_t *label, int64_t N, const uint8_t *colors, int C,
+                      const uint8_t *background, uint8_t *out, int *err, pn2_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

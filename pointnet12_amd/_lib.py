@@ -98,6 +98,10 @@ SIGNATURES = {
     "pn2_chamfer_nn": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "pn2_chamfer_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "pn2_seg_confusion": (_i, [_vp, _i, _vp, _i, _i64, _i, _i64, _vp, _i64, _vp, _vp]),
+    "pn2_seg_predict": (_i, [_vp, _i, _i64, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
+    "pn2_project_points": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "pn2_splat_discs": (_i, [_vp, _i64, _vp, _i, _i, _i, _vp, _vp]),
+    "pn2_splat_resolve": (_i, [_vp, _i, _i, _vp, _i64, _vp, _i, _vp, _vp, _vp, _vp]),
 }
 
 

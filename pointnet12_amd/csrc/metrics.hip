@@ -8,13 +8,14 @@
 //
 // Prediction (the contract, include/pn2.h): the index of the row's largest entry among its first C columns, the LOWEST index on
 // equal values; a NaN counts as largest and the first NaN wins; a row of all -inf predicts 0 -- what torch.max(dim)[1] and
-// argmax return.  Columns c >= C of a padded row are read (float4 quads) but never compared.
+// argmax return (row_argmax.h, shared with view.hip).  Columns c >= C of a padded row are read (float4 quads) but never compared.
 //
 // A thread owns a row.  Labels of neighbouring points are mostly equal, so the lanes of a wave mostly hit one bin: up to
 // kAggregateRounds bins are counted per wave with a ballot and added by one lane, whatever is left goes one lane at a time.  The
 // counts go into a per-wave copy of the table in LDS (32-bit; a workgroup never sees 2^32 rows), and only the non-zero bins are
 // flushed with 64-bit integer atomics: integer adds commute, the table is bit-identical however the workgroups were scheduled.
 #include "pn2_common.h"
+#include "row_argmax.h"
 
 #include <algorithm>
 
@@ -28,8 +29,6 @@ constexpr int kMaxStaticLds = 64 * 1024;
 
 // Table copies in LDS: one per wave while four of them fit the 64 KiB a workgroup gets without asking (C <= 63), two at C = 64.
 inline int table_copies(int C) { return 4 * (C + 1) * C * (int)sizeof(unsigned) <= kMaxStaticLds ? kWaves : 2; }
-
-__device__ __forceinline__ bool beats(float v, float best) { return v > best || (v != v && best == best); }
 
 // grid: B * wgs_per_cloud workgroups; workgroup w of a cloud takes the rows n = w * 256 + thread + i * wgs_per_cloud * 256.
 template <bool QUADS>
@@ -55,28 +54,7 @@ __global__ __launch_bounds__(kThreads) void seg_confusion_kernel(const float *__
             const int64_t r = (int64_t)b * N + n;
             const float *row = logp + r * ld;
             float best;
-            int arg = 0;
-            if (QUADS) {
-                const float4 *row4 = reinterpret_cast<const float4 *>(row);
-                float4 t = row4[0];
-                best = t.x;
-                if (1 < C && beats(t.y, best)) { best = t.y; arg = 1; }
-                if (2 < C && beats(t.z, best)) { best = t.z; arg = 2; }
-                if (3 < C && beats(t.w, best)) { best = t.w; arg = 3; }
-                for (int c = 4; c < C; c += 4) {
-                    t = row4[c >> 2];                             // ld >= round4(C): the quad lies inside the row
-                    if (beats(t.x, best)) { best = t.x; arg = c; }
-                    if (c + 1 < C && beats(t.y, best)) { best = t.y; arg = c + 1; }
-                    if (c + 2 < C && beats(t.z, best)) { best = t.z; arg = c + 2; }
-                    if (c + 3 < C && beats(t.w, best)) { best = t.w; arg = c + 3; }
-                }
-            } else {
-                best = row[0];
-                for (int c = 1; c < C; ++c) {
-                    const float v = row[c];
-                    if (beats(v, best)) { best = v; arg = c; }
-                }
-            }
+            const int arg = pn2_row_argmax<QUADS>(row, C, best);
             if (pred != nullptr) pred[r] = arg;
             const int64_t t = target[r];
             live = t != ignore_index;

@@ -1,0 +1,469 @@
+"""The second half of the reference's KITTI demo (``python pcdvis.py``) on the device: labels, pixels, image.
+
+``pcdvis.py:115-144`` reads a scan, resamples it to 25 000 points, normalises it, runs the network and takes the arg-max; it
+then projects the points into the camera (``Semantic_KITTI_Utils.torch_project_3d_to_2d``), colours them by class and draws them
+one ``cv2.circle`` at a time (``draw_2d_points``, data_utils/kitti_utils.py:368-379).  ``kitti.read_scan`` /
+``loader.prepare_batch`` and the model zoo cover the first half; this module is the second, on ``csrc/view.hip``:
+
+  * ``predict`` / ``merge_classes``   ``logits[0].argmax(-1)`` and the class merges of ``KITTI_2_Common`` /
+    ``SemKITTI_2_Common`` (kitti_utils.py:41-58, :92-117) -- ``pn2_seg_predict``;
+  * ``project_3d_to_2d``              kitti_utils.py:313-336 -- ``pn2_project_points``;
+  * ``draw_2d_points`` / ``draw_2d_top_view``   kitti_utils.py:368-392 -- ``pn2_splat_discs`` + ``pn2_splat_resolve``;
+  * ``FrameSegmenter``                the frame loop's body, device tensors in and out, nothing read back.
+
+Nothing here copies the reference's tables: class names and colours come from the dataset's own ``semantic-kitti.yaml``
+(``classes_from_config``: ``labels[learning_map_inv[i]]`` and ``color_map[learning_map_inv[i]]``, which is what the reference's
+literal lists hold, entry for entry), merge lists come from the caller in the reference's ``'a+b'`` format.
+
+Differences from the reference, all deliberate:
+
+  * ``project_3d_to_2d`` (and its alias ``torch_project_3d_to_2d``) returns the numbers of the reference's NUMPY method
+    (fp64 products on fp32 points, each stage stored as float32, fp32 division) bit for bit.  The reference's torch method, an
+    fp32 ``bmm``, differs from those by rounding; it has no counterpart here.
+  * Pixel coordinates are ``astype(np.int32)``'s truncation toward zero.  Where a projected coordinate is not finite or its
+    magnitude is 2^31 or more, numpy's cast is undefined (it depends on the platform); here such a point gets ``INT32_MIN`` in
+    both components and is never drawn.
+  * Drawing order.  The reference draws point after point, so a pixel shows the last point that covered it; here every pixel
+    takes the largest covering point index (an integer maximum), which is the same image, bit-identical from run to run.
+  * THE DISC TABLES ARE UNVERIFIED AGAINST OPENCV.  ``cv2.circle(..., radius, color, -1)`` fills a rasterised disc; the two
+    default tables below (radius 2: rows of 3, 5, 5, 5, 3 pixels = 21; radius 3: 3, 5, 7, 7, 7, 5, 3 = 37) were written from
+    memory of OpenCV's filled-circle rasteriser and could not be checked, because OpenCV was not available where this was
+    written.  The tests hold the kernel to the table, not to OpenCV.  Any other radius needs an explicit ``half_widths``.
+  * float32 log-probabilities on the GPU only: a CPU tensor raises ``Pn2Error``; there is no fallback path.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check as _check, ptr as _p
+from .metrics import MAX_CLASSES, _rows
+
+INT32_MIN = -2 ** 31
+MAX_GROUPS = 64
+# row dy = j - radius of the disc covers dx in [-half_width[j], half_width[j]] -- see the module docstring: unverified against OpenCV
+DISC_HALF_WIDTHS = {2: (1, 2, 2, 2, 1), 3: (1, 2, 3, 3, 3, 2, 1)}
+
+
+# ------------------------------------------------------------------------------------------------------------- calibration
+def _values(val):
+    return np.array(val.split(), dtype=np.float64)
+
+
+def calib_velo2cam(fn):
+    """``(R [3, 3], T [3, 1])`` float64 of a KITTI ``calib_velo_to_cam.txt`` (kitti_utils.py:282-295)."""
+    R = T = None
+    with open(fn, "r") as f:
+        for line in f:
+            if ":" not in line:
+                continue
+            key, val = line.split(":", 1)
+            if key == "R":
+                R = _values(val).reshape(3, 3)
+            if key == "T":
+                T = _values(val).reshape(3, 1)
+    if R is None or T is None:
+        raise ValueError("%s holds no R / T line" % fn)
+    return R, T
+
+
+def calib_cam2cam(fn, mode="02"):
+    """``P [3, 3]`` float64: the first three columns of ``P_rect_<mode>`` of a KITTI ``calib_cam_to_cam.txt`` (:297-311)."""
+    P = None
+    with open(fn, "r") as f:
+        for line in f:
+            if ":" not in line:
+                continue
+            key, val = line.split(":", 1)
+            if key == ("P_rect_" + mode):
+                P = _values(val).reshape(3, 4)[:3, :3]
+    if P is None:
+        raise ValueError("%s holds no P_rect_%s line" % (fn, mode))
+    return P
+
+
+class Calibration:
+    """``R [3, 3]``, ``T [3, 1]``, ``P [3, 3]`` (float64) and ``RT = [R | T]`` (kitti_utils.py:148-150)."""
+
+    def __init__(self, R, T, P):
+        self.R = np.ascontiguousarray(R, np.float64).reshape(3, 3)
+        self.T = np.ascontiguousarray(T, np.float64).reshape(3, 1)
+        self.P = np.ascontiguousarray(P, np.float64).reshape(3, 3)
+        self.RT = np.ascontiguousarray(np.concatenate((self.R, self.T), axis=1))
+
+    @classmethod
+    def from_files(cls, fn_velo2cam, fn_cam2cam, mode="02"):
+        R, T = calib_velo2cam(fn_velo2cam)
+        return cls(R, T, calib_cam2cam(fn_cam2cam, mode))
+
+
+# ------------------------------------------------------------------------------------------------------- classes and merges
+def classes_from_config(cfg):
+    """``(class_names, colors uint8 [K, 3], colors_bgr uint8 [K, 3])`` of the training classes 1..K of a ``semantic-kitti.yaml``
+    (a dict with its ``labels``, ``color_map`` and ``learning_map_inv`` blocks): training class ``i`` is entry ``i - 1``, named
+    ``labels[learning_map_inv[i]]`` and coloured ``color_map[learning_map_inv[i]]`` -- the reference's ``sem_kitti_class_names``
+    / ``sem_kitti_colors`` (kitti_utils.py:120-129); ``colors_bgr`` is each row reversed (:181)."""
+    inv = {int(k): int(v) for k, v in cfg["learning_map_inv"].items()}
+    labels = {int(k): v for k, v in cfg["labels"].items()}
+    cmap = {int(k): v for k, v in cfg["color_map"].items()}
+    ids = sorted(i for i in inv if i != 0)
+    if ids != list(range(1, len(ids) + 1)):
+        raise ValueError("learning_map_inv must name the training classes 1..K")
+    names = [str(labels[inv[i]]) for i in ids]
+    colors = np.array([list(cmap[inv[i]]) for i in ids], np.uint8).reshape(len(ids), 3)
+    return names, colors, np.ascontiguousarray(colors[:, ::-1])
+
+
+class Groups:
+    """A merge table: group ``g`` consists of the classes ``member[begin[g]:begin[g + 1]]`` (int32 arrays, the layout
+    ``pn2_seg_predict`` reads); ``names`` the merged names, ``first`` each group's first member, ``colors`` its colour."""
+
+    def __init__(self, begin, member, names=None, colors=None):
+        self.begin = np.ascontiguousarray(begin, np.int32)
+        self.member = np.ascontiguousarray(member, np.int32)
+        if self.begin.ndim != 1 or self.begin.size < 2 or self.begin[0] != 0 or (np.diff(self.begin) <= 0).any() or \
+                self.begin[-1] != self.member.size:
+            raise ValueError("Groups: begin must rise from 0 to len(member), no group empty")
+        if len(self) > MAX_GROUPS:
+            raise _lib.Pn2Error("Groups: %d groups are not supported (at most %d)" % (len(self), MAX_GROUPS))
+        self.names = list(names) if names is not None else None
+        self.first = self.member[self.begin[:-1]]
+        self.colors = colors
+
+    def __len__(self):
+        return int(self.begin.size) - 1
+
+    def members(self, g):
+        return self.member[self.begin[g]:self.begin[g + 1]].tolist()
+
+
+def merge_groups(class_names, merged, colors=None):
+    """``Groups`` of a merge list in the reference's format, e.g. ``['road', 'parking+sidewalk', ...]``: the members of each entry
+    are ``class_names.index`` of its ``'+'``-separated names (an unknown name raises ``ValueError``, as ``list.index`` does), in
+    the order written; any number of members per group (the reference raises above two).  With ``colors`` ``[K, 3]``,
+    ``.colors`` holds the colour of each group's FIRST member (kitti_utils.py:83-87)."""
+    class_names = list(class_names)
+    begin, member = [0], []
+    for entry in merged:
+        for name in entry.split("+"):
+            member.append(class_names.index(name))
+        begin.append(len(member))
+    g = Groups(begin, member, merged)
+    if colors is not None:
+        g.colors = np.ascontiguousarray(np.asarray(colors)[g.first])
+    return g
+
+
+def _as_groups(groups):
+    if groups is None or isinstance(groups, Groups):
+        return groups
+    begin, member = groups
+    return Groups(begin, member)
+
+
+# ------------------------------------------------------------------------------------------------------------------ predict
+def _i32p(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _logp(log_probs, what):
+    if not isinstance(log_probs, torch.Tensor) or not log_probs.is_cuda:
+        raise _lib.Pn2Error("%s: log_probs must live on the GPU: this package has no CPU path" % what)
+    if log_probs.dtype != torch.float32:
+        raise RuntimeError("%s: log_probs must be float32 (got %s)" % (what, log_probs.dtype))
+    C = int(log_probs.shape[-1])
+    if not 1 <= C <= MAX_CLASSES:
+        raise _lib.Pn2Error("%s: %d classes are not supported (1 <= C <= %d; there is no fallback path)" % (what, C, MAX_CLASSES))
+    logp, B, N, ld = _rows(log_probs.detach(), C)
+    return logp, B * N, C, ld
+
+
+def _seg_predict(logp, R, C, ld, groups, pred, merged):
+    G = 0 if groups is None else len(groups)
+    if groups is not None and (groups.member.min() < 0 or groups.member.max() >= C):
+        raise ValueError("groups name class %d, log_probs has %d columns" % (int(groups.member.max()), C))
+    if R > 0:
+        _check(_lib.load().pn2_seg_predict(_p(logp), ld, R, C, _i32p(groups.begin) if G else None, _i32p(groups.member) if G else None,
+                                           G, _p(pred), _p(merged), G, _lib.stream()), "pn2_seg_predict")
+
+
+def predict(log_probs, groups=None, out=None):
+    """int64 labels ``[...]`` of log-probabilities ``[B, N, C]`` or ``[R, C]``: ``log_probs.max(-1)[1]`` exactly (the lowest index
+    on ties, the first NaN if there is one).  With ``groups`` (``merge_groups``) the arg-max is taken over the merged classes:
+    ``merge_classes(log_probs, groups).max(-1)[1]`` without materialising them.  A column slice of a padded buffer is read in
+    place.  Nothing is read back: the call can be captured in a graph (``out``: a contiguous int64 tensor to write into)."""
+    groups = _as_groups(groups)
+    logp, R, C, ld = _logp(log_probs, "predict")
+    shape = tuple(log_probs.shape[:-1])
+    if out is None:
+        out = torch.empty(shape, device=logp.device, dtype=torch.int64)
+    elif out.dtype != torch.int64 or out.device != logp.device or out.numel() != R or not out.is_contiguous():
+        raise ValueError("predict: out must be a contiguous int64 tensor of %d elements on %s" % (R, logp.device))
+    _seg_predict(logp, R, C, ld, groups, out, None)
+    return out
+
+
+def merge_classes(log_probs, groups):
+    """``[..., C]`` -> ``[..., G]``: column ``g`` is the maximum over the members of group ``g`` (NaN where any member is NaN, as
+    ``Tensor.max(dim)``) -- ``SemKITTI_2_Common.__call__`` (kitti_utils.py:92-117) for any number of members per group."""
+    groups = _as_groups(groups)
+    if groups is None:
+        raise ValueError("merge_classes needs a group table (merge_groups)")
+    logp, R, C, ld = _logp(log_probs, "merge_classes")
+    out = torch.empty(tuple(log_probs.shape[:-1]) + (len(groups),), device=logp.device, dtype=torch.float32)
+    _seg_predict(logp, R, C, ld, groups, None, out)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------ project
+def _xyz_rows(pts, what):
+    """[N, >= 3] float32 on the GPU -> (tensor, N, row pitch), rows read in place when their elements are adjacent."""
+    if not isinstance(pts, torch.Tensor) or not pts.is_cuda:
+        raise _lib.Pn2Error("%s: points must live on the GPU: this package has no CPU path" % what)
+    if pts.dtype != torch.float32:
+        raise RuntimeError("%s: points must be float32 (got %s)" % (what, pts.dtype))
+    if pts.dim() != 2 or pts.shape[1] < 3:
+        raise AssertionError(tuple(pts.shape))
+    pts = pts.detach()
+    N = int(pts.shape[0])
+    if N > 1 and (pts.stride(1) != 1 or pts.stride(0) < 3 or pts.stride(0) >= 2 ** 31):
+        pts = pts[:, :3].contiguous()
+    elif N == 1 and pts.stride(1) != 1:
+        pts = pts[:, :3].contiguous()
+    return pts, N, int(pts.stride(0)) if N > 1 else 3
+
+
+def project_3d_to_2d(pts_3d, calib, return_pixels=False, out=None):
+    """``pts_2d`` float32 ``[N, 2]`` of velodyne points ``[N, 3]`` (or the first three columns of ``[N, 4]`` scan rows, read in
+    place): ``Semantic_KITTI_Utils.project_3d_to_2d`` (kitti_utils.py:313-336), bit for bit.  These are the NUMPY method's
+    numbers; the reference's ``torch_project_3d_to_2d`` (an fp32 ``bmm``) differs from them by rounding.
+
+    ``return_pixels``: also int32 ``[N, 2]``, ``pts_2d.astype(np.int32)`` (truncation toward zero, :374).  A point whose
+    projection is not finite (on the camera plane) or reaches 2^31 in magnitude gets ``INT32_MIN`` in both components: numpy's
+    cast is undefined there, and the drawing kernels skip such points.  ``out``: ``(pts_2d | None, pix | None)`` buffers to write
+    into (a given ``pix`` is filled either way); what is RETURNED depends on ``return_pixels`` alone."""
+    pts, N, ld = _xyz_rows(pts_3d, "project_3d_to_2d")
+    pts_2d, pix = out if out is not None else (None, None)
+    if pts_2d is None:
+        pts_2d = torch.empty(N, 2, device=pts.device, dtype=torch.float32)
+    if pix is None and return_pixels:
+        pix = torch.empty(N, 2, device=pts.device, dtype=torch.int32)
+    if pts_2d.shape != (N, 2) or pts_2d.dtype != torch.float32 or not pts_2d.is_contiguous() or \
+            (pix is not None and (pix.shape != (N, 2) or pix.dtype != torch.int32 or not pix.is_contiguous())):
+        raise ValueError("project_3d_to_2d: out must be contiguous ([N, 2] float32, [N, 2] int32 | None)")
+    if N > 0:
+        _check(_lib.load().pn2_project_points(_p(pts), ld, N, calib.RT.ctypes.data_as(ctypes.c_void_p),
+                                              calib.P.ctypes.data_as(ctypes.c_void_p), _p(pts_2d), _p(pix), _lib.stream()),
+               "pn2_project_points")
+    return (pts_2d, pix) if return_pixels else pts_2d
+
+
+torch_project_3d_to_2d = project_3d_to_2d
+
+
+def top_view_pixels(pcd_3d, out=None):
+    """int32 ``[N, 2]`` disc centres ``(Y, X)`` of the top view (kitti_utils.py:387-390): ``X = int(-x*800 + 600)``,
+    ``Y = int(-y*800 + 400)`` in Python's float arithmetic; ``INT32_MIN`` where Python's ``int()`` would raise or leave int32."""
+    pts, N, ld = _xyz_rows(pcd_3d, "top_view_pixels")
+    if out is None:
+        out = torch.empty(N, 2, device=pts.device, dtype=torch.int32)
+    elif out.shape != (N, 2) or out.dtype != torch.int32 or not out.is_contiguous():
+        raise ValueError("top_view_pixels: out must be a contiguous [N, 2] int32 tensor")
+    if N > 0:
+        _check(_lib.load().pn2_project_points(_p(pts), ld, N, None, None, None, _p(out), _lib.stream()), "pn2_project_points")
+    return out
+
+
+def pcd_unnormalize(pcd):
+    """The inverse of the loader's normalisation (``pcd_unnormalize``, data_utils/SemKITTI_Loader.py:32-38) on a tensor
+    ``[N, 4]``: x*70, y*70, z*3, i/2 + 0.5 (one scaled copy; the offset goes to the intensity column alone, so a -0.0
+    coordinate keeps its sign)."""
+    out = pcd * pcd.new_tensor([70.0, 70.0, 3.0, 0.5])
+    out[:, 3] += 0.5
+    return out
+
+
+# --------------------------------------------------------------------------------------------------------------------- draw
+def _half_widths(radius, half_widths):
+    radius = int(radius)
+    if half_widths is None:
+        if radius not in DISC_HALF_WIDTHS:
+            raise ValueError("draw: no default disc table for radius %d (only %s): pass half_widths, %d row half-widths"
+                             % (radius, sorted(DISC_HALF_WIDTHS), 2 * radius + 1))
+        half_widths = DISC_HALF_WIDTHS[radius]
+    hw = np.ascontiguousarray(half_widths, np.int32)
+    if hw.shape != (2 * radius + 1,):
+        raise ValueError("draw: half_widths must hold 2 * radius + 1 = %d rows" % (2 * radius + 1))
+    return radius, hw
+
+
+def to_pixels(pts_2d):
+    """``pts_2d.astype(np.int32)`` of a float tensor ``[N, 2]`` under the rule of ``project_3d_to_2d``: truncation toward zero,
+    ``INT32_MIN`` in both components of a point that is not finite or reaches 2^31."""
+    ok = (torch.isfinite(pts_2d) & (pts_2d.abs() < 2.0 ** 31)).all(-1, keepdim=True)
+    return torch.where(ok, pts_2d, torch.zeros_like(pts_2d)).trunc().to(torch.int32).masked_fill(~ok, INT32_MIN).contiguous()
+
+
+def _dev_u8(a, device, what):
+    if isinstance(a, torch.Tensor):
+        if a.dtype != torch.uint8:
+            raise RuntimeError("%s must be uint8 (got %s)" % (what, a.dtype))
+        return a.to(device).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(a, np.uint8)).to(device)
+
+
+def draw_2d_points(pts_2d, labels, colors, image=None, size=(375, 1242), radius=2, half_widths=None, out=None, owner=None,
+                   err=None):
+    """The image ``draw_2d_points`` paints (kitti_utils.py:368-379): uint8 ``[H, W, 3]`` on the device, pixel order
+    ``[row = y, col = x]``.  ``pts_2d``: float ``[N, 2]`` ``(x, y)`` (cast as ``to_pixels`` does) or int32 ``[N, 2]`` pixel
+    centres (``project_3d_to_2d(..., return_pixels=True)``).  Point ``i`` paints the disc of ``radius`` around its centre with
+    ``colors[labels[i]]`` (``colors`` uint8 ``[C, 3]``, ``labels`` int64 ``[N]``), later points over earlier ones; ``image`` is the
+    background (uint8 ``[H, W, 3]``, not modified; None: black, ``size = (H, W)``).  Default disc tables exist for radius 2 and 3
+    only (see the module docstring: unverified against OpenCV); any other radius needs ``half_widths``.
+
+    A label outside ``[0, C)`` paints nothing and sets ``err`` (a zeroed device int32 tensor).  Without ``err`` the flag is
+    read back and raises ``IndexError`` (skipped under stream capture).  ``out`` / ``owner``: the image and a uint32-sized
+    (int32) ``[H * W]`` scratch to write into; with both and ``err`` given the call allocates nothing."""
+    if not isinstance(pts_2d, torch.Tensor) or not pts_2d.is_cuda or not isinstance(labels, torch.Tensor) or not labels.is_cuda:
+        raise _lib.Pn2Error("draw_2d_points: points and labels must live on the GPU: this package has no CPU path")
+    radius, hw = _half_widths(radius, half_widths)
+    dev = pts_2d.device
+    if pts_2d.dim() != 2 or pts_2d.shape[1] != 2:
+        raise AssertionError(tuple(pts_2d.shape))
+    N = int(pts_2d.shape[0])
+    if labels.numel() != N or labels.dtype != torch.int64:
+        raise ValueError("draw_2d_points: labels must be int64 [%d]" % N)
+    pix = pts_2d.contiguous() if pts_2d.dtype == torch.int32 else to_pixels(pts_2d.detach())
+    labels = labels.reshape(-1).contiguous()
+    colors = _dev_u8(colors, dev, "colors")
+    if colors.dim() != 2 or colors.shape[1] != 3:
+        raise ValueError("draw_2d_points: colors must be [C, 3]")
+    if image is not None:
+        image = _dev_u8(image, dev, "image")
+        if image.dim() != 3 or image.shape[2] != 3:
+            raise ValueError("draw_2d_points: image must be [H, W, 3]")
+        size = (int(image.shape[0]), int(image.shape[1]))
+    H, W = int(size[0]), int(size[1])
+    if out is None:
+        out = torch.empty(H, W, 3, device=dev, dtype=torch.uint8)
+    elif out.shape != (H, W, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != dev:
+        raise ValueError("draw_2d_points: out must be a contiguous uint8 [%d, %d, 3] tensor on %s" % (H, W, dev))
+    if owner is None:
+        owner = torch.empty(H * W, device=dev, dtype=torch.int32)
+    elif owner.numel() != H * W or owner.element_size() != 4 or not owner.is_contiguous() or owner.device != dev:
+        raise ValueError("draw_2d_points: owner must be a contiguous 32-bit tensor of %d elements on %s" % (H * W, dev))
+    flag = err if err is not None else torch.zeros(1, device=dev, dtype=torch.int32)
+    lib, st = _lib.load(), _lib.stream()
+    _check(lib.pn2_splat_discs(_p(pix), N, _i32p(hw), radius, H, W, _p(owner), st), "pn2_splat_discs")
+    _check(lib.pn2_splat_resolve(_p(owner), H, W, _p(labels), N, _p(colors), int(colors.shape[0]), _p(image), _p(out), _p(flag), st),
+           "pn2_splat_resolve")
+    if err is None and not torch.cuda.is_current_stream_capturing() and int(flag.item()) != 0:
+        raise IndexError("draw_2d_points: a label is outside [0, %d)" % colors.shape[0])
+    return out
+
+
+def draw_2d_top_view(pcd_3d, labels, colors, out=None, owner=None, err=None):
+    """The 600 x 800 top view of ``draw_2d_top_view`` (kitti_utils.py:381-392) of NORMALISED points ``[N, >= 3]``: discs of radius
+    3 at ``(Y, X)``, on black."""
+    return draw_2d_points(top_view_pixels(pcd_3d), labels, colors, None, (600, 800), 3, None, out, owner, err)
+
+
+# -------------------------------------------------------------------------------------------------------------------- frame
+class FrameSegmenter:
+    """The body of the reference's frame loop (pcdvis.py:116-144) for one scan ``[M, 4]`` (x, y, z, intensity, as
+    ``kitti.read_scan`` returns it): resample to ``npoints`` rows, normalise (``pn2_prepare_clouds``), run ``model`` in eval
+    mode, predict, project the resampled un-normalised xyz into the camera and draw both views.
+
+    ``colors`` uint8 ``[C, 3]`` (one row per class, or per group with ``groups``); ``groups``: a ``merge_groups`` table, the
+    prediction is then taken over the merged classes.  ``frame`` returns a dict of device tensors -- ``pred`` int64 ``[N]``,
+    ``log_probs`` ``[N, C]``, ``points`` (normalised, ``[N, 4]``), ``pts_3d`` ``[N, 3]``, ``pts_2d`` float32 ``[N, 2]``, ``pix``,
+    ``image`` uint8 ``[H, W, 3]`` and ``top_view`` uint8 ``[600, 800, 3]`` -- and reads nothing back.  The outputs are buffers owned
+    by the segmenter and overwritten by the next frame.  ``error_flag`` (device int32, cleared at the start of every ``frame``;
+    ``render`` alone only ever sets it) becomes non-zero if a predicted label had
+    no colour or a ``choice`` lay outside the scan.  ``render(log_probs, raw_rows, points)`` is the post-network part alone: it allocates nothing, so it can be
+    captured in a graph."""
+
+    def __init__(self, model, calib, colors, npoints=25000, image_size=(375, 1242), groups=None, radius=2, device="cuda"):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.Pn2Error("FrameSegmenter: the HIP device is the only implementation")
+        self.model, self.calib, self.groups = model, calib, _as_groups(groups)
+        self.npoints, self.radius = int(npoints), int(radius)
+        self.image_size = (int(image_size[0]), int(image_size[1]))
+        _half_widths(self.radius, None)
+        self.colors = _dev_u8(colors, self.device, "colors")
+        n, dev, (H, W) = self.npoints, self.device, self.image_size
+        self.raw_rows = torch.empty(n, 4, device=dev, dtype=torch.float32)
+        self.pred = torch.empty(n, device=dev, dtype=torch.int64)
+        self.pts_2d = torch.empty(n, 2, device=dev, dtype=torch.float32)
+        self.pix = torch.empty(n, 2, device=dev, dtype=torch.int32)
+        self.top_pix = torch.empty(n, 2, device=dev, dtype=torch.int32)
+        self.image = torch.empty(H, W, 3, device=dev, dtype=torch.uint8)
+        self.top_view = torch.empty(600, 800, 3, device=dev, dtype=torch.uint8)
+        self._owner = torch.empty(max(H * W, 600 * 800), device=dev, dtype=torch.int32)
+        self.error_flag = torch.zeros(1, device=dev, dtype=torch.int32)
+
+    def choice(self, length, rng="numpy"):
+        """``np.random.choice(length, npoints, replace=True)`` (pcdvis.py:121: a seeded numpy run draws what the reference
+        draws), or the same distribution from a device ``torch.Generator``."""
+        if isinstance(rng, torch.Generator):
+            u = torch.rand(self.npoints, device=self.device, dtype=torch.float64, generator=rng)
+            return torch.clamp((u * length).long(), max=length - 1)
+        if rng != "numpy":
+            raise ValueError('FrameSegmenter: rng must be "numpy" or a device torch.Generator')
+        return torch.from_numpy(np.random.choice(length, self.npoints, replace=True).astype(np.int64)).to(self.device)
+
+    def render(self, log_probs, raw_rows, points, background=None):
+        """Post-network stages into the segmenter's buffers: predict, project ``raw_rows[:, :3]``, draw the camera image over
+        ``background`` and the top view of the normalised ``points``."""
+        H, W = self.image_size
+        predict(log_probs, self.groups, out=self.pred)
+        project_3d_to_2d(raw_rows, self.calib, out=(self.pts_2d, self.pix))
+        draw_2d_points(self.pix, self.pred, self.colors, background, self.image_size, self.radius, None, self.image,
+                       self._owner[:H * W], self.error_flag)
+        top_view_pixels(points, out=self.top_pix)
+        draw_2d_points(self.top_pix, self.pred, self.colors, None, (600, 800), 3, None, self.top_view, self._owner[:600 * 800],
+                       self.error_flag)
+
+    def frame(self, points, background=None, choice=None, rng="numpy"):
+        lib = _lib.load()
+        self.error_flag.zero_()                                      # per frame; an async fill, nothing is read back
+        if isinstance(points, np.ndarray):
+            points = torch.from_numpy(np.ascontiguousarray(points, np.float32))
+        if points.dim() != 2 or points.shape[1] != 4 or points.dtype != torch.float32:
+            raise ValueError("FrameSegmenter.frame: points must be float32 [M, 4] (x, y, z, intensity)")
+        raw = points.to(self.device).contiguous()
+        M = int(raw.shape[0])
+        if M == 0:
+            raise ValueError("FrameSegmenter.frame: empty scan")
+        if choice is None:
+            choice = self.choice(M, rng)
+        choice = torch.as_tensor(choice).to(device=self.device, dtype=torch.int64).reshape(-1).contiguous()
+        if choice.numel() != self.npoints:
+            raise ValueError("FrameSegmenter.frame: choice must hold npoints = %d rows" % self.npoints)
+        n = self.npoints
+        begin = torch.zeros(1, device=self.device, dtype=torch.int64)
+        count = torch.full((1,), M, device=self.device, dtype=torch.int64)
+        normed = torch.empty(1, n, 4, device=self.device, dtype=torch.float32)
+        # (a choice outside the scan sets error_flag and reads row 0 / zeros: numpy raises IndexError)
+        _check(lib.pn2_prepare_clouds(_p(raw), _p(begin), _p(count), None, None, None, _p(choice), 1, n, _p(normed), None,
+                                      _p(self.error_flag), _lib.stream()), "pn2_prepare_clouds")
+        # the resampled raw rows (pcdvis.py:122, :125) through the library's row gather: [1, M, 4] -> [1, n, 4]
+        _check(lib.pn2_gather_rows(_p(raw), _p(choice), 1, M, 4, n, _p(self.raw_rows), _p(self.error_flag), _lib.stream()),
+               "pn2_gather_rows")
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            with torch.no_grad():
+                log_probs = self.model(normed.transpose(2, 1))
+        finally:
+            self.model.train(was_training)
+        if isinstance(log_probs, (tuple, list)):                     # 'pointnet' returns (pred, trans_feat)
+            log_probs = log_probs[0]
+        log_probs = log_probs[0]
+        if background is not None:
+            background = _dev_u8(background, self.device, "background")
+        self.render(log_probs, self.raw_rows, normed[0], background)
+        return {"pred": self.pred, "log_probs": log_probs, "points": normed[0], "pts_3d": self.raw_rows[:, :3],
+                "pts_2d": self.pts_2d, "pix": self.pix, "image": self.image, "top_view": self.top_view}

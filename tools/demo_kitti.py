@@ -1,0 +1,178 @@
+#!/usr/bin/env python3
+"""One frame of the reference's KITTI demo (``python pcdvis.py``) on the HIP library: scan -> labels -> pixels -> two images.
+
+    python tools/demo_kitti.py [--out DIR] [--npoints 25000] [--seed 0] [--merge] [--time]
+    python tools/demo_kitti.py --root $KITTI_ROOT --part 01 --index 0 --calib DIR --config semantic-kitti.yaml [--checkpoint CKPT]
+
+Without ``--root`` the scan is synthetic (``synthetic.kitti_cloud``, un-normalised back to metres), the calibration is the one
+recorded in tests/golden/g18_kitti_view.npz and the network (the zoo's ``PointNet2SemSeg(19, feature_dims=1)``) has seeded random
+weights, so the colours mean nothing; the point is the path.  With ``--root`` the scan, its camera image, the calibration files
+(``--calib``: the directory holding calib_velo_to_cam.txt and calib_cam_to_cam.txt) and the dataset's yaml (``--config``) are read
+from disk, and ``--checkpoint`` loads reference weights.  ``FrameSegmenter`` does the rest on the device; the two images are
+written as PNG through PIL (``semantic.png``: the camera view, ``top_view.png``).  Neither cv2 nor open3d is used.
+
+``--time`` prints one JSON line with medians of 20 (device work included, host clock) for the post-network stages --
+predict + project + both images (``render_ms``), and the same as a captured graph (``render_graph_ms``) -- and beside them, in
+the same run, the same stages the way the reference goes about them, written in this project's own words: an arg-max read back
+to the host (``ref_argmax_ms``), an fp32 stock-torch projection of a host array with its upload and read-back
+(``ref_project_ms``), and -- only if ``cv2`` imports, else null -- one filled ``cv2.circle`` per point on the host
+(``ref_draw_ms``: a median of 3, not of 20; the loop takes tens of milliseconds).
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch                                          # noqa: E402
+
+from pointnet12_amd import kitti_view as V            # noqa: E402
+from pointnet12_amd import synthetic as syn           # noqa: E402
+from pointnet12_amd.pointnet2 import PointNet2SemSeg, load_reference_state   # noqa: E402
+
+# the merge list of the reference's SemKITTI_2_Common comes from the caller; this is the demo's own choice of merges
+MERGE = ["road", "parking+sidewalk+other-ground", "building+fence", "vegetation+trunk+terrain", "pole+traffic-sign",
+         "person+bicyclist+motorcyclist", "car+truck+other-vehicle", "motorcycle+bicycle"]
+
+
+def synthetic_inputs(seed):
+    g = np.load(os.path.join(ROOT, "tests", "golden", "g18_kitti_view.npz"), allow_pickle=False)
+    n = syn.kitti_cloud(seed, 60000, 60000, 1)[:, :4]
+    scan = np.stack([n[:, 0] * 70, n[:, 1] * 70, n[:, 2] * 3, n[:, 3] / 2 + 0.5], 1).astype(np.float32)
+    cfg = {k: dict(zip(g[k + "_keys"].tolist(), g[k + "_values"].tolist())) for k in ("labels", "color_map", "learning_map_inv")}
+    return scan, None, V.Calibration(g["R"], g["T"], g["P"]), cfg
+
+
+def dataset_inputs(args):
+    import yaml
+    from PIL import Image
+    from pointnet12_amd import kitti
+    cfg = yaml.safe_load(open(args.config))
+    seq = os.path.join(args.root, "sequences", args.part)
+    scan, _ = kitti.read_scan(os.path.join(seq, "velodyne", "%06d.bin" % args.index), os.path.join(seq, "labels", "%06d.label" % args.index),
+                              cfg["learning_map"], "inview")
+    fn = os.path.join(seq, "image_2", "%06d.png" % args.index)
+    frame = np.asarray(Image.open(fn).convert("RGB")) if os.path.exists(fn) else None
+    calib = V.Calibration.from_files(os.path.join(args.calib, "calib_velo_to_cam.txt"), os.path.join(args.calib, "calib_cam_to_cam.txt"))
+    return scan, frame, calib, cfg
+
+
+def host_ms(fn, reps=20, warmup=3):
+    for _ in range(warmup):
+        fn()
+    out = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) * 1e3)
+    return round(float(np.median(out)), 4)
+
+
+def baseline_project(points_host, calib, dev):
+    """The projection as a stock-torch user would write it around a host array: upload, fp32 rotation + translation, fp32
+    camera matrix, perspective division, read back -- the shape of work (two host round trips, fp32 products) that the
+    reference's torch formulation does, in this project's own words."""
+    rot = torch.as_tensor(calib.R, dtype=torch.float32, device=dev)
+    shift = torch.as_tensor(calib.T.reshape(3), dtype=torch.float32, device=dev)
+    cam = torch.as_tensor(calib.P, dtype=torch.float32, device=dev)
+    homog = (torch.as_tensor(points_host, device=dev) @ rot.T + shift) @ cam.T
+    return (homog[:, :2] / homog[:, 2:3]).cpu().numpy()
+
+
+def timings(seg, out, calib, colors, frame):
+    lp, raw, pts = out["log_probs"].clone(), seg.raw_rows.clone(), out["points"].clone()
+    bg = None if frame is None else torch.from_numpy(np.ascontiguousarray(frame)).cuda()
+    res = {"npoints": seg.npoints, "image": list(seg.image_size), "device": torch.cuda.get_device_name(0)}
+    res["render_ms"] = host_ms(lambda: seg.render(lp, raw, pts, bg))
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        seg.render(lp, raw, pts, bg)
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        seg.render(lp, raw, pts, bg)
+    res["render_graph_ms"] = host_ms(graph.replay)
+    pred = {}
+
+    def ref_argmax():
+        pred["v"] = lp.argmax(-1).cpu().numpy()
+    res["ref_argmax_ms"] = host_ms(ref_argmax)
+    points_host = raw[:, :3].cpu().numpy()
+    pixels = {}
+
+    def ref_project():
+        pixels["v"] = baseline_project(points_host, calib, raw.device)
+    res["ref_project_ms"] = host_ms(ref_project)
+    res["ref_draw_ms"] = None
+    try:
+        import cv2
+    except ImportError:
+        cv2 = None
+    if cv2 is not None and seg.groups is None:
+        H, W = seg.image_size
+        canvas = np.zeros((H, W, 3), np.uint8) if frame is None else np.ascontiguousarray(frame)
+        centres = [tuple(c) for c in np.nan_to_num(pixels["v"], nan=-1e6, posinf=-1e6, neginf=-1e6).clip(-1e6, 1e6).astype(np.int32).tolist()]
+        paint = [tuple(int(v) for v in colors[k]) for k in pred["v"]]
+
+        def ref_draw():                                    # one filled circle per point on the host, in point order
+            picture = canvas.copy()
+            for k in range(len(centres)):
+                cv2.circle(picture, centres[k], seg.radius, paint[k], -1)
+        res["ref_draw_ms"] = host_ms(ref_draw, reps=3, warmup=1)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default="demo_out")
+    ap.add_argument("--npoints", type=int, default=25000)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--merge", action="store_true", help="predict over the demo's merged classes")
+    ap.add_argument("--time", action="store_true")
+    ap.add_argument("--root")
+    ap.add_argument("--part", default="01")
+    ap.add_argument("--index", type=int, default=0)
+    ap.add_argument("--calib")
+    ap.add_argument("--config")
+    ap.add_argument("--checkpoint")
+    args = ap.parse_args()
+    from PIL import Image
+
+    if args.root:
+        if not (args.calib and args.config):
+            ap.error("--root needs --calib and --config")
+        scan, frame, calib, cfg = dataset_inputs(args)
+    else:
+        scan, frame, calib, cfg = synthetic_inputs(args.seed)
+    names, colors, _ = V.classes_from_config(cfg)
+    torch.manual_seed(args.seed)
+    np.random.seed(args.seed)
+    model = PointNet2SemSeg(len(names), feature_dims=1)
+    if args.checkpoint:
+        state = torch.load(args.checkpoint, map_location="cpu")
+        load_reference_state(model, state.get("model_state_dict", state) if isinstance(state, dict) else state)
+    model = model.cuda().eval()
+    groups = V.merge_groups(names, MERGE, colors) if args.merge else None
+    size = (375, 1242) if frame is None else frame.shape[:2]
+    seg = V.FrameSegmenter(model, calib, colors if groups is None else groups.colors, npoints=args.npoints, image_size=size, groups=groups)
+    out = seg.frame(scan, background=frame)
+    os.makedirs(args.out, exist_ok=True)
+    Image.fromarray(out["image"].cpu().numpy()).save(os.path.join(args.out, "semantic.png"))
+    Image.fromarray(out["top_view"].cpu().numpy()).save(os.path.join(args.out, "top_view.png"))
+    counts = torch.bincount(out["pred"], minlength=len(colors)).cpu().tolist()
+    drawn = int((out["pix"][:, 0] != V.INT32_MIN).sum())
+    print("scan of %d points resampled to %d; %d with a pixel, %d classes predicted; error flag %d; wrote %s/semantic.png and top_view.png"
+          % (len(scan), args.npoints, drawn, sum(c > 0 for c in counts), int(seg.error_flag.item()), args.out))
+    if args.time:
+        print(json.dumps(timings(seg, out, calib, colors if groups is None else groups.colors, frame)))
+
+
+if __name__ == "__main__":
+    main()
