@@ -80,7 +80,7 @@ __global__ __launch_bounds__(kThreads) void nll_bwd_kernel(const int64_t *__rest
     const int c = (int)(i - r * ld);
     const int64_t t = target[r];
     float v = 0.f;
-    if (t == c && t != ignore_index) v = -(*grad_loss) * (weight ? weight[t] : 1.f) / *denom;
+    if (t == c && t < C && t != ignore_index) v = -(*grad_loss) * (weight ? weight[t] : 1.f) / *denom;
     dlogp[i] = v;
 }
 
@@ -125,10 +125,13 @@ __global__ __launch_bounds__(kThreads) void log_softmax_bwd_kernel(const float *
     if (r >= R) return;
     const float *gr = g + r * ldg, *orow = out + r * ldo;
     float gv[kMaxClasses];
-    float s = 0.f;
+    // the row sum as four interleaved partial sums: one running sum over 50..64 like-signed terms (the gradient of y.sum(), of a
+    // per-row weight) carried 3..6 x the rounding error of ATen's tree-shaped sum into every gx through exp(out) * s
+    float s4[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int c = 0; c < kMaxClasses; ++c)
-        if (c < C) { gv[c] = gr[c]; s += gv[c]; }
+        if (c < C) { gv[c] = gr[c]; s4[c & 3] += gv[c]; }
+    const float s = (s4[0] + s4[1]) + (s4[2] + s4[3]);
     float *d = gx + r * ldgx;
 #pragma unroll
     for (int c = 0; c < kMaxClasses; ++c) {

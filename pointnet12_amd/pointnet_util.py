@@ -1070,7 +1070,7 @@ class _LogSoftmaxRows(torch.autograd.Function):
     def backward(ctx, grad):
         out, = ctx.saved_tensors
         P, C = out.shape
-        if grad.stride(-1) != 1:
+        if grad.stride(-1) != 1 or grad.stride(0) < C:        # (a row-broadcast gradient, as .sum(0) hands back, has pitch 0)
             grad = grad.contiguous()
         gx = torch.empty(P, ctx.ld, device=out.device, dtype=torch.float32)
         _check(_lib.load().pn2_log_softmax_bwd(_p(grad), grad.stride(0), _p(out), C, P, C, _p(gx), ctx.ld, _lib.stream()),
