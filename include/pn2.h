@@ -684,6 +684,26 @@ int pn2_splat_discs(const int32_t *pix, int64_t N, const int32_t *half_width, in
  * may be NULL) to 1, as pn2_gather_rows does (the reference's `colors[pred]` raises IndexError). */
 int pn2_splat_resolve(const uint32_t *owner, int H, int W, const int64_t *label, int64_t N, const uint8_t *colors, int C,
                       const uint8_t *background, uint8_t *out, int *err, pn2_stream_t stream);
+/* pn2_depth_splat + pn2_depth_resolve (+ pn2_splat_resolve for the colours) replace the demo's 3-D ego view, Window_Manager.update
+ * (pcdvis.py:31-51, called at :143): the cloud seen through a fixed pinhole camera (config/ego_view.json), drawn as square points
+ * of integer size (config/render_option.json) with a depth test.  THE RASTERISATION RULE IS STATED HERE, NOT TAKEN FROM open3d,
+ * against which it could not be checked.  xyz: N rows of pitch ldx >= 3 floats, read in place; extrinsic host double[12] (3 x 4,
+ * row-major: [R | t], world -> camera, +X right, +Y down, +Z forward); intrinsic host double[4]: fx, fy, cx, cy.  Per point i, in
+ * fp64 on the fp32 coordinates, every product and sum rounded separately in this order (no fused multiply-add):
+ *   c_k = ((E[k][0]*x + E[k][1]*y) + E[k][2]*z) + E[k][3],  Z = c_2;  drawn iff z_near < Z && Z < z_far (a NaN Z is not);
+ *   d = f32(Z);  xw = ((fx*c_0)/Z + cx) + 0.5,  yw = ((fy*c_1)/Z + cy) + 0.5  (the principal point counts pixel centres);
+ *   skipped if xw or yw is not finite or reaches 2^30 in magnitude (compared as doubles, before any integer conversion);
+ *   OpenGL's non-antialiased point of size s: columns x0 .. x0 + s - 1 with x0 = floor(xw + (s even ? 0.5 : 0.0)) - s / 2,
+ *   rows likewise from yw (row = y, top row first), clipped to [0, W) x [0, H).
+ * Every covered pixel takes the minimum of key = bits(d) << 32 | i (64-bit unsigned; zkey [H * W], set to all-ones by the call
+ * itself): the nearest point wins, the lowest index among equal float32 depths (GL_LESS in draw order); integer minima commute,
+ * the result does not depend on scheduling.  0 < z_near < z_far <= 3e38, so d is finite and its bits order like its value.
+ * 1 <= point_size <= 16 (else PN2_EUNSUPPORTED), H * W < 2^31, N < 2^31; N == 0 leaves the empty image. */
+int pn2_depth_splat(const float *xyz, int ldx, int64_t N, const double *extrinsic, const double *intrinsic, double z_near,
+                    double z_far, int point_size, int H, int W, uint64_t *zkey, pn2_stream_t stream);
+/* owner (uint32 [H * W], may be NULL) = the visible point's index + 1, 0 where the pixel is empty: the format pn2_splat_resolve
+ * colours from.  depth (float [H * W], may be NULL) = that point's float32 depth, +inf where empty. */
+int pn2_depth_resolve(const uint64_t *zkey, int H, int W, uint32_t *owner, float *depth, pn2_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -102,6 +102,8 @@ SIGNATURES = {
     "pn2_project_points": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
     "pn2_splat_discs": (_i, [_vp, _i64, _vp, _i, _i, _i, _vp, _vp]),
     "pn2_splat_resolve": (_i, [_vp, _i, _i, _vp, _i64, _vp, _i, _vp, _vp, _vp, _vp]),
+    "pn2_depth_splat": (_i, [_vp, _i, _i64, _vp, _vp, _d, _d, _i, _i, _i, _vp, _vp]),
+    "pn2_depth_resolve": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
 }
 
 

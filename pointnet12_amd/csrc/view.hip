@@ -11,6 +11,10 @@
 //   pn2_splat_resolve    pixel shows the LAST point that covered it: here that order is an integer maximum, owner[p] = max(i + 1)
 //                        over the points i whose disc covers p (non-returning 32-bit atomics), and a second pass colours every
 //                        pixel from its owner's label.  Integer maxima commute: the image is bit-identical from run to run.
+//   pn2_depth_splat /    the 3-D ego view, Window_Manager.update (pcdvis.py:31-51, :143): the scan seen through a fixed pinhole
+//   pn2_depth_resolve    camera, drawn as square points of integer size with a depth test.  Here the depth test is an integer
+//                        minimum of (float32 depth bits, point index) per pixel (non-returning 64-bit atomics): the nearest
+//                        point wins, the lowest index among equal depths (GL_LESS in draw order); minima commute as well.
 //
 // Small tables (calibration, merge groups, the disc's row half-widths) are HOST arrays: they are validated on the host and
 // travel inside the launch's arguments, so no entry point allocates, copies or waits, and every call can be captured in a graph.
@@ -38,6 +42,13 @@ struct Calib {
 struct Stencil {
     int half_width[kMaxStencilRows];
 };
+struct Pinhole {
+    double E[12];                               // [R | t], row-major
+    double fx, fy, cx, cy;
+    double z_near, z_far;
+};
+constexpr int kMaxPointSize = 16;
+constexpr unsigned long long kEmptyKey = ~0ull;
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
@@ -156,6 +167,47 @@ __global__ __launch_bounds__(kThreads) void splat_resolve_kernel(const unsigned 
     out[3 * p] = r; out[3 * p + 1] = g; out[3 * p + 2] = b;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- depth test
+// One thread per (point, row of its square).  fp64 on the widened fp32 coordinates, every product and sum rounded separately and in
+// the order include/pn2.h states (this file is built with -ffp-contract=off).  The centre is compared as a double before anything
+// is converted to an integer: below 2^30 in magnitude, floor() and the half size fit 64 bits with room to spare.
+__global__ __launch_bounds__(kThreads) void depth_splat_kernel(const float *__restrict__ xyz, int ldx, int64_t N, Pinhole cam, int s,
+                                                               int H, int W, unsigned long long *__restrict__ zkey) {
+    const int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (t >= N * s) return;
+    const int64_t i = t / s;
+    const int j = (int)(t - i * s);
+    const float *p = xyz + i * ldx;
+    const double x = (double)p[0], y = (double)p[1], z = (double)p[2];
+    double c[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c[k] = ((cam.E[4 * k] * x + cam.E[4 * k + 1] * y) + cam.E[4 * k + 2] * z) + cam.E[4 * k + 3];
+    const double Z = c[2];
+    if (!(cam.z_near < Z && Z < cam.z_far)) return;                 // (a NaN depth fails both)
+    const float d = (float)Z;                                       // finite and not negative: its bits order like its value
+    const double xw = ((cam.fx * c[0]) / Z + cam.cx) + 0.5, yw = ((cam.fy * c[1]) / Z + cam.cy) + 0.5;
+    if (!(fabs(xw) < 1073741824.0) || !(fabs(yw) < 1073741824.0)) return;      // not finite, or 2^30 and beyond
+    const double half = (s & 1) ? 0.0 : 0.5;
+    const int64_t row = (int64_t)floor(yw + half) - s / 2 + j;
+    if (row < 0 || row >= H) return;
+    const int64_t lo = (int64_t)floor(xw + half) - s / 2, hi = lo + s - 1;
+    const int64_t x0 = lo < 0 ? 0 : lo, x1 = hi > W - 1 ? W - 1 : hi;
+    unsigned long long *line = zkey + row * W;
+    const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)i;
+    for (int64_t col = x0; col <= x1; ++col)
+        (void)__hip_atomic_fetch_min(line + col, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);    // result unused: non-returning
+}
+
+__global__ __launch_bounds__(kThreads) void depth_resolve_kernel(const unsigned long long *__restrict__ zkey, int64_t pixels,
+                                                                 unsigned *__restrict__ owner, float *__restrict__ depth) {
+    const int64_t p = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (p >= pixels) return;
+    const unsigned long long key = zkey[p];
+    const bool empty = key == kEmptyKey;
+    if (owner != nullptr) owner[p] = empty ? 0u : (unsigned)key + 1u;
+    if (depth != nullptr) depth[p] = empty ? __uint_as_float(0x7f800000u) : __uint_as_float((unsigned)(key >> 32));
+}
+
 }  // namespace
 
 extern "C" {
@@ -235,6 +287,35 @@ int pn2_splat_resolve(const uint32_t *owner, int H, int W, const int64_t *label,
     const int64_t pixels = (int64_t)H * W;
     hipLaunchKernelGGL(splat_resolve_kernel, dim3((unsigned)pn2_cdiv(pixels, kThreads)), dim3(kThreads), 0, pn2_s(stream), owner,
                        pixels, label, N, colors, C, background, out, err);
+    return pn2_launch_status();
+}
+
+int pn2_depth_splat(const float *xyz, int ldx, int64_t N, const double *extrinsic, const double *intrinsic, double z_near,
+                    double z_far, int point_size, int H, int W, uint64_t *zkey, pn2_stream_t stream) {
+    PN2_CHECK_ARG(ldx >= 3 && N >= 0 && (N == 0 || xyz) && extrinsic && intrinsic && H > 0 && W > 0 && zkey);
+    PN2_CHECK_ARG((int64_t)H * W < (int64_t)1 << 31 && N < (int64_t)1 << 31);
+    PN2_CHECK_ARG(0.0 < z_near && z_near < z_far && z_far <= 3e38);                                  // (NaN planes fail)
+    if (point_size < 1 || point_size > kMaxPointSize) return PN2_EUNSUPPORTED;
+    pn2_fill_u32(zkey, 0xffffffffu, 2 * (int64_t)H * W, pn2_s(stream));     // (a kernel, not a memset node: see pn2_common.h)
+    if (N > 0) {
+        Pinhole cam;
+        for (int k = 0; k < 12; ++k) cam.E[k] = extrinsic[k];
+        cam.fx = intrinsic[0]; cam.fy = intrinsic[1]; cam.cx = intrinsic[2]; cam.cy = intrinsic[3];
+        cam.z_near = z_near; cam.z_far = z_far;
+        const int64_t blocks = pn2_cdiv(N * point_size, kThreads);
+        PN2_CHECK_ARG(blocks <= 0x7fffffff);
+        hipLaunchKernelGGL(depth_splat_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, pn2_s(stream), xyz, ldx, N, cam, point_size,
+                           H, W, reinterpret_cast<unsigned long long *>(zkey));
+    }
+    return pn2_launch_status();
+}
+
+int pn2_depth_resolve(const uint64_t *zkey, int H, int W, uint32_t *owner, float *depth, pn2_stream_t stream) {
+    PN2_CHECK_ARG(zkey && H > 0 && W > 0 && (int64_t)H * W < (int64_t)1 << 31);
+    if (owner == nullptr && depth == nullptr) return PN2_OK;
+    const int64_t pixels = (int64_t)H * W;
+    hipLaunchKernelGGL(depth_resolve_kernel, dim3((unsigned)pn2_cdiv(pixels, kThreads)), dim3(kThreads), 0, pn2_s(stream),
+                       reinterpret_cast<const unsigned long long *>(zkey), pixels, owner, depth);
     return pn2_launch_status();
 }
 

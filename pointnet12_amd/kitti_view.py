@@ -9,6 +9,10 @@ one ``cv2.circle`` at a time (``draw_2d_points``, data_utils/kitti_utils.py:368-
     ``SemKITTI_2_Common`` (kitti_utils.py:41-58, :92-117) -- ``pn2_seg_predict``;
   * ``project_3d_to_2d``              kitti_utils.py:313-336 -- ``pn2_project_points``;
   * ``draw_2d_points`` / ``draw_2d_top_view``   kitti_utils.py:368-392 -- ``pn2_splat_discs`` + ``pn2_splat_resolve``;
+  * ``render_points``                 the 3-D ego view, ``Window_Manager.update`` (pcdvis.py:31-51, :143): the scan through the fixed
+    pinhole camera of ``config/ego_view.json`` (``PinholeCamera.from_json``), square points of ``config/render_option.json``'s
+    size (``RenderOption.from_json``), nearest point per pixel -- ``pn2_depth_splat`` + ``pn2_depth_resolve`` +
+    ``pn2_splat_resolve``; also the depth image and the index image (which point is visible where) of a cloud;
   * ``FrameSegmenter``                the frame loop's body, device tensors in and out, nothing read back.
 
 Nothing here copies the reference's tables: class names and colours come from the dataset's own ``semantic-kitti.yaml``
@@ -29,9 +33,18 @@ Differences from the reference, all deliberate:
     default tables below (radius 2: rows of 3, 5, 5, 5, 3 pixels = 21; radius 3: 3, 5, 7, 7, 7, 5, 3 = 37) were written from
     memory of OpenCV's filled-circle rasteriser and could not be checked, because OpenCV was not available where this was
     written.  The tests hold the kernel to the table, not to OpenCV.  Any other radius needs an explicit ``half_widths``.
+  * THE EGO VIEW'S RASTERISATION RULE IS UNVERIFIED AGAINST OPEN3D.  The reference lets open3d's GL window draw the cloud;
+    open3d was not available where this was written, so ``render_points`` states its rule itself (``pn2_depth_splat`` in
+    include/pn2.h): an fp64 pinhole projection with the principal point counting pixel centres, OpenGL's rule for a
+    non-antialiased point of integer size (a square of ``point_size`` pixels, ``floor`` of the window coordinate, plus a half for
+    even sizes), and ``GL_LESS`` on the float32 camera depth with the lowest point index winning among equal depths.  The tests
+    hold the kernel to an fp64 restatement of that rule, not to open3d; a pixel here and there may differ from open3d's window.
+  * THE EGO VIEW'S NEAR / FAR PLANES ARE THIS PACKAGE'S CHOICE (0.1 and 1000 in the cloud's units), also unverified: open3d
+    derives its clipping planes from the scene's bounding box.  Lighting, normals and the coordinate frame are not drawn.
   * float32 log-probabilities on the GPU only: a CPU tensor raises ``Pn2Error``; there is no fallback path.
 """
 import ctypes
+import json
 
 import numpy as np
 import torch
@@ -369,6 +382,140 @@ def draw_2d_top_view(pcd_3d, labels, colors, out=None, owner=None, err=None):
     return draw_2d_points(top_view_pixels(pcd_3d), labels, colors, None, (600, 800), 3, None, out, owner, err)
 
 
+# ----------------------------------------------------------------------------------------------------------------- ego view
+class PinholeCamera:
+    """``extrinsic`` ``[4, 4]`` (world -> camera; +X right, +Y down, +Z forward, open3d's convention), ``intrinsic`` ``[3, 3]``
+    (float64) and the image's ``width`` / ``height``.  ``E`` is the ``[3, 4]`` block ``[R | t]`` and ``K`` the four numbers
+    ``fx, fy, cx, cy`` that ``pn2_depth_splat`` reads; a skewed intrinsic matrix is refused."""
+
+    def __init__(self, extrinsic, intrinsic, width, height):
+        self.extrinsic = np.ascontiguousarray(extrinsic, np.float64).reshape(4, 4)
+        self.intrinsic = np.ascontiguousarray(intrinsic, np.float64).reshape(3, 3)
+        self.width, self.height = int(width), int(height)
+        if self.width <= 0 or self.height <= 0:
+            raise ValueError("PinholeCamera: width and height must be positive")
+        k = self.intrinsic
+        if k[0, 1] != 0 or k[1, 0] != 0 or k[2, 0] != 0 or k[2, 1] != 0 or k[2, 2] != 1:
+            raise ValueError("PinholeCamera: the intrinsic matrix must be [[fx, 0, cx], [0, fy, cy], [0, 0, 1]]")
+        self.E = np.ascontiguousarray(self.extrinsic[:3, :])
+        self.K = np.array([k[0, 0], k[1, 1], k[0, 2], k[1, 2]], np.float64)
+
+    @classmethod
+    def from_json(cls, fn):
+        """An open3d ``PinholeCameraParameters`` file (the reference's ``config/ego_view.json``): ``extrinsic`` holds 16 numbers and
+        ``intrinsic.intrinsic_matrix`` 9, both COLUMN-major (so the translation is extrinsic numbers 12, 13 and 14);
+        keys this class does not know (``h_fov``, ``d_range``, ...) are ignored."""
+        with open(fn, "r") as f:
+            d = json.load(f)
+        intr = d["intrinsic"]
+        ext = np.array(d["extrinsic"], np.float64)
+        mat = np.array(intr["intrinsic_matrix"], np.float64)
+        if ext.shape != (16,) or mat.shape != (9,):
+            raise ValueError("%s: extrinsic must hold 16 numbers and intrinsic.intrinsic_matrix 9" % fn)
+        return cls(ext.reshape(4, 4).T, mat.reshape(3, 3).T, intr["width"], intr["height"])
+
+
+class RenderOption:
+    """``point_size`` (int) and ``background_color`` (a uint8 triple) of an open3d ``RenderOption``; nothing else of it is used."""
+
+    def __init__(self, point_size=2, background_color=(0, 0, 0)):
+        if int(point_size) != point_size:
+            raise ValueError("RenderOption: point_size %r is not an integer (only whole point sizes are drawn)" % (point_size,))
+        self.point_size = int(point_size)
+        self.background_color = tuple(int(c) for c in background_color)
+        if len(self.background_color) != 3 or not all(0 <= c <= 255 for c in self.background_color):
+            raise ValueError("RenderOption: background_color must be three values in 0 .. 255")
+
+    @classmethod
+    def from_json(cls, fn):
+        """An open3d ``RenderOption`` file (the reference's ``config/render_option.json``): ``point_size`` as an int (a non-integer
+        size raises ``ValueError``), ``background_color`` (floats in [0, 1]) as ``round(c * 255)``.  A missing key takes this
+        class's default (2, black); every other key is ignored."""
+        with open(fn, "r") as f:
+            d = json.load(f)
+        bg = d.get("background_color", (0.0, 0.0, 0.0))
+        if len(bg) != 3 or not all(0.0 <= float(c) <= 1.0 for c in bg):
+            raise ValueError("%s: background_color must be three floats in [0, 1]" % fn)
+        return cls(d.get("point_size", 2), tuple(int(round(float(c) * 255)) for c in bg))
+
+
+def _buffer(t, numel, itemsize, dev, what):
+    if not isinstance(t, torch.Tensor) or t.numel() != numel or t.element_size() != itemsize or not t.is_contiguous() or t.device != dev:
+        raise ValueError("render_points: %s must be a contiguous %d-byte tensor of %d elements on %s" % (what, itemsize, numel, dev))
+    return t
+
+
+def render_points(pts_3d, labels, colors, camera, point_size=2, background=(0, 0, 0), near=0.1, far=1000.0, out=None, zkey=None,
+                  owner=None, depth=None, err=None, return_depth=False, return_index=False):
+    """The 3-D ego view of ``Window_Manager.update`` (pcdvis.py:31-51): uint8 ``[H, W, 3]`` on the device, ``H, W`` the camera's.
+    ``pts_3d``: float32 ``[N, >= 3]`` (the first three columns of scan rows are read in place), ``labels`` int64 ``[N]``, ``colors``
+    uint8 ``[C, 3]``, as for ``draw_2d_points``.  Point ``i`` is a square of ``point_size`` pixels (1 .. 16) of ``colors[labels[i]]``
+    around its projection through ``camera`` (a ``PinholeCamera``); every pixel shows the NEAREST point that covers it, the
+    lowest index among points of equal float32 depth; a pixel no point covers shows ``background`` (a colour triple, or a uint8
+    ``[H, W, 3]`` image, not modified).  Points with a camera depth outside ``(near, far)`` are not drawn.  The rule is written
+    out in include/pn2.h (``pn2_depth_splat``) and is UNVERIFIED AGAINST OPEN3D, as are the defaults ``near = 0.1`` and
+    ``far = 1000``: they are this package's choice, open3d derives its planes from the scene's bounding box (module docstring).
+
+    ``return_depth`` adds float32 ``[H, W]``, the visible point's camera depth (``+inf``: empty); ``return_index`` adds int32
+    ``[H, W]``, its index (``-1``: empty) -- the range / index image of the cloud; the return value is then a tuple in that order.
+
+    A label outside ``[0, C)`` leaves the background and sets ``err`` (a zeroed device int32 tensor); without ``err`` the flag is
+    read back and raises ``IndexError`` (skipped under stream capture).  ``out``, ``zkey`` (64-bit, ``[H * W]``), ``owner``
+    (32-bit, ``[H * W]``) and ``depth`` (float32, ``[H * W]`` elements): buffers to write into.  With ``out``, ``zkey``, ``owner``
+    and ``err`` given (and ``depth`` if it is asked for, and a black or an image background) the image is drawn without an
+    allocation or a read-back, so the call can be captured in a graph."""
+    if not isinstance(labels, torch.Tensor) or not labels.is_cuda:
+        raise _lib.Pn2Error("render_points: points and labels must live on the GPU: this package has no CPU path")
+    pts, N, ld = _xyz_rows(pts_3d, "render_points")
+    dev = pts.device
+    if int(point_size) != point_size:
+        raise ValueError("render_points: point_size %r is not an integer" % (point_size,))
+    if labels.numel() != N or labels.dtype != torch.int64:
+        raise ValueError("render_points: labels must be int64 [%d]" % N)
+    labels = labels.reshape(-1).contiguous()
+    colors = _dev_u8(colors, dev, "colors")
+    if colors.dim() != 2 or colors.shape[1] != 3:
+        raise ValueError("render_points: colors must be [C, 3]")
+    H, W = camera.height, camera.width
+    if isinstance(background, (torch.Tensor, np.ndarray)):
+        background = _dev_u8(background, dev, "background")
+        if background.shape != (H, W, 3):
+            raise ValueError("render_points: a background image must be [%d, %d, 3]" % (H, W))
+    else:
+        bg = tuple(int(c) for c in background)
+        if len(bg) != 3 or not all(0 <= c <= 255 for c in bg):
+            raise ValueError("render_points: a background colour must be three values in 0 .. 255")
+        background = None if bg == (0, 0, 0) else torch.tensor(bg, device=dev, dtype=torch.uint8).expand(H, W, 3).contiguous()
+    if out is None:
+        out = torch.empty(H, W, 3, device=dev, dtype=torch.uint8)
+    elif out.shape != (H, W, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != dev:
+        raise ValueError("render_points: out must be a contiguous uint8 [%d, %d, 3] tensor on %s" % (H, W, dev))
+    zkey = torch.empty(H * W, device=dev, dtype=torch.int64) if zkey is None else _buffer(zkey, H * W, 8, dev, "zkey")
+    owner = torch.empty(H * W, device=dev, dtype=torch.int32) if owner is None else _buffer(owner, H * W, 4, dev, "owner")
+    if depth is None and return_depth:
+        depth = torch.empty(H, W, device=dev, dtype=torch.float32)
+    if depth is not None:
+        if depth.dtype != torch.float32:
+            raise RuntimeError("render_points: depth must be float32 (got %s)" % depth.dtype)
+        _buffer(depth, H * W, 4, dev, "depth")
+    flag = err if err is not None else torch.zeros(1, device=dev, dtype=torch.int32)
+    lib, st = _lib.load(), _lib.stream()
+    _check(lib.pn2_depth_splat(_p(pts) if N > 0 else None, ld, N, camera.E.ctypes.data_as(ctypes.c_void_p),
+                               camera.K.ctypes.data_as(ctypes.c_void_p), float(near), float(far), int(point_size), H, W, _p(zkey), st),
+           "pn2_depth_splat")
+    _check(lib.pn2_depth_resolve(_p(zkey), H, W, _p(owner), _p(depth), st), "pn2_depth_resolve")
+    _check(lib.pn2_splat_resolve(_p(owner), H, W, _p(labels), N, _p(colors), int(colors.shape[0]), _p(background), _p(out), _p(flag), st),
+           "pn2_splat_resolve")
+    if err is None and not torch.cuda.is_current_stream_capturing() and int(flag.item()) != 0:
+        raise IndexError("render_points: a label is outside [0, %d)" % colors.shape[0])
+    ret = (out,)
+    if return_depth:
+        ret += (depth.view(H, W),)
+    if return_index:
+        ret += (owner.view(torch.int32).view(H, W) - 1,)
+    return ret if len(ret) > 1 else out
+
+
 # -------------------------------------------------------------------------------------------------------------------- frame
 class FrameSegmenter:
     """The body of the reference's frame loop (pcdvis.py:116-144) for one scan ``[M, 4]`` (x, y, z, intensity, as
@@ -382,9 +529,14 @@ class FrameSegmenter:
     by the segmenter and overwritten by the next frame.  ``error_flag`` (device int32, cleared at the start of every ``frame``;
     ``render`` alone only ever sets it) becomes non-zero if a predicted label had
     no colour or a ``choice`` lay outside the scan.  ``render(log_probs, raw_rows, points)`` is the post-network part alone: it allocates nothing, so it can be
-    captured in a graph."""
+    captured in a graph.
 
-    def __init__(self, model, calib, colors, npoints=25000, image_size=(375, 1242), groups=None, radius=2, device="cuda"):
+    ``camera`` (a ``PinholeCamera``): ``render`` then also draws the 3-D ego view of the un-normalised points (pcdvis.py:143,
+    ``render_points`` with ``point_size`` on ``ego_background``, a colour triple) into ``ego_view`` uint8
+    ``[camera.height, camera.width, 3]``, and ``frame`` returns it under ``"ego_view"``.  Without a camera there is no such key, buffer or launch."""
+
+    def __init__(self, model, calib, colors, npoints=25000, image_size=(375, 1242), groups=None, radius=2, device="cuda", camera=None,
+                 point_size=2, ego_background=(0, 0, 0)):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.Pn2Error("FrameSegmenter: the HIP device is the only implementation")
@@ -401,7 +553,15 @@ class FrameSegmenter:
         self.top_pix = torch.empty(n, 2, device=dev, dtype=torch.int32)
         self.image = torch.empty(H, W, 3, device=dev, dtype=torch.uint8)
         self.top_view = torch.empty(600, 800, 3, device=dev, dtype=torch.uint8)
-        self._owner = torch.empty(max(H * W, 600 * 800), device=dev, dtype=torch.int32)
+        self.camera, self.point_size = camera, RenderOption(point_size).point_size
+        ego = 0 if camera is None else camera.height * camera.width
+        self._owner = torch.empty(max(H * W, 600 * 800, ego), device=dev, dtype=torch.int32)
+        if camera is not None:
+            self.ego_view = torch.empty(camera.height, camera.width, 3, device=dev, dtype=torch.uint8)
+            self._zkey = torch.empty(ego, device=dev, dtype=torch.int64)
+            bg = RenderOption(self.point_size, ego_background).background_color
+            self._ego_background = bg if bg == (0, 0, 0) else \
+                torch.tensor(bg, device=dev, dtype=torch.uint8).expand(camera.height, camera.width, 3).contiguous()
         self.error_flag = torch.zeros(1, device=dev, dtype=torch.int32)
 
     def choice(self, length, rng="numpy"):
@@ -416,7 +576,7 @@ class FrameSegmenter:
 
     def render(self, log_probs, raw_rows, points, background=None):
         """Post-network stages into the segmenter's buffers: predict, project ``raw_rows[:, :3]``, draw the camera image over
-        ``background`` and the top view of the normalised ``points``."""
+        ``background`` and the top view of the normalised ``points``; with a camera, the ego view of ``raw_rows[:, :3]`` too."""
         H, W = self.image_size
         predict(log_probs, self.groups, out=self.pred)
         project_3d_to_2d(raw_rows, self.calib, out=(self.pts_2d, self.pix))
@@ -425,6 +585,9 @@ class FrameSegmenter:
         top_view_pixels(points, out=self.top_pix)
         draw_2d_points(self.top_pix, self.pred, self.colors, None, (600, 800), 3, None, self.top_view, self._owner[:600 * 800],
                        self.error_flag)
+        if self.camera is not None:
+            render_points(raw_rows, self.pred, self.colors, self.camera, self.point_size, self._ego_background, out=self.ego_view,
+                          zkey=self._zkey, owner=self._owner[:self.camera.height * self.camera.width], err=self.error_flag)
 
     def frame(self, points, background=None, choice=None, rng="numpy"):
         lib = _lib.load()
@@ -465,5 +628,8 @@ class FrameSegmenter:
         if background is not None:
             background = _dev_u8(background, self.device, "background")
         self.render(log_probs, self.raw_rows, normed[0], background)
-        return {"pred": self.pred, "log_probs": log_probs, "points": normed[0], "pts_3d": self.raw_rows[:, :3],
-                "pts_2d": self.pts_2d, "pix": self.pix, "image": self.image, "top_view": self.top_view}
+        out = {"pred": self.pred, "log_probs": log_probs, "points": normed[0], "pts_3d": self.raw_rows[:, :3],
+               "pts_2d": self.pts_2d, "pix": self.pix, "image": self.image, "top_view": self.top_view}
+        if self.camera is not None:
+            out["ego_view"] = self.ego_view
+        return out

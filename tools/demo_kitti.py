@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""One frame of the reference's KITTI demo (``python pcdvis.py``) on the HIP library: scan -> labels -> pixels -> two images.
+"""One frame of the reference's KITTI demo (``python pcdvis.py``) on the HIP library: scan -> labels -> pixels -> two images,
+three with ``--ego``.
 
-    python tools/demo_kitti.py [--out DIR] [--npoints 25000] [--seed 0] [--merge] [--time]
+    python tools/demo_kitti.py [--out DIR] [--npoints 25000] [--seed 0] [--merge] [--time] [--ego CAMERA.json [--render-option FILE.json]]
     python tools/demo_kitti.py --root $KITTI_ROOT --part 01 --index 0 --calib DIR --config semantic-kitti.yaml [--checkpoint CKPT]
 
 Without ``--root`` the scan is synthetic (``synthetic.kitti_cloud``, un-normalised back to metres), the calibration is the one
@@ -11,12 +12,19 @@ weights, so the colours mean nothing; the point is the path.  With ``--root`` th
 from disk, and ``--checkpoint`` loads reference weights.  ``FrameSegmenter`` does the rest on the device; the two images are
 written as PNG through PIL (``semantic.png``: the camera view, ``top_view.png``).  Neither cv2 nor open3d is used.
 
+``--ego CAMERA.json`` (an open3d ``PinholeCameraParameters`` file, the reference's ``config/ego_view.json``) adds the demo's 3-D ego
+view (``Window_Manager.update``, pcdvis.py:31-51) as ``ego_view.png``; ``--render-option FILE.json`` (an open3d ``RenderOption``
+file, the reference's ``config/render_option.json``) sets its point size and background colour (defaults: 2, black).  The picture follows the rule stated in include/pn2.h, which is unverified against open3d.
+
 ``--time`` prints one JSON line with medians of 20 (device work included, host clock) for the post-network stages --
 predict + project + both images (``render_ms``), and the same as a captured graph (``render_graph_ms``) -- and beside them, in
 the same run, the same stages the way the reference goes about them, written in this project's own words: an arg-max read back
 to the host (``ref_argmax_ms``), an fp32 stock-torch projection of a host array with its upload and read-back
 (``ref_project_ms``), and -- only if ``cv2`` imports, else null -- one filled ``cv2.circle`` per point on the host
-(``ref_draw_ms``: a median of 3, not of 20; the loop takes tens of milliseconds).
+(``ref_draw_ms``: a median of 3, not of 20; the loop takes tens of milliseconds).  With ``--ego`` also the ego view's stage alone
+(``ego_ms``: depth test, resolve and colouring into the segmenter's buffers) beside a stock-torch z-buffer of the same picture
+(``ref_zbuffer_ms``: fp64 projection, packed int64 (depth bits, index) keys, ``scatter_reduce(..., "amin")`` per square offset,
+colours gathered from the winners); ``ego_matches_ref`` says whether the two pictures are equal.
 """
 import argparse
 import json
@@ -85,6 +93,34 @@ def baseline_project(points_host, calib, dev):
     return (homog[:, :2] / homog[:, 2:3]).cpu().numpy()
 
 
+def baseline_zbuffer(pts, labels, colors, cam, s, background=(0, 0, 0), near=0.1, far=1000.0):
+    """The ego view as a stock-torch user would write it: fp64 pinhole projection, one int64 key per point (float32 depth bits
+    above the index), a ``scatter_reduce`` minimum per offset of the square, then colours gathered from the winning indices."""
+    dev = pts.device
+    H, W = cam.height, cam.width
+    E = torch.as_tensor(cam.E, device=dev)
+    fx, fy, cx, cy = cam.K.tolist()
+    c = pts[:, :3].double() @ E[:, :3].T + E[:, 3]
+    Z = c[:, 2]
+    xw, yw = fx * c[:, 0] / Z + cx + 0.5, fy * c[:, 1] / Z + cy + 0.5
+    ok = (Z > near) & (Z < far) & (xw.abs() < 2.0 ** 30) & (yw.abs() < 2.0 ** 30)
+    half = 0.5 if s % 2 == 0 else 0.0
+    x0 = torch.floor(torch.where(ok, xw, torch.zeros_like(xw)) + half).long() - s // 2
+    y0 = torch.floor(torch.where(ok, yw, torch.zeros_like(yw)) + half).long() - s // 2
+    key = (Z.float().view(torch.int32).long() << 32) | torch.arange(len(pts), device=dev)
+    empty = torch.iinfo(torch.int64).max
+    zbuf = torch.full((H * W,), empty, device=dev, dtype=torch.int64)
+    for dy in range(s):
+        for dx in range(s):
+            x, y = x0 + dx, y0 + dy
+            m = ok & (x >= 0) & (x < W) & (y >= 0) & (y < H)
+            zbuf.scatter_reduce_(0, (y * W + x)[m], key[m], "amin")
+    seen = zbuf != empty
+    img = torch.as_tensor(background, device=dev, dtype=torch.uint8).expand(H * W, 3).contiguous()
+    img[seen] = colors[labels[(zbuf[seen] & 0xffffffff)]]
+    return img.view(H, W, 3)
+
+
 def timings(seg, out, calib, colors, frame):
     lp, raw, pts = out["log_probs"].clone(), seg.raw_rows.clone(), out["points"].clone()
     bg = None if frame is None else torch.from_numpy(np.ascontiguousarray(frame)).cuda()
@@ -110,6 +146,19 @@ def timings(seg, out, calib, colors, frame):
     def ref_project():
         pixels["v"] = baseline_project(points_host, calib, raw.device)
     res["ref_project_ms"] = host_ms(ref_project)
+    if seg.camera is not None:
+        cam, s = seg.camera, seg.point_size
+        option_background = (0, 0, 0) if isinstance(seg._ego_background, tuple) else seg._ego_background[0, 0].tolist()
+        owner = seg._owner[:cam.height * cam.width]
+        res["ego"] = [cam.height, cam.width, s]
+        res["ego_ms"] = host_ms(lambda: V.render_points(raw, seg.pred, seg.colors, cam, s, out=seg.ego_view, zkey=seg._zkey, owner=owner,
+                                                        background=seg._ego_background, err=seg.error_flag))
+        picture = {}
+
+        def ref_zbuffer():
+            picture["v"] = baseline_zbuffer(raw, seg.pred, seg.colors, cam, s, option_background)
+        res["ref_zbuffer_ms"] = host_ms(ref_zbuffer)
+        res["ego_matches_ref"] = bool(torch.equal(picture["v"], seg.ego_view))
     res["ref_draw_ms"] = None
     try:
         import cv2
@@ -136,6 +185,8 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--merge", action="store_true", help="predict over the demo's merged classes")
     ap.add_argument("--time", action="store_true")
+    ap.add_argument("--ego", metavar="CAMERA.json", help="also draw the 3-D ego view through this open3d PinholeCameraParameters file")
+    ap.add_argument("--render-option", metavar="FILE.json", help="open3d RenderOption file: the ego view's point size and background colour")
     ap.add_argument("--root")
     ap.add_argument("--part", default="01")
     ap.add_argument("--index", type=int, default=0)
@@ -161,11 +212,20 @@ def main():
     model = model.cuda().eval()
     groups = V.merge_groups(names, MERGE, colors) if args.merge else None
     size = (375, 1242) if frame is None else frame.shape[:2]
-    seg = V.FrameSegmenter(model, calib, colors if groups is None else groups.colors, npoints=args.npoints, image_size=size, groups=groups)
+    if args.render_option and not args.ego:
+        ap.error("--render-option needs --ego")
+    camera = V.PinholeCamera.from_json(args.ego) if args.ego else None
+    option = V.RenderOption.from_json(args.render_option) if args.render_option else V.RenderOption()
+    seg = V.FrameSegmenter(model, calib, colors if groups is None else groups.colors, npoints=args.npoints, image_size=size, groups=groups,
+                           camera=camera, point_size=option.point_size, ego_background=option.background_color)
     out = seg.frame(scan, background=frame)
     os.makedirs(args.out, exist_ok=True)
     Image.fromarray(out["image"].cpu().numpy()).save(os.path.join(args.out, "semantic.png"))
     Image.fromarray(out["top_view"].cpu().numpy()).save(os.path.join(args.out, "top_view.png"))
+    if camera is not None:
+        Image.fromarray(out["ego_view"].cpu().numpy()).save(os.path.join(args.out, "ego_view.png"))
+        print("ego view %d x %d, point size %d, background %s; wrote %s/ego_view.png"
+              % (camera.height, camera.width, option.point_size, option.background_color, args.out))
     counts = torch.bincount(out["pred"], minlength=len(colors)).cpu().tolist()
     drawn = int((out["pix"][:, 0] != V.INT32_MIN).sum())
     print("scan of %d points resampled to %d; %d with a pixel, %d classes predicted; error flag %d; wrote %s/semantic.png and top_view.png"
