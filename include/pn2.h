@@ -500,6 +500,25 @@ int pn2_log_softmax_bwd(const float *grad_out, int ldg, const float *out, int ld
 int pn2_adam_step(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, double lr, double beta1,
                   double beta2, double eps, double weight_decay, int64_t step, const float *lr_dev, int64_t *step_dev,
                   int zero_grad, pn2_stream_t stream);
+/* pn2_sgd_step (added within ABI 15: purely additive, no version change) replaces torch.optim.SGD(params, lr, momentum,
+ * dampening, weight_decay, nesterov, maximize=) -- the other branch of the reference's --optimizer switch (semseg.py:103-104,
+ * partseg.py:113, clf.py:72, pcdseg.py:130-131: lr=0.01, momentum=0.9) -- with the conventions of pn2_adam_step: one launch over
+ * one flat fp32 buffer, `step` = t (>= 1) of this call, step_dev = device int64[2] {steps taken, ticket} read and advanced by the
+ * launch itself, lr_dev = the learning rate in device memory, zero_grad != 0 clears grad in the same pass.
+ * The arithmetic is torch/optim/sgd.py::_single_tensor_sgd's, bit for bit: the scalars are doubles rounded to fp32 once
+ * (wd = (float)weight_decay, om = (float)(1.0 - dampening), mu = (float)momentum, nl = (float)(-lr), or -(*lr_dev)), every
+ * add(alpha=) is ONE rounding (fmaf), the mul_ of the buffer is rounded on its own:
+ *     g = maximize ? -grad : grad;  if (weight_decay != 0) g = fmaf(wd, p, g);
+ *     if (momentum != 0) { buf = t == 1 ? g : fmaf(om, g, buf * mu);  g = nesterov ? fmaf(mu, buf, g) : buf; }
+ *     p = fmaf(nl, g, p)
+ * (no dampening on the first step: torch clones the gradient into the new buffer).  momentum_buf is a flat twin of param, read
+ * and written only when momentum != 0 (NULL, or ignored, otherwise: that path moves 12 B/element, 16 with zero_grad, against
+ * 24 with a buffer and zero_grad).  float4 accesses where all pointers used are 16-byte aligned, a scalar kernel otherwise.
+ * Returns PN2_EINVAL without a launch where torch.optim.SGD.__init__ raises (lr, momentum or weight_decay negative; nesterov
+ * with momentum <= 0 or dampening != 0), for momentum != 0 without a buffer, and for n <= 0. */
+int pn2_sgd_step(float *param, float *grad, float *momentum_buf, int64_t n, double lr, double momentum, double dampening,
+                 double weight_decay, int nesterov, int maximize, int64_t step, const float *lr_dev, int64_t *step_dev,
+                 int zero_grad, pn2_stream_t stream);
 /* pn2_prepare_clouds replaces SemKITTI_Loader.__getitem__ (data_utils/SemKITTI_Loader.py:93-113) for a batch:
  * pcd_normalize (:23-30: x/70, y/70, z/3, (i-0.5)*2, clip to [-1,1]), pcd_jitter (:17-21: += noise) and
  * `pcd[choice]`, `label[choice]` (:110-113).

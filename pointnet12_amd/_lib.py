@@ -80,6 +80,7 @@ SIGNATURES = {
     "pn2_log_softmax_fwd": (_i, [_vp, _i, _i64, _i, _vp, _i, _vp]),
     "pn2_log_softmax_bwd": (_i, [_vp, _i, _vp, _i, _i64, _i, _vp, _i, _vp]),
     "pn2_adam_step": (_i, [_vp, _vp, _vp, _vp, _i64, _d, _d, _d, _d, _d, _i64, _vp, _vp, _i, _vp]),
+    "pn2_sgd_step": (_i, [_vp, _vp, _vp, _i64, _d, _d, _d, _d, _i, _i, _i64, _vp, _vp, _i, _vp]),
     "pn2_prepare_clouds": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "pn2_prepare_shapes": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "pn2_point_transform": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _vp]),

@@ -3,17 +3,35 @@
 //   * pn2_adam_step       torch.optim.Adam(lr, betas, eps, weight_decay) as semseg.py:106-111 / pcdseg.py:133-138
 //                         build it, over ONE flat fp32 parameter buffer: 28 B/element, a single launch instead of
 //                         ~10 foreach launches over 150 tensors.
+//   * pn2_sgd_step        torch.optim.SGD(lr, momentum, ...) -- the other branch of the reference's --optimizer switch
+//                         (semseg.py:103-104, partseg.py:113, clf.py:72, pcdseg.py:130-131) -- over the same flat buffers:
+//                         24 B/element with a momentum buffer and the fused zero-grad, bit for bit ATen's arithmetic.
 //   * pn2_prepare_clouds  pcd_normalize + pcd_jitter + the with-replacement resampling of
 //                         data_utils/SemKITTI_Loader.py:17-30,93-113, as one gather over the raw [M,4] scans.
 //   * pn2_prepare_shapes  rotate_point_cloud + jitter_point_cloud (data_utils/augmentation.py:25-45,70-82) + the resampling
 //                         of ShapeNetDataLoader.py:116-126, over raw [M,C] rows (ShapeNet-part, ModelNet, S3DIS blocks).
 // All are HBM-bound streaming kernels: nothing staged.  The file is built with -ffp-contract=off: the fp64 forms of
-// pn2_prepare_shapes are numpy's, un-fused.
+// pn2_prepare_shapes are numpy's, un-fused, and where ATen rounds a*b + c once (pn2_sgd_step) the code says fmaf.
 #include "pn2_common.h"
 
 namespace {
 
 constexpr int kThreads = 256;
+
+// The epilogue of a step kernel whose step counter lives in device memory (step_dev: int64[2] {steps taken, ticket}).
+// Every workgroup read the counter before it got here; the last one to finish publishes t and re-arms the ticket, so the
+// launch can be replayed from a hipGraph without host-side arguments changing.  Called by ALL threads of every workgroup.
+__device__ __forceinline__ void publish_step(int64_t *step_dev, int64_t t) {
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long *ticket = reinterpret_cast<unsigned long long *>(step_dev + 1);
+        const unsigned long long done = __hip_atomic_fetch_add(ticket, 1ull, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        if (done == gridDim.x - 1) {
+            __hip_atomic_store(ticket, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(step_dev, t, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
 
 struct AdamScalars {
     float step_size, bc2_sqrt, beta1_w, beta2, one_m_beta2, eps, wd;
@@ -93,20 +111,86 @@ __global__ __launch_bounds__(kThreads) void adam_kernel(float *__restrict__ para
             if (zero_grad) grad[i] = 0.f;
         }
     }
-    if (step_dev) {
-        // Every workgroup read the counter before it got here; the last one to finish publishes t and re-arms
-        // the ticket, so the launch can be replayed from a hipGraph without host-side arguments changing.
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            unsigned long long *ticket = reinterpret_cast<unsigned long long *>(step_dev + 1);
-            const unsigned long long done =
-                __hip_atomic_fetch_add(ticket, 1ull, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-            if (done == gridDim.x - 1) {
-                __hip_atomic_store(ticket, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(step_dev, t_sh, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-            }
+    if (step_dev) publish_step(step_dev, t_sh);
+}
+
+// ---- SGD.  The arithmetic of torch/optim/sgd.py::_single_tensor_sgd: its scalars are Python doubles that ATen rounds to
+// fp32 once, every add(alpha=) is ONE rounding of a + alpha*b (fmaf), the mul_ of the buffer is rounded on its own.
+struct SgdScalars {
+    float wd, one_m_damp, mu, neg_lr;
+    int decay, first, nesterov, maximize;
+};
+
+template <bool kMomentum>
+__device__ __forceinline__ void sgd_elem(float &p, float g, float &buf, const SgdScalars &s) {
+    if (s.maximize) g = -g;
+    if (s.decay) g = fmaf(s.wd, p, g);                          // grad.add(param, alpha=weight_decay)
+    if constexpr (kMomentum) {
+        // buf = clone(grad) on the first step (dampening NOT applied), else buf.mul_(momentum).add_(grad, alpha=1-dampening)
+        buf = s.first ? g : fmaf(s.one_m_damp, g, buf * s.mu);
+        g = s.nesterov ? fmaf(s.mu, buf, g) : buf;               // grad.add(buf, alpha=momentum)
+    }
+    p = fmaf(s.neg_lr, g, p);                                    // param.add_(grad, alpha=-lr)
+}
+
+// kMomentum == false reads p, g and writes p: momentum_buf is never dereferenced (it is NULL).
+template <bool kMomentum, bool kVec>
+__global__ __launch_bounds__(kThreads) void sgd_kernel(float *__restrict__ param, float *__restrict__ grad,
+                                                       float *__restrict__ momentum_buf, int64_t n, double lr, double momentum,
+                                                       double dampening, double wd, int nesterov, int maximize, int64_t step,
+                                                       const float *__restrict__ lr_dev, int64_t *__restrict__ step_dev,
+                                                       int zero_grad) {
+    __shared__ SgdScalars sh;
+    __shared__ int64_t t_sh;
+    if (threadIdx.x == 0) {
+        const int64_t t = step_dev ? __hip_atomic_load(step_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1 : step;
+        SgdScalars s;
+        s.wd = (float)wd;
+        s.one_m_damp = (float)(1.0 - dampening);
+        s.mu = (float)momentum;
+        s.neg_lr = lr_dev ? -*lr_dev : (float)(-lr);
+        s.decay = wd != 0.0;
+        s.first = t == 1;
+        s.nesterov = nesterov;
+        s.maximize = maximize;
+        sh = s;
+        t_sh = t;
+    }
+    __syncthreads();
+    const SgdScalars s = sh;
+    const int64_t stride = (int64_t)gridDim.x * kThreads;
+    float none = 0.f;                                           // stands in for the buffer element when there is no buffer
+    if constexpr (kVec) {
+        const int64_t n4 = n >> 2;
+        for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n4; i += stride) {
+            float4 p = reinterpret_cast<float4 *>(param)[i];
+            const float4 g = reinterpret_cast<const float4 *>(grad)[i];
+            float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (kMomentum) b = reinterpret_cast<float4 *>(momentum_buf)[i];
+            sgd_elem<kMomentum>(p.x, g.x, b.x, s);
+            sgd_elem<kMomentum>(p.y, g.y, b.y, s);
+            sgd_elem<kMomentum>(p.z, g.z, b.z, s);
+            sgd_elem<kMomentum>(p.w, g.w, b.w, s);
+            reinterpret_cast<float4 *>(param)[i] = p;
+            if constexpr (kMomentum) reinterpret_cast<float4 *>(momentum_buf)[i] = b;
+            if (zero_grad) reinterpret_cast<float4 *>(grad)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
+    // the scalar tail of the vector form, or (unaligned pointers) everything
+    const int64_t lo = kVec ? (n >> 2) << 2 : 0;
+    for (int64_t i = lo + (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) {
+        float p = param[i];
+        if constexpr (kMomentum) {
+            float b = momentum_buf[i];
+            sgd_elem<true>(p, grad[i], b, s);
+            momentum_buf[i] = b;
+        } else {
+            sgd_elem<false>(p, grad[i], none, s);
+        }
+        param[i] = p;
+        if (zero_grad) grad[i] = 0.f;
+    }
+    if (step_dev) publish_step(step_dev, t_sh);
 }
 
 // One thread per output point: row = choice[b, n] of cloud b's raw scan, normalised as pcd_normalize
@@ -207,6 +291,32 @@ int pn2_adam_step(float *param, float *grad, float *exp_avg, float *exp_avg_sq, 
     else
         hipLaunchKernelGGL(adam_kernel<false>, dim3((unsigned)blocks), dim3(kThreads), 0, pn2_s(stream), param, grad, exp_avg,
                            exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, lr_dev, step_dev, zero_grad);
+    return pn2_launch_status();
+}
+
+int pn2_sgd_step(float *param, float *grad, float *momentum_buf, int64_t n, double lr, double momentum, double dampening,
+                 double weight_decay, int nesterov, int maximize, int64_t step, const float *lr_dev, int64_t *step_dev,
+                 int zero_grad, pn2_stream_t stream) {
+    PN2_CHECK_ARG(param && grad && n > 0);
+    PN2_CHECK_ARG(step_dev || step >= 1);
+    // refused exactly where torch.optim.SGD.__init__ raises
+    PN2_CHECK_ARG(!(lr < 0.0) && !(momentum < 0.0) && !(weight_decay < 0.0));
+    PN2_CHECK_ARG(!(nesterov && (momentum <= 0.0 || dampening != 0.0)));
+    const bool mom = momentum != 0.0;
+    PN2_CHECK_ARG(!mom || momentum_buf);
+    if (!mom) momentum_buf = nullptr;                           // never touched without momentum
+    const bool vec = aligned16(param) && aligned16(grad) && aligned16(momentum_buf);
+    int64_t blocks = pn2_cdiv(vec ? pn2_cdiv(n, 4) : n, kThreads);
+    if (blocks > 8192) blocks = 8192;
+#define PN2_SGD_LAUNCH(M, V)                                                                                                  \
+    hipLaunchKernelGGL((sgd_kernel<M, V>), dim3((unsigned)blocks), dim3(kThreads), 0, pn2_s(stream), param, grad, momentum_buf, \
+                       n, lr, momentum, dampening, weight_decay, nesterov != 0, maximize != 0, step, lr_dev, step_dev, zero_grad)
+    if (mom) {
+        if (vec) PN2_SGD_LAUNCH(true, true); else PN2_SGD_LAUNCH(true, false);
+    } else {
+        if (vec) PN2_SGD_LAUNCH(false, true); else PN2_SGD_LAUNCH(false, false);
+    }
+#undef PN2_SGD_LAUNCH
     return pn2_launch_status();
 }
 

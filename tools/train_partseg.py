@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """The reference's part-segmentation loop (partseg.py) on synthetic shapes, every step of it on the HIP library: resident
 ``[M, 6]`` shapes (``shapes.ShapeStore``) -> pn2_prepare_shapes (rotate, jitter, resample; draws on the device) ->
-PointNet2PartSegMsg_one_hot(50) forward -> nll_loss -> backward -> pn2_adam_step.
+PointNet2PartSegMsg_one_hot(50) forward -> nll_loss -> backward -> pn2_adam_step (``--optimizer SGD``: partseg.py:113's
+SGD(lr=0.01, momentum=0.9) -> pn2_sgd_step).
 
 The part label of a point is a function of its category and its height inside the normalised shape, so the loss must fall; the
 script prints the loss curve and the all-inclusive time per step (batch preparation + step + optimiser).
 
-    python tools/train_partseg.py --steps 20 --batch 16 --npoints 2048
+    python tools/train_partseg.py --steps 20 --batch 16 --npoints 2048 [--optimizer SGD]
 """
 import argparse
 import json
@@ -51,7 +52,8 @@ def main():
     ap.add_argument("--npoints", type=int, default=2048)
     ap.add_argument("--shapes", type=int, default=64)
     ap.add_argument("--raw-points", type=int, default=2700)
-    ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--lr", type=float, default=1e-3, help="Adam's learning rate (SGD takes the reference's 0.01)")
+    ap.add_argument("--optimizer", choices=("Adam", "SGD"), default="Adam")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -59,8 +61,11 @@ def main():
     net = pointnet2.PointNet2PartSegMsg_one_hot(PARTS).to(dev)
     net.train()
     bucket = parallel.FlatGradBucket(net, direct=True)
-    opt = optim.Adam(net.parameters(), lr=args.lr, betas=(0.9, 0.999), eps=1e-08, weight_decay=1e-4, bucket=bucket,
-                     fused_zero_grad=True)
+    if args.optimizer == "SGD":
+        opt = optim.SGD(net.parameters(), lr=0.01, momentum=0.9, bucket=bucket, fused_zero_grad=True)
+    else:
+        opt = optim.Adam(net.parameters(), lr=args.lr, betas=(0.9, 0.999), eps=1e-08, weight_decay=1e-4, bucket=bucket,
+                         fused_zero_grad=True)
     gen = torch.Generator(device=dev)
     gen.manual_seed(1)
     pick = np.random.default_rng(0)
@@ -73,7 +78,7 @@ def main():
         pts, seg, cls = shapes.prepare_shapes(store, pick.integers(0, len(store), args.batch), args.npoints, rotate=True,
                                               jitter=True, rng=gen, out=out)
         one_hot = torch.nn.functional.one_hot(cls, CATEGORIES).float()                 # to_categorical of partseg.py
-        opt.zero_grad()                                            # free after the first step (fused into Adam)
+        opt.zero_grad()                                            # free after the first step (fused into the optimiser's)
         lp = net(pts[..., 0:3].transpose(2, 1), pts[..., 3:6].transpose(2, 1), one_hot)
         loss = nll_loss(lp.reshape(-1, PARTS), seg.reshape(-1))
         loss.backward()
@@ -83,7 +88,7 @@ def main():
             curve.append((it, round(float(loss.detach()), 4)))     # the float() is this loop's only sync
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    print(json.dumps({"net": "partseg_msg_one_hot", "steps": args.steps, "batch": args.batch, "npoints": args.npoints,
+    print(json.dumps({"net": "partseg_msg_one_hot", **({"optimizer": "SGD"} if args.optimizer == "SGD" else {}), "steps": args.steps, "batch": args.batch, "npoints": args.npoints,
                       "ms_per_step_all_in": round(dt / args.steps * 1e3, 3), "loss_first": curve[0][1], "loss_last": curve[-1][1],
                       "curve": curve}))
 

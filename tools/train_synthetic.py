@@ -2,11 +2,12 @@
 """The reference's training loop (semseg.py:120-150) on synthetic scans, every step of it on the HIP library:
 resident raw scans -> pn2_prepare_clouds -> PointNet2SemSeg forward -> nll_loss -> backward into the flat gradient
 bucket -> (gradient all-reduce when launched under torch.distributed.run) -> pn2_adam_step, StepLR as semseg.py:113.
+``--optimizer SGD`` takes the other branch of semseg.py:103-104 (SGD, lr=0.01, momentum=0.9) -> pn2_sgd_step.
 
 Labels are a function of the normalised height and intensity, so the loss must fall; the script prints the loss
 curve and the all-inclusive throughput (loader + step + optimiser), which bench.py's metric deliberately excludes.
 
-    python tools/train_synthetic.py --steps 200 --batch 16 --npoints 4096 [--msg] [--graph]
+    python tools/train_synthetic.py --steps 200 --batch 16 --npoints 4096 [--msg] [--graph] [--optimizer SGD]
 """
 import argparse
 import json
@@ -45,7 +46,8 @@ def main():
     ap.add_argument("--raw-points", type=int, default=20000)
     ap.add_argument("--msg", action="store_true")
     ap.add_argument("--graph", action="store_true", help="capture zero-grad + forward + loss + backward + Adam")
-    ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--lr", type=float, default=1e-3, help="Adam's learning rate (SGD takes the reference's 0.01)")
+    ap.add_argument("--optimizer", choices=("Adam", "SGD"), default="Adam")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -54,8 +56,11 @@ def main():
     net = (pointnet2.PointNet2SemSegMsg if args.msg else pointnet2.PointNet2SemSeg)(CLASSES, feature_dims=1).to(dev)
     net.train()
     bucket = parallel.FlatGradBucket(net, direct=True)
-    opt = optim.Adam(net.parameters(), lr=args.lr, betas=(0.9, 0.999), eps=1e-08, weight_decay=1e-4, bucket=bucket,
-                     device_step=args.graph, fused_zero_grad=True)
+    if args.optimizer == "SGD":
+        opt = optim.SGD(net.parameters(), lr=0.01, momentum=0.9, bucket=bucket, device_step=args.graph, fused_zero_grad=True)
+    else:
+        opt = optim.Adam(net.parameters(), lr=args.lr, betas=(0.9, 0.999), eps=1e-08, weight_decay=1e-4, bucket=bucket,
+                         device_step=args.graph, fused_zero_grad=True)
     sched = torch.optim.lr_scheduler.StepLR(opt, step_size=max(args.steps // 3, 1), gamma=0.5)
     gen = torch.Generator(device=dev)
     gen.manual_seed(1)
@@ -64,7 +69,7 @@ def main():
     lab = torch.empty(args.batch, args.npoints, device=dev, dtype=torch.int64)
 
     def compute():
-        opt.zero_grad()                                            # free after the first step (fused into Adam)
+        opt.zero_grad()                                            # free after the first step (fused into the optimiser's)
         loss = nll_loss(net(pts.transpose(2, 1)).reshape(-1, CLASSES), lab.reshape(-1))
         loss.backward()
         bucket.all_reduce()
@@ -90,7 +95,8 @@ def main():
             opt.sync_lr()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    print(json.dumps({"net": "msg" if args.msg else "ssg", "graph": args.graph, "steps": args.steps,
+    print(json.dumps({"net": "msg" if args.msg else "ssg", "graph": args.graph,
+                      **({"optimizer": "SGD"} if args.optimizer == "SGD" else {}), "steps": args.steps,
                       "batch": args.batch, "npoints": args.npoints, "ms_per_step_all_in": round(dt / args.steps * 1e3, 3),
                       "points_per_s_all_in": round(args.batch * args.npoints * args.steps / dt),
                       "loss_first": curve[0][1], "loss_last": curve[-1][1], "curve": curve}))
