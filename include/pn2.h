@@ -462,8 +462,8 @@ int pn2_group_affine_bwd_seg(const float *dZ, int ldz, const float *Y, int ldy, 
                              const pn2_bn_coef_lazy *coef_lazy, pn2_stream_t stream);
 
 /* ---- the loss either side of the path ---------------------------------------
- * Replaces F.nll_loss(pred, target) of semseg.py:143 (weight == NULL) and the class-weighted form of
- * pcdseg.py:179, reduction "mean":
+ * Replaces F.nll_loss(pred, target) of semseg.py:143 (weight == NULL; weight != NULL: its class-weighted form), reduction
+ * "mean" (the criterion of pcdseg.py:178-179 is a cross entropy: pn2_cross_entropy_* below):
  *     loss = - sum_r w[t_r] * logp[r, t_r] / sum_r w[t_r]     over rows with t_r != ignore_index.
  * logp [R, ld >= C] log-probabilities, target int64[R].  A target outside [0, C) that is not ignore_index
  * turns the loss NaN (ATen raises a device assert).  workspace: pn2_nll_loss_workspace_bytes(R) bytes,
@@ -477,6 +477,35 @@ int pn2_nll_loss_fwd(const float *logp, int ld, const int64_t *target, const flo
  * every element of dlogp [R, ld] is written. */
 int pn2_nll_loss_bwd(const int64_t *target, const float *weight, int64_t R, int C, int64_t ignore_index,
                      const float *grad_loss, const float *denom, float *dlogp, int ld, pn2_stream_t stream);
+/* pn2_cross_entropy_* (added within ABI 15: purely additive, no version change) replace the criterion of the SemanticKITTI loop,
+ * pcdseg.py:178-179 `nn.CrossEntropyLoss()(logits.transpose(2, 1), target)`, with the semantics of
+ * torch.nn.functional.cross_entropy(input, target, weight, ignore_index=, reduction=, label_smoothing=) for class-index targets:
+ *     l_r = (1 - eps) * w[t_r] * (-log p[t_r]) + eps / C * sum_c w[c] * (-log p[c]),   p = softmax(x_r),   0 on ignored rows;
+ *     reduction 0 "none": loss[r] = l_r;  1 "mean": *loss = sum_r l_r / sum_r w[t_r] (rows not ignored);  2 "sum": *loss = sum_r l_r.
+ * x is read in place, C <= 64 classes, R rows, in one of two layouts:
+ *     inner == 0: row-major, element (r, c) at x[r * ld + c], any pitch ld >= C (rows are read as float4 quads when ld % 4 == 0 and
+ *                 x is 16-byte aligned, as dwords otherwise; nothing past column C of a row is touched);
+ *     inner  > 0: class-strided [R / inner, C, inner], element (b, c, n) at x[b * C * inner + c * inner + n], row r = b * inner + n
+ *                 (ld is ignored).
+ * The transposed view of a contiguous [B, N, C] tensor that pcdseg.py passes IS the row-major case (ld = C).
+ * weight: float[C] or NULL.  A target outside [0, C) that is not ignore_index never indexes weight or the row: the reduced loss
+ * and that row's "none" entry turn NaN, and its gradient row is zero (the contract of pn2_nll_loss_*).
+ * logsum: float[R], log sum_c exp(x[r, c] - max_c x[r, c]), kept for the backward (the row's log-sum-exp RELATIVE to its maximum:
+ * max + log sum would round at the magnitude of the logits).  workspace (reductions 1, 2; NULL otherwise):
+ * pn2_cross_entropy_workspace_bytes(R) bytes, zeroed ONCE by the caller; the kernel leaves it reusable; do not share it between
+ * concurrent launches.  *denom = sum of the weights of the rows that count (reductions 1, 2).  fp64 partial sums combined in a
+ * fixed order: the result does not depend on scheduling. */
+int64_t pn2_cross_entropy_workspace_bytes(int64_t R);
+int pn2_cross_entropy_fwd(const float *x, int ld, int64_t inner, const int64_t *target, const float *weight, int64_t R, int C,
+                          int64_t ignore_index, double label_smoothing, int reduction, void *workspace, float *logsum, float *loss,
+                          float *denom, pn2_stream_t stream);
+/* One launch: dx[r, c] = g_r * [(1 - eps) * w[t_r] * (p_c - [c == t_r]) + eps / C * (p_c * sum_k w[k] - w[c])] in the layout of x
+ * (same ld / inner), p_c recomputed from x and logsum.  g_r = *grad_out / *denom (mean), *grad_out (sum), grad_out[r] (none), all
+ * read on the device.  Ignored rows and rows with an out-of-range target are written as zeros; bytes outside the C logical
+ * columns of a padded row are never written. */
+int pn2_cross_entropy_bwd(const float *x, int ld, int64_t inner, const int64_t *target, const float *weight, const float *logsum,
+                          int64_t R, int C, int64_t ignore_index, double label_smoothing, int reduction, const float *grad_out,
+                          const float *denom, float *dx, pn2_stream_t stream);
 /* F.log_softmax(x, dim=-1) of the segmentation heads (model/pointnet2.py:175; :46, :103, :138) on rows whose C <= 64 logits
  * are the leading columns of a padded row (pitch ldx, a multiple of 4: the output of pn2_conv1x1_fwd as it stands -- no
  * slice copy): out[r, c] = x[r, c] - max_c x - log sum_c exp(x - max) for c < C, pitch ldo >= C. */

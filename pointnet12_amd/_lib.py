@@ -77,6 +77,9 @@ SIGNATURES = {
     "pn2_nll_loss_workspace_bytes": (_i64, [_i64]),
     "pn2_nll_loss_fwd": (_i, [_vp, _i, _vp, _vp, _i64, _i, _i64, _vp, _vp, _vp, _vp]),
     "pn2_nll_loss_bwd": (_i, [_vp, _vp, _i64, _i, _i64, _vp, _vp, _vp, _i, _vp]),
+    "pn2_cross_entropy_workspace_bytes": (_i64, [_i64]),
+    "pn2_cross_entropy_fwd": (_i, [_vp, _i, _i64, _vp, _vp, _i64, _i, _i64, _d, _i, _vp, _vp, _vp, _vp, _vp]),
+    "pn2_cross_entropy_bwd": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _i64, _i, _i64, _d, _i, _vp, _vp, _vp, _vp]),
     "pn2_log_softmax_fwd": (_i, [_vp, _i, _i64, _i, _vp, _i, _vp]),
     "pn2_log_softmax_bwd": (_i, [_vp, _i, _vp, _i, _i64, _i, _vp, _i, _vp]),
     "pn2_adam_step": (_i, [_vp, _vp, _vp, _vp, _i64, _d, _d, _d, _d, _d, _i64, _vp, _vp, _i, _vp]),
@@ -165,7 +168,7 @@ class _Timed:
     def __getattr__(self, name):
         fn = getattr(_raw, name)
         if not name.startswith("pn2_") or name in ("pn2_version", "pn2_error_string", "pn2_set_option", "pn2_get_option", "pn2_option_name", "pn2_fps_workspace_bytes",
-                                                   "pn2_nll_loss_workspace_bytes", "pn2_res_supported", "pn2_bwd_res_supported", "pn2_conv1x1_wgrad_workspace_bytes",
+                                                   "pn2_nll_loss_workspace_bytes", "pn2_cross_entropy_workspace_bytes", "pn2_res_supported", "pn2_bwd_res_supported", "pn2_conv1x1_wgrad_workspace_bytes",
                                                    "pn2_conv1x1_wgrad_cf_scratch_bytes", "pn2_conv1x1_bwd_cf_supported", "pn2_conv1x1_bwd_first_supported", "pn2_conv1x1_bwd_cf_scratch_bytes", "pn2_last_kernel", "pn2_clear_last_kernel",
                                                    "pn2_ball_query_workspace_bytes", "pn2_point_transform_workspace_bytes",
                                                    "pn2_group_colsum_workspace_bytes", "pn2_chamfer_nn_workspace_bytes"):

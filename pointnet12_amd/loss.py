@@ -1,10 +1,15 @@
-"""The loss either side of the hot path, on the HIP library.
+"""The criteria either side of the hot path, on the HIP library.
 
 ``nll_loss(log_probs, target)`` is a drop-in for ``torch.nn.functional.nll_loss`` as the reference calls it:
-``F.nll_loss(pred, target)`` on ``[B*N, C]`` log-probabilities (semseg.py:143, mean over all points) and
-the class-weighted mean of pcdseg.py:179.  ATen's kernel for this reduction runs in a single workgroup
-(66 us forward + 37 us backward at 65 536 rows, fully exposed between the forward and the backward pass);
-``pn2_nll_loss_fwd`` spreads it over the chip with fp64 partials combined in a fixed order.
+``F.nll_loss(pred, target)`` on ``[B*N, C]`` log-probabilities (semseg.py:143, mean over all points), with an optional
+class weight.  ATen's kernel for this reduction runs in a single workgroup (66 us forward + 37 us backward at
+65 536 rows, fully exposed between the forward and the backward pass); ``pn2_nll_loss_fwd`` spreads it over the
+chip with fp64 partials combined in a fixed order.
+
+``cross_entropy`` / ``CrossEntropyLoss`` are ``torch.nn.functional.cross_entropy`` / ``nn.CrossEntropyLoss`` for
+class-index targets: the criterion of the SemanticKITTI loop, ``nn.CrossEntropyLoss()(logits.transpose(2, 1), target)``
+(pcdseg.py:178-179: no weight, the input is the model's ``[B, N, C]`` output seen through a class-dim-1 view).  One
+launch each way (``pn2_cross_entropy_fwd`` / ``_bwd``), the input read where it lies, 4 bytes per row kept for the backward.
 """
 import torch
 
@@ -62,3 +67,122 @@ def nll_loss(log_probs, target, weight=None, ignore_index=-100):
         if weight.numel() != log_probs.shape[1]:
             raise ValueError("nll_loss: weight must have one entry per class")
     return _NllLoss.apply(log_probs.contiguous(), target.contiguous(), weight, int(ignore_index))
+
+
+_REDUCTIONS = {"none": 0, "mean": 1, "sum": 2}
+
+
+def _ce_layout(x):
+    """How ``pn2_cross_entropy_*`` reads ``x`` ([R, C] or [B, C, d1, ...]) in place -> (R, ld, inner), or None.
+
+    Row-major: with the class dim moved last, the classes are adjacent and the leading dims collapse into rows of one pitch
+    ld >= C (a contiguous [R, C], a column slice of a padded buffer, the transposed view of a contiguous [B, N, C]).
+    Class-strided: contiguous [B, C, N] (a [R, C] whose transpose is contiguous is B = 1)."""
+    C = x.shape[1]
+    y = x.movedim(1, -1)
+    lead = [(n, st) for n, st in zip(y.shape[:-1], y.stride()[:-1]) if n != 1]
+    R = 1
+    for n, _ in lead:
+        R *= n
+    if C == 1 or y.stride(-1) == 1:
+        ld = lead[-1][1] if lead else C
+        if ld >= C and all(a[1] == b[0] * b[1] for a, b in zip(lead[:-1], lead[1:])) and ld < 2 ** 31:
+            return R, ld, 0
+    if x.dim() == 2:
+        x = x.t().unsqueeze(0)
+    if x.is_contiguous():
+        return R, 0, R // x.shape[0]
+    return None
+
+
+class _CrossEntropy(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, target, weight, ignore_index, reduction, label_smoothing, layout):
+        lib, st = _lib.load(), _lib.stream()
+        R, ld, inner = layout
+        C = x.shape[1]
+        lse = torch.empty(R, device=x.device, dtype=torch.float32)       # log sum exp(x - max x) per row
+        if reduction == 0:
+            out, res, ws = torch.empty(target.shape, device=x.device, dtype=torch.float32), None, None
+        else:
+            from .pointnet_util import _zeros_small                       # the zero arena: no fill launch of its own
+            ws = _zeros_small(int(lib.pn2_cross_entropy_workspace_bytes(R)), x.device)
+            res = torch.empty(2, device=x.device, dtype=torch.float32)    # loss, sum of weights
+            out = res[0]
+        _lib.check(lib.pn2_cross_entropy_fwd(_p(x), ld, inner, _p(target), _p(weight), R, C, ignore_index, label_smoothing,
+                                             reduction, _p(ws), _p(lse), out.data_ptr(), None if res is None else res.data_ptr() + 4,
+                                             st), "pn2_cross_entropy_fwd")
+        ctx.save_for_backward(x, target, weight, lse, res)
+        ctx.meta = (R, C, ld, inner, ignore_index, reduction, label_smoothing)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        lib, st = _lib.load(), _lib.stream()
+        x, target, weight, lse, res = ctx.saved_tensors
+        R, C, ld, inner, ignore_index, reduction, label_smoothing = ctx.meta
+        grad = grad.contiguous().float()                                  # a scalar, or one value per row ("none")
+        dx = torch.empty_strided(x.shape, x.stride(), device=x.device, dtype=torch.float32)      # the input's own layout
+        _lib.check(lib.pn2_cross_entropy_bwd(_p(x), ld, inner, _p(target), _p(weight), _p(lse), R, C, ignore_index,
+                                             label_smoothing, reduction, _p(grad), None if res is None else res.data_ptr() + 4,
+                                             _p(dx), st), "pn2_cross_entropy_bwd")
+        return dx, None, None, None, None, None, None
+
+
+def cross_entropy(input, target, weight=None, ignore_index=-100, reduction="mean", label_smoothing=0.0):
+    """``F.cross_entropy(input, target, weight, ignore_index=, reduction=, label_smoothing=)`` for class-index targets.
+
+    input float32 on the GPU, ``[R, C]`` or ``[B, C, d1, ...]`` (classes in dim 1, C <= 64), read in place: row-major at any
+    row pitch, the transposed view of a contiguous ``[B, N, C]`` tensor (pcdseg.py:178) or contiguous ``[B, C, N]``; any
+    other layout is refused (no hidden ``.contiguous()``).  target int64 ``[R]`` / ``[B, d1, ...]``.  The gradient comes back
+    with the input's strides.  No host synchronisation: forward and backward capture into a graph -- provided target and
+    weight already are int64 / float32 tensors on the input's device; otherwise they are converted and copied there on every
+    call (as ``nll_loss`` does), and a host-to-device copy does not belong inside a capture."""
+    if reduction not in _REDUCTIONS:
+        raise ValueError("cross_entropy: %r is not a valid value for reduction" % (reduction,))
+    if not 0.0 <= float(label_smoothing) <= 1.0:
+        raise ValueError("cross_entropy: label_smoothing must be between 0.0 and 1.0, got %r" % (label_smoothing,))
+    if input.dtype != torch.float32:
+        raise TypeError("cross_entropy: float32 logits expected, got %s" % input.dtype)
+    if target.is_floating_point():
+        raise NotImplementedError("cross_entropy: class-probability targets are not supported, class indices only")
+    if input.dim() < 2:
+        raise ValueError("cross_entropy: input must be [R, C] or [B, C, d1, ...], got %s" % (tuple(input.shape),))
+    if tuple(target.shape) != tuple(input.shape[:1] + input.shape[2:]):
+        raise ValueError("cross_entropy: input %s wants a target of shape %s, got %s"
+                         % (tuple(input.shape), tuple(input.shape[:1] + input.shape[2:]), tuple(target.shape)))
+    C = input.shape[1]
+    if weight is not None and weight.numel() != C:
+        raise ValueError("cross_entropy: weight must have one entry per class")
+    if C > 64:
+        raise _lib.Pn2Error("cross_entropy: %d classes, the kernels hold a row of at most 64" % C)
+    if input.numel() == 0:
+        raise ValueError("cross_entropy: empty input")
+    layout = _ce_layout(input)
+    if layout is None:
+        raise _lib.Pn2Error("cross_entropy: input of shape %s and strides %s is neither row-major rows of classes nor "
+                            "contiguous [B, C, N]; lay it out as one of the two" % (tuple(input.shape), input.stride()))
+    if not input.is_cuda:
+        raise _lib.Pn2Error("cross_entropy: input must be a GPU tensor (the HIP library is the only implementation)")
+    target = target.to(device=input.device, dtype=torch.int64).contiguous()
+    if weight is not None:
+        weight = weight.to(device=input.device, dtype=torch.float32).contiguous()
+    return _CrossEntropy.apply(input, target, weight, int(ignore_index), _REDUCTIONS[reduction], float(label_smoothing), layout)
+
+
+class CrossEntropyLoss(torch.nn.Module):
+    """``torch.nn.CrossEntropyLoss`` on :func:`cross_entropy` (``size_average`` / ``reduce`` are torch's deprecated spellings
+    of ``reduction`` and are mapped the way torch maps them).  ``weight`` is a buffer: move the module to the device
+    (``.to(device)``) like any other, or every call copies the weight there."""
+
+    def __init__(self, weight=None, size_average=None, ignore_index=-100, reduce=None, reduction="mean", label_smoothing=0.0):
+        super().__init__()
+        if size_average is not None or reduce is not None:
+            reduction = torch.nn._reduction.legacy_get_string(size_average, reduce)
+        self.register_buffer("weight", weight)
+        self.ignore_index = ignore_index
+        self.reduction = reduction
+        self.label_smoothing = label_smoothing
+
+    def forward(self, input, target):
+        return cross_entropy(input, target, self.weight, self.ignore_index, self.reduction, self.label_smoothing)
