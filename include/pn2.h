@@ -752,6 +752,52 @@ int pn2_depth_splat(const float *xyz, int ldx, int64_t N, const double *extrinsi
 /* owner (uint32 [H * W], may be NULL) = the visible point's index + 1, 0 where the pixel is empty: the format pn2_splat_resolve
  * colours from.  depth (float [H * W], may be NULL) = that point's float32 depth, +inf where empty. */
 int pn2_depth_resolve(const uint64_t *zkey, int H, int W, uint32_t *owner, float *depth, pn2_stream_t stream);
+/* pn2_scan_filter (added within ABI 15: purely additive, no version change) replaces Semantic_KITTI_Utils.get
+ * (data_utils/kitti_utils.py:183-227: the class map :204-213, the drop of class 0 and the shift :215-219, the `inview` subset
+ * :221-225) with points_basic_filter (:259-280: hv_in_range :237-249, box_in_range :251-257) and the boolean-index compaction,
+ * for a batch of B raw scans that lie back to back in device memory.  Three plain launches on the caller's stream; no host
+ * synchronisation, no allocation, no workgroup waits on another, no atomic decides a position.
+ *   raw        [rows, 4] fp32, the .bin rows (16-byte aligned); scan b is rows [row_begin[b], row_begin[b] + row_count[b])
+ *              (int64[B] each, DEVICE memory: the convention of pn2_prepare_clouds).
+ *   raw_label  uint32[rows], the .label words, or NULL: an unlabelled scan, no class map and no class drop.
+ *   max_rows   host upper bound of every row_count[b], 0 <= max_rows < 2^31; it sizes the grid and the workspace only.  Tiles of
+ *              PN2_SCAN_TILE rows that start at or beyond the device-side row_count[b] do nothing, so a captured launch stays
+ *              valid when the count changes.  A negative row_count counts as 0.
+ *   lut        int32[lut_len] (device): raw class -> training class, -1 = not in the map (unused when raw_label is NULL).
+ *   fov        host float[4] t0, t1, t2, t3, or NULL: no angular test (subset 'all').
+ *   box        host float[8]: lower, upper bound of x, y, z, d; or NULL: no box test (what `get` does for subset 'all').
+ *   out_begin  int64[B] (device): where scan b's kept rows start in the outputs; may equal row_begin.  Outputs must not alias
+ *              inputs, and every output must hold out_begin[b] + (the kept count of scan b) rows for every b.
+ * THE RULE, per row (x, y, z, intensity) with label word w:
+ *   sem = w & 0xFFFF;  c = sem < lut_len ? lut[sem] : -1;  kept only if c > 0; the output class is c - 1.  (c < 0: the reference
+ *   raises KeyError; here the row is dropped and PN2_SCAN_ERR_CLASS is set.)
+ *   d = sqrtf((x*x + y*y) + z*z): fp32, every operation rounded on its own (no fused multiply-add), correctly rounded square
+ *   root -- numpy's np.sqrt(x**2 + y**2 + z**2).
+ *   box: x > box[0] && x < box[1] && y > box[2] && y < box[3] && z > box[4] && z < box[5] && d > box[6] && d < box[7], strict
+ *   float32 comparisons (:251-257); a NaN or infinite coordinate fails them.
+ *   angles: az = (float)atan2((double)y, (double)x), el = (float)atan2((double)z, (double)d); kept iff t0 < az && az < t1 &&
+ *   t2 < el && el < t3, strict, in float32.  The fp64 atan2 rounded to float32 is deliberate: numpy's float32 arctan2 is not
+ *   correctly rounded and differs between builds.  IEEE special cases hold: atan2(+0, -0) = pi, atan2(+-0, +0) = +-0; the point
+ *   (0, 0, 0) has az = el = 0 and is kept, as in the reference.
+ *   compaction is STABLE: kept rows keep their scan order, so the output is the reference's points[mask], identical from run
+ *   to run.
+ * Outputs: out_points fp32 [., 4] (16-byte aligned; the kept rows, bit for bit); out_labels int32 (c - 1; 0 for an unlabelled
+ * scan; may be NULL); out_index int32 (the raw row inside its scan each kept row came from, strictly increasing; may be NULL);
+ * out_count int64[B]; err (device int, caller zeroes, may be NULL) receives
+ *   PN2_SCAN_ERR_CLASS  a raw class outside the map (sem >= lut_len or lut[sem] < 0): the row is dropped;
+ *   PN2_SCAN_ERR_ROWS   a row_count[b] above max_rows: the rows beyond max_rows are ignored.
+ * workspace: pn2_scan_filter_workspace_bytes(B, max_rows) bytes of device memory, 16-byte aligned (a one-byte flag per row of
+ * every tile, a count and an offset per tile); its content need not be kept between calls.  PN2_EINVAL without a launch for a null
+ * required pointer, B < 1 or B > 65535, max_rows < 0 or >= 2^31, lut_len < 1 (or a null lut) with labels given, a misaligned
+ * raw / out_points / workspace; pn2_scan_filter_workspace_bytes returns PN2_EINVAL for such B / max_rows. */
+#define PN2_SCAN_TILE 1024
+#define PN2_SCAN_ERR_CLASS 1
+#define PN2_SCAN_ERR_ROWS 2
+int64_t pn2_scan_filter_workspace_bytes(int B, int64_t max_rows);
+int pn2_scan_filter(const float *raw, const uint32_t *raw_label, const int64_t *row_begin, const int64_t *row_count, int B,
+                    int64_t max_rows, const int32_t *lut, int lut_len, const float *fov, const float *box, const int64_t *out_begin,
+                    float *out_points, int32_t *out_labels, int32_t *out_index, int64_t *out_count, int *err, void *workspace,
+                    pn2_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -108,6 +108,8 @@ SIGNATURES = {
     "pn2_splat_resolve": (_i, [_vp, _i, _i, _vp, _i64, _vp, _i, _vp, _vp, _vp, _vp]),
     "pn2_depth_splat": (_i, [_vp, _i, _i64, _vp, _vp, _d, _d, _i, _i, _i, _vp, _vp]),
     "pn2_depth_resolve": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "pn2_scan_filter_workspace_bytes": (_i64, [_i, _i64]),
+    "pn2_scan_filter": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 
@@ -115,6 +117,8 @@ ABI_VERSION = 15
 PN2_EUNSUPPORTED = -3            # include/pn2.h
 PN2_OK_SPLIT = 1                 # pn2_conv1x1_bwd_pair: done as two launches
 DWX_REPLICAS = 32        # PN2_DWX_REPLICAS of include/pn2.h
+SCAN_TILE = 1024         # PN2_SCAN_TILE of include/pn2.h: rows per workgroup of pn2_scan_filter
+SCAN_ERR_CLASS, SCAN_ERR_ROWS = 1, 2     # PN2_SCAN_ERR_* of include/pn2.h
 
 
 class BnLazy(ctypes.Structure):
@@ -171,7 +175,8 @@ class _Timed:
                                                    "pn2_nll_loss_workspace_bytes", "pn2_cross_entropy_workspace_bytes", "pn2_res_supported", "pn2_bwd_res_supported", "pn2_conv1x1_wgrad_workspace_bytes",
                                                    "pn2_conv1x1_wgrad_cf_scratch_bytes", "pn2_conv1x1_bwd_cf_supported", "pn2_conv1x1_bwd_first_supported", "pn2_conv1x1_bwd_cf_scratch_bytes", "pn2_last_kernel", "pn2_clear_last_kernel",
                                                    "pn2_ball_query_workspace_bytes", "pn2_point_transform_workspace_bytes",
-                                                   "pn2_group_colsum_workspace_bytes", "pn2_chamfer_nn_workspace_bytes"):
+                                                   "pn2_group_colsum_workspace_bytes", "pn2_chamfer_nn_workspace_bytes",
+                                                   "pn2_scan_filter_workspace_bytes"):
             return fn
 
         def timed(*args):

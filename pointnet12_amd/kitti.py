@@ -7,13 +7,24 @@ the points of class 0 and shift the rest down by one (:215-221), and for the ``i
 field of view (:223-227 with ``points_basic_filter`` :259-280).  This runs once per scan when the store is filled;
 everything per batch happens on the device (loader.prepare_batch).
 
+``ScanFilter`` / ``read_scan_device`` / ``load_scans(ingest="device")`` do the same five steps on the device
+(``pn2_scan_filter``, csrc/scan.hip): the raw ``.bin`` / ``.label`` words are uploaded as they are, and the kept rows,
+their classes, their row numbers and the kept COUNT stay in device memory, so a frame path or a live feed needs no host
+pass.  The device rule is the one of include/pn2.h; it differs from ``in_view`` in one place only: the two angles are
+fp64 ``atan2`` values rounded to float32, where numpy's float32 ``arctan2`` is a few ulp off the correctly rounded value
+(and differs between numpy builds), so a point within a few float32 steps of a field-of-view border may fall on the
+other side (tests/scan_filter_ref.py quantifies it).
+
 The filter keeps the reference's exact forms: the azimuth test is ``-40 deg < atan2(y, x) < 40 deg`` on float32
 angles, and the elevation test takes ``atan2(z, d)`` with d the full 3-D range ``sqrt(x^2 + y^2 + z^2)`` (not the
 ground range), bounds -20 deg .. 20 deg (:263-268, :237-249).
 """
-import numpy as np
+import ctypes
 
-from . import loader
+import numpy as np
+import torch
+
+from . import _lib, loader
 
 
 def in_view(points, h_fov=(-40, 40), v_fov=(-20, 20)):
@@ -56,9 +67,202 @@ def read_scan(fn_velo, fn_label, learning_map, subset="all"):
     return points, label
 
 
-def load_scans(pairs, learning_map, subset="inview", device="cuda"):
+def _read_files(fn_velo, fn_label):
+    points = np.fromfile(fn_velo, dtype=np.float32).reshape(-1, 4)
+    raw = None
+    if fn_label is not None:
+        raw = np.fromfile(fn_label, dtype=np.uint32).reshape(-1)
+        if raw.shape[0] != points.shape[0]:
+            raise ValueError("Scan and Label don't contain same number of points")
+    return points, raw
+
+
+class ScanBuffers:
+    """The static buffers of one ``ScanFilter.filter`` call shape (``ScanFilter.buffers``): ``points`` float32 ``[rows, 4]``,
+    ``labels`` / ``index`` int32 ``[rows]``, ``count`` int64 ``[B]`` and the kernel's ``workspace``."""
+
+    def __init__(self, rows, B, max_rows, device):
+        nbytes = _lib.load().pn2_scan_filter_workspace_bytes(int(B), int(max_rows))
+        if nbytes < 0:
+            raise _lib.Pn2Error("ScanBuffers: B = %d, max_rows = %d are not supported" % (B, max_rows))
+        self.rows, self.B, self.max_rows = int(rows), int(B), int(max_rows)
+        self.points = torch.empty(self.rows, 4, device=device, dtype=torch.float32)
+        self.labels = torch.empty(self.rows, device=device, dtype=torch.int32)
+        self.index = torch.empty(self.rows, device=device, dtype=torch.int32)
+        self.count = torch.zeros(self.B, device=device, dtype=torch.int64)
+        self.workspace = torch.empty(nbytes, device=device, dtype=torch.uint8)
+
+
+class ScanFilter:
+    """``Semantic_KITTI_Utils.get``'s class map, class drop, view filter and compaction on the device (``pn2_scan_filter``).
+
+    ``learning_map``: dict raw class -> training class (0 = ignored), uploaded once as a look-up table; None serves
+    unlabelled scans only.  The filter arguments have the defaults and the meaning of the reference's ``set_filter``
+    (kitti_utils.py:229-235): ``subset="inview"`` takes ``h_fov = (-40, 40)``, ``v_fov = (-20, 20)`` where they are not given, as
+    ``get`` does (:222), and every range defaults to ``(-10000, 10000)``.  ``subset="all"`` applies no angular test (``h_fov`` /
+    ``v_fov`` must be None), and the range box only if one of the four ranges is given: without any, every row passes, NaN
+    rows included, as in ``get``.  The angular thresholds are computed as the reference computes them (``-h_fov[1] * np.pi / 180``
+    and so on) and rounded to float32, which is what numpy compares a float32 array with.
+
+    ``error_flag`` (device int32, cleared at the start of every ``filter``) collects ``_lib.SCAN_ERR_CLASS`` (a raw class
+    outside the map: the reference raises ``KeyError``, here the row is dropped) and ``_lib.SCAN_ERR_ROWS`` (a ``row_count``
+    above ``max_rows``: the rows beyond are ignored); ``check()`` reads it back and raises."""
+
+    def __init__(self, learning_map=None, subset="inview", h_fov=None, v_fov=None, x_range=None, y_range=None, z_range=None,
+                 d_range=None, device="cuda"):
+        if subset not in ("all", "inview"):
+            raise AssertionError(subset)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.Pn2Error("ScanFilter: the HIP device is the only implementation")
+        self.subset = subset
+        ranges = (x_range, y_range, z_range, d_range)
+        if subset == "inview":
+            h_fov = (-40, 40) if h_fov is None else h_fov
+            v_fov = (-20, 20) if v_fov is None else v_fov
+            self.fov = np.array([-h_fov[1] * np.pi / 180, -h_fov[0] * np.pi / 180, v_fov[0] * np.pi / 180, v_fov[1] * np.pi / 180],
+                                np.float64).astype(np.float32)
+        else:
+            if h_fov is not None or v_fov is not None:
+                raise ValueError('ScanFilter: subset="all" applies no angular test (h_fov and v_fov must be None)')
+            self.fov = None
+        self.box = None
+        if subset == "inview" or any(r is not None for r in ranges):
+            self.box = np.array([r if r is not None else (-10000, 10000) for r in ranges], np.float64).reshape(8).astype(np.float32)
+        self.lut = None
+        if learning_map is not None:
+            lut = np.full(int(max(learning_map)) + 1, -1, np.int32)
+            for k, v in learning_map.items():
+                lut[int(k)] = int(v)
+            self.lut = torch.from_numpy(lut).to(self.device)
+        self.error_flag = torch.zeros(1, device=self.device, dtype=torch.int32)
+        self._zero = torch.zeros(1, device=self.device, dtype=torch.int64)
+
+    def buffers(self, rows, B=1, max_rows=None):
+        """``ScanBuffers`` for calls of ``B`` scans of at most ``max_rows`` rows each (default ``rows``) whose outputs fit ``rows``."""
+        return ScanBuffers(rows, B, rows if max_rows is None else max_rows, self.device)
+
+    def filter(self, raw, raw_label=None, row_begin=None, row_count=None, max_rows=None, out=None, out_begin=None):
+        """``(points, labels, index, count)`` as device tensors.  ``raw``: float32 ``[rows, 4]`` on the device, the ``.bin`` rows of
+        one scan or of B scans back to back; ``raw_label``: their ``.label`` words (32-bit: int32 or uint32 tensor ``[rows]``) or
+        None for unlabelled scans (``labels`` is then None).  ``row_begin`` / ``row_count``: int64 ``[B]`` DEVICE tensors as
+        ``pn2_prepare_clouds`` reads them (None: one scan, all of ``raw``); ``max_rows``: a host bound of every count (None:
+        ``raw``'s rows).  Scan b's kept rows are ``points[out_begin[b] : out_begin[b] + count[b]]`` (``out_begin``: int64 ``[B]`` on
+        the device, None: ``row_begin``) in scan order -- the reference's ``points[mask]`` -- with ``labels`` int32 (the class
+        after the shift) and ``index`` int32 (the raw row inside its scan, strictly increasing) beside them; rows outside those
+        ranges are not written.  ``count`` is int64 ``[B]`` and stays on the device: nothing is read back.  With ``out`` (a
+        ``ScanBuffers`` of this shape) and ``row_begin`` / ``row_count`` given the call allocates nothing and can be captured
+        in a graph; a captured call stays valid when ``row_count``'s content changes."""
+        if not isinstance(raw, torch.Tensor) or not raw.is_cuda:
+            raise _lib.Pn2Error("ScanFilter.filter: raw must live on the GPU: this package has no CPU path")
+        if raw.dtype != torch.float32 or raw.dim() != 2 or raw.shape[1] != 4 or not raw.is_contiguous():
+            raise ValueError("ScanFilter.filter: raw must be a contiguous float32 [rows, 4] tensor")
+        rows = int(raw.shape[0])
+        if raw_label is not None:
+            if self.lut is None:
+                raise ValueError("ScanFilter.filter: labels given, but the filter has no learning_map")
+            if not raw_label.is_cuda or raw_label.element_size() != 4 or raw_label.is_floating_point() or \
+                    raw_label.numel() != rows or not raw_label.is_contiguous():
+                raise ValueError("Scan and Label don't contain same number of points")     # (or not 32-bit words on the device)
+        if (row_begin is None) != (row_count is None):
+            raise ValueError("ScanFilter.filter: row_begin and row_count go together")
+        if row_begin is None:
+            row_begin, row_count = self._zero, torch.full((1,), rows, device=self.device, dtype=torch.int64)
+        B = int(row_begin.numel())
+        for t in (row_begin, row_count) + (() if out_begin is None else (out_begin,)):
+            if not t.is_cuda or t.dtype != torch.int64 or t.numel() != B or not t.is_contiguous():
+                raise ValueError("ScanFilter.filter: row_begin, row_count and out_begin must be int64 [B] device tensors")
+        max_rows = rows if max_rows is None else int(max_rows)
+        if out is None:
+            out = ScanBuffers(rows, B, max_rows, self.device)
+        elif out.B != B or out.max_rows < max_rows:
+            raise ValueError("ScanFilter.filter: out was made for B = %d, max_rows = %d" % (out.B, out.max_rows))
+        p = _lib.ptr
+        fp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+        self.error_flag.zero_()                                      # an async fill, nothing is read back
+        # (max_rows as the buffers were made for: the workspace layout follows it)
+        _lib.check(_lib.load().pn2_scan_filter(p(raw), p(raw_label), p(row_begin), p(row_count), B, out.max_rows, p(self.lut),
+                                               0 if self.lut is None else int(self.lut.numel()), fp(self.fov), fp(self.box),
+                                               p(row_begin if out_begin is None else out_begin), p(out.points),
+                                               p(out.labels) if raw_label is not None else None, p(out.index), p(out.count),
+                                               p(self.error_flag), p(out.workspace), _lib.stream()), "pn2_scan_filter")
+        return out.points, (out.labels if raw_label is not None else None), out.index, out.count
+
+    def check(self):
+        """Reads ``error_flag`` back: ``KeyError`` for a raw class missing from the map (as the reference's dict lookup),
+        ``ValueError`` for a ``row_count`` above ``max_rows``."""
+        flag = int(self.error_flag.item())
+        if flag & _lib.SCAN_ERR_CLASS:
+            raise KeyError("a raw class is missing from the learning map")
+        if flag & _lib.SCAN_ERR_ROWS:
+            raise ValueError("ScanFilter: a row_count is above max_rows")
+
+
+def _upload_words(words, device):
+    return torch.from_numpy(np.ascontiguousarray(words).view(np.int32)).to(device)     # the same 32 bits (torch has no uint32 math)
+
+
+def read_scan_device(fn_velo, fn_label, scan_filter):
+    """``read_scan`` through the device: ``np.fromfile`` of both files, one upload, ``scan_filter.filter``.  Returns
+    ``(points [M, 4] float32, labels [M] int32)`` as DEVICE tensors of exact size, for which the one kept count is read back
+    (``ScanFilter.filter`` itself reads nothing back).  ``fn_label`` None: an unlabelled scan, ``labels`` is None.  A raw class
+    missing from the map raises ``KeyError``, as ``read_scan`` does."""
+    points, words = _read_files(fn_velo, fn_label)
+    raw = torch.from_numpy(points).to(scan_filter.device)
+    lab = None if words is None else _upload_words(words, scan_filter.device)
+    pts, labels, _, count = scan_filter.filter(raw, lab)
+    m = int(count.item())
+    scan_filter.check()
+    return pts[:m], (None if labels is None else labels[:m])
+
+
+def _ingest_chunk(chunk, scan_filter):
+    """One batched launch over the scans of ``chunk`` ([(points, words)], host arrays): (points, labels, counts) packed."""
+    dev = scan_filter.device
+    counts = np.array([p.shape[0] for p, _ in chunk], np.int64)
+    begins = np.cumsum(counts) - counts
+    if counts.sum() == 0:                                            # (nothing to launch on)
+        return torch.empty(0, 4, device=dev), torch.empty(0, device=dev, dtype=torch.int32), np.zeros(len(chunk), np.int64)
+    raw = torch.from_numpy(np.ascontiguousarray(np.concatenate([p for p, _ in chunk], 0))).to(dev)
+    lab = _upload_words(np.concatenate([w for _, w in chunk], 0), dev)
+    begin_dev = torch.from_numpy(begins).to(dev)
+    pts, labels, _, kept = scan_filter.filter(raw, lab, begin_dev, torch.from_numpy(counts).to(dev), int(counts.max()))
+    kept = kept.cpu().numpy()                                        # the one read-back of the chunk
+    scan_filter.check()
+    total = int(kept.sum())
+    out_p = torch.empty(total, 4, device=dev, dtype=torch.float32)
+    out_l = torch.empty(total, device=dev, dtype=torch.int32)
+    at = 0
+    for b, k in zip(begins.tolist(), kept.tolist()):                 # the pack: device-to-device copies of the kept runs
+        out_p[at:at + k] = pts[b:b + k]
+        out_l[at:at + k] = labels[b:b + k]
+        at += k
+    return out_p, out_l, kept
+
+
+def load_scans(pairs, learning_map, subset="inview", device="cuda", ingest="host", chunk_rows=1 << 22):
     """``ScanStore`` over the ``(bin_path, label_path)`` pairs (a sequence's scans, e.g. every second one for
-    training as SemKITTI_Loader.py:62-66 selects them)."""
+    training as SemKITTI_Loader.py:62-66 selects them).  ``ingest="host"``: every scan through ``read_scan`` (numpy).
+    ``ingest="device"``: the raw files are uploaded in chunks of about ``chunk_rows`` rows, each chunk goes through one
+    batched ``pn2_scan_filter`` launch, its kept counts are read back once and the kept runs are packed into the store; the
+    store equals the host one except where a point lies within a few float32 steps of a field-of-view border (module
+    docstring)."""
+    if ingest not in ("host", "device"):
+        raise ValueError('load_scans: ingest must be "host" or "device"')
+    if ingest == "device":
+        pairs = list(pairs)
+        if not pairs:
+            raise ValueError("ScanStore: no scans")
+        scan_filter = ScanFilter(learning_map, subset, device=device)
+        parts, chunk, rows = [], [], 0
+        for k, (fn_velo, fn_label) in enumerate(pairs):
+            chunk.append(_read_files(fn_velo, fn_label))
+            rows += chunk[-1][0].shape[0]
+            if rows >= chunk_rows or k == len(pairs) - 1:
+                parts.append(_ingest_chunk(chunk, scan_filter))
+                chunk, rows = [], 0
+        return loader.ScanStore.from_device(torch.cat([p for p, _, _ in parts]), torch.cat([l for _, l, _ in parts]),
+                                            np.concatenate([c for _, _, c in parts]))
     scans, labels = [], []
     for fn_velo, fn_label in pairs:
         p, l = read_scan(fn_velo, fn_label, learning_map, subset)

@@ -566,13 +566,17 @@ class FrameSegmenter:
 
     def choice(self, length, rng="numpy"):
         """``np.random.choice(length, npoints, replace=True)`` (pcdvis.py:121: a seeded numpy run draws what the reference
-        draws), or the same distribution from a device ``torch.Generator``."""
+        draws), or the same distribution from a device ``torch.Generator``.  With a generator ``length`` may be a device int64
+        tensor of one element (``ScanFilter.filter``'s count): the draw is ``min((u * length).long(), length - 1)`` on the device,
+        nothing is read back, and a length of 0 gives -1 everywhere."""
         if isinstance(rng, torch.Generator):
             u = torch.rand(self.npoints, device=self.device, dtype=torch.float64, generator=rng)
+            if isinstance(length, torch.Tensor):
+                return torch.minimum((u * length).long(), length - 1)
             return torch.clamp((u * length).long(), max=length - 1)
         if rng != "numpy":
             raise ValueError('FrameSegmenter: rng must be "numpy" or a device torch.Generator')
-        return torch.from_numpy(np.random.choice(length, self.npoints, replace=True).astype(np.int64)).to(self.device)
+        return torch.from_numpy(np.random.choice(int(length), self.npoints, replace=True).astype(np.int64)).to(self.device)
 
     def render(self, log_probs, raw_rows, points, background=None):
         """Post-network stages into the segmenter's buffers: predict, project ``raw_rows[:, :3]``, draw the camera image over
@@ -615,6 +619,10 @@ class FrameSegmenter:
         # the resampled raw rows (pcdvis.py:122, :125) through the library's row gather: [1, M, 4] -> [1, n, 4]
         _check(lib.pn2_gather_rows(_p(raw), _p(choice), 1, M, 4, n, _p(self.raw_rows), _p(self.error_flag), _lib.stream()),
                "pn2_gather_rows")
+        return self._finish(normed, background)
+
+    def _finish(self, normed, background):
+        """The network and the post-network stages on the normalised rows ``[1, n, 4]`` (``self.raw_rows`` holds the raw ones)."""
         was_training = self.model.training
         self.model.eval()
         try:
@@ -632,4 +640,80 @@ class FrameSegmenter:
                "pts_2d": self.pts_2d, "pix": self.pix, "image": self.image, "top_view": self.top_view}
         if self.camera is not None:
             out["ego_view"] = self.ego_view
+        return out
+
+    def _raw_buffers(self, scan_filter, rows):
+        """Static input and ``ScanBuffers`` of capacity ``rows`` for ``frame_raw`` (kept while the capacity and the filter's device
+        stay the same)."""
+        held = getattr(self, "_raw_state", None)
+        if held is None or held["rows"] < rows:
+            dev = self.device
+            held = {"rows": rows, "raw": torch.empty(rows, 4, device=dev, dtype=torch.float32),
+                    "words": torch.empty(rows, device=dev, dtype=torch.int32), "out": scan_filter.buffers(rows),
+                    "begin": torch.zeros(1, device=dev, dtype=torch.int64), "count": torch.zeros(1, device=dev, dtype=torch.int64)}
+            self._raw_state = held
+        return held
+
+    def frame_raw(self, raw_scan, raw_label=None, scan_filter=None, rng="numpy", background=None, choice=None, max_rows=None):
+        """``frame`` for a RAW scan: ``raw_scan`` float32 ``[M, 4]`` (the ``.bin`` rows) and, if there is one, ``raw_label`` ``[M]``
+        (the ``.label`` words, uint32 / int32; None: a live feed), as numpy arrays or tensors on either side.  ``scan_filter``: a
+        ``kitti.ScanFilter`` (its class map, subset and ranges).  The stages are: upload into a static buffer of ``max_rows`` rows
+        (default: the largest scan seen so far) -> ``pn2_scan_filter`` -> the choice -> ``pn2_prepare_clouds`` and the row
+        gather with the DEVICE-side kept count -> the rest of ``frame``.  The result holds ``frame``'s keys plus ``count`` (int64
+        ``[1]`` on the device), ``labels`` (int32, the kept rows' classes, None without ``raw_label``) and ``index`` (int32, their
+        raw rows); only the first ``count`` entries of the last two mean anything.
+
+        ``rng``: with a device ``torch.Generator`` the choice is ``min((u * count).long(), count - 1)`` on the device and NOTHING
+        is read back (with ``raw_scan`` / ``raw_label`` already on the device, or pinned, the whole call is free of host
+        synchronisation).  With ``rng="numpy"`` the ONE kept count is read back and ``np.random.choice(count, npoints)`` is
+        drawn, which is the reference's draw (pcdvis.py:121) from a seeded numpy run.  An explicit ``choice`` (row numbers in the
+        FILTERED scan) is used as it is.
+
+        A scan of which nothing survives the filter makes the device choice -1 everywhere: ``pn2_prepare_clouds`` flags that in
+        ``error_flag`` (the frame then shows row 0 / zeros); with ``rng="numpy"`` it raises ``ValueError``, as ``frame`` does for
+        an empty scan.  A raw class outside the map or more rows than ``max_rows`` set ``scan_filter.error_flag``."""
+        lib = _lib.load()
+        if scan_filter is None:
+            raise ValueError("FrameSegmenter.frame_raw: a kitti.ScanFilter is needed")
+        self.error_flag.zero_()
+        if isinstance(raw_scan, np.ndarray):
+            raw_scan = torch.from_numpy(np.ascontiguousarray(raw_scan, np.float32))
+        if raw_scan.dim() != 2 or raw_scan.shape[1] != 4 or raw_scan.dtype != torch.float32:
+            raise ValueError("FrameSegmenter.frame_raw: raw_scan must be float32 [M, 4] (x, y, z, intensity)")
+        M = int(raw_scan.shape[0])
+        if M == 0:
+            raise ValueError("FrameSegmenter.frame_raw: empty scan")
+        if raw_label is not None:
+            if isinstance(raw_label, np.ndarray):
+                raw_label = torch.from_numpy(np.ascontiguousarray(raw_label).view(np.int32))
+            if raw_label.numel() != M or raw_label.element_size() != 4 or raw_label.is_floating_point():
+                raise ValueError("Scan and Label don't contain same number of points")
+        held = self._raw_buffers(scan_filter, max(M, int(max_rows or 0)))
+        # (asynchronous only from the device or from pinned memory; a pageable host array is copied before the call returns)
+        held["raw"][:M].copy_(raw_scan, non_blocking=raw_scan.is_cuda or raw_scan.is_pinned())
+        if raw_label is not None:
+            held["words"][:M].copy_(raw_label.reshape(-1).view(torch.int32), non_blocking=raw_label.is_cuda or raw_label.is_pinned())
+        held["count"].fill_(M)
+        pts, labels, index, count = scan_filter.filter(held["raw"], held["words"] if raw_label is not None else None, held["begin"],
+                                                       held["count"], held["rows"], out=held["out"])
+        if choice is None:
+            if isinstance(rng, torch.Generator):
+                choice = self.choice(count, rng)
+            else:
+                kept = int(count.item())                             # the one read-back of the numpy draw
+                if kept == 0:
+                    raise ValueError("FrameSegmenter.frame_raw: nothing of the scan survives the filter")
+                choice = self.choice(kept, rng)
+        choice = torch.as_tensor(choice).to(device=self.device, dtype=torch.int64).reshape(-1).contiguous()
+        if choice.numel() != self.npoints:
+            raise ValueError("FrameSegmenter.frame_raw: choice must hold npoints = %d rows" % self.npoints)
+        n = self.npoints
+        normed = torch.empty(1, n, 4, device=self.device, dtype=torch.float32)
+        # (a choice outside [0, count) sets error_flag and reads row 0: the count is the kernel's own, in device memory)
+        _check(lib.pn2_prepare_clouds(_p(pts), _p(held["begin"]), _p(count), None, None, None, _p(choice), 1, n, _p(normed), None,
+                                      _p(self.error_flag), _lib.stream()), "pn2_prepare_clouds")
+        _check(lib.pn2_gather_rows(_p(pts), _p(choice), 1, held["rows"], 4, n, _p(self.raw_rows), _p(self.error_flag), _lib.stream()),
+               "pn2_gather_rows")
+        out = self._finish(normed, background)
+        out.update({"count": count, "labels": labels, "index": index})
         return out

@@ -47,6 +47,27 @@ class ScanStore:
         self._begin_dev = self.row_begin.to(self.device)
         self._count_dev = self.row_count.to(self.device)
 
+    @classmethod
+    def from_device(cls, raw, label, row_count):
+        """A store over rows that are on the device already (``kitti.load_scans(ingest="device")``): ``raw`` float32 ``[rows, 4]``,
+        ``label`` int32 ``[rows]`` or None, ``row_count`` the scans' row counts (host)."""
+        self = cls.__new__(cls)
+        self.device = raw.device
+        if self.device.type != "cuda":
+            raise _lib.Pn2Error("ScanStore: the HIP device is the only implementation")
+        self.row_count = torch.as_tensor(np.asarray(row_count), dtype=torch.int64)
+        if self.row_count.numel() == 0:
+            raise ValueError("ScanStore: no scans")
+        if raw.dim() != 2 or raw.shape[1] != 4 or raw.dtype != torch.float32 or int(self.row_count.sum()) != raw.shape[0] or \
+                (label is not None and (label.dtype != torch.int32 or label.shape != (raw.shape[0],))):
+            raise ValueError("ScanStore: raw must be float32 [sum(row_count), 4] and label int32 [sum(row_count)]")
+        self.row_begin = torch.cumsum(self.row_count, 0) - self.row_count
+        self.raw = raw.contiguous()
+        self.label = None if label is None else label.contiguous()
+        self._begin_dev = self.row_begin.to(self.device)
+        self._count_dev = self.row_count.to(self.device)
+        return self
+
     def __len__(self):
         return self.row_count.numel()
 

@@ -2,7 +2,7 @@
 """One frame of the reference's KITTI demo (``python pcdvis.py``) on the HIP library: scan -> labels -> pixels -> two images,
 three with ``--ego``.
 
-    python tools/demo_kitti.py [--out DIR] [--npoints 25000] [--seed 0] [--merge] [--time] [--ego CAMERA.json [--render-option FILE.json]]
+    python tools/demo_kitti.py [--out DIR] [--npoints 25000] [--seed 0] [--merge] [--time] [--raw] [--ego CAMERA.json [--render-option FILE.json]]
     python tools/demo_kitti.py --root $KITTI_ROOT --part 01 --index 0 --calib DIR --config semantic-kitti.yaml [--checkpoint CKPT]
 
 Without ``--root`` the scan is synthetic (``synthetic.kitti_cloud``, un-normalised back to metres), the calibration is the one
@@ -15,6 +15,10 @@ written as PNG through PIL (``semantic.png``: the camera view, ``top_view.png``)
 ``--ego CAMERA.json`` (an open3d ``PinholeCameraParameters`` file, the reference's ``config/ego_view.json``) adds the demo's 3-D ego
 view (``Window_Manager.update``, pcdvis.py:31-51) as ``ego_view.png``; ``--render-option FILE.json`` (an open3d ``RenderOption``
 file, the reference's ``config/render_option.json``) sets its point size and background colour (defaults: 2, black).  The picture follows the rule stated in include/pn2.h, which is unverified against open3d.
+
+``--raw`` feeds the RAW scan through ``FrameSegmenter.frame_raw``: the class map, the class drop, the view filter and the
+compaction run on the device (``kitti.ScanFilter``, ``pn2_scan_filter``) and the kept count never leaves it; the synthetic scan has
+no label file (a live feed), a dataset scan goes in with its ``.label`` words.  The choice is then drawn on the device.
 
 ``--time`` prints one JSON line with medians of 20 (device work included, host clock) for the post-network stages --
 predict + project + both images (``render_ms``), and the same as a captured graph (``render_graph_ms``) -- and beside them, in
@@ -52,7 +56,7 @@ def synthetic_inputs(seed):
     n = syn.kitti_cloud(seed, 60000, 60000, 1)[:, :4]
     scan = np.stack([n[:, 0] * 70, n[:, 1] * 70, n[:, 2] * 3, n[:, 3] / 2 + 0.5], 1).astype(np.float32)
     cfg = {k: dict(zip(g[k + "_keys"].tolist(), g[k + "_values"].tolist())) for k in ("labels", "color_map", "learning_map_inv")}
-    return scan, None, V.Calibration(g["R"], g["T"], g["P"]), cfg
+    return scan, None, V.Calibration(g["R"], g["T"], g["P"]), cfg, None
 
 
 def dataset_inputs(args):
@@ -61,12 +65,17 @@ def dataset_inputs(args):
     from pointnet12_amd import kitti
     cfg = yaml.safe_load(open(args.config))
     seq = os.path.join(args.root, "sequences", args.part)
-    scan, _ = kitti.read_scan(os.path.join(seq, "velodyne", "%06d.bin" % args.index), os.path.join(seq, "labels", "%06d.label" % args.index),
-                              cfg["learning_map"], "inview")
+    words = None
+    if args.raw:
+        scan = np.fromfile(os.path.join(seq, "velodyne", "%06d.bin" % args.index), dtype=np.float32).reshape(-1, 4)
+        words = np.fromfile(os.path.join(seq, "labels", "%06d.label" % args.index), dtype=np.uint32)
+    else:
+        scan, _ = kitti.read_scan(os.path.join(seq, "velodyne", "%06d.bin" % args.index), os.path.join(seq, "labels", "%06d.label" % args.index),
+                                  cfg["learning_map"], "inview")
     fn = os.path.join(seq, "image_2", "%06d.png" % args.index)
     frame = np.asarray(Image.open(fn).convert("RGB")) if os.path.exists(fn) else None
     calib = V.Calibration.from_files(os.path.join(args.calib, "calib_velo_to_cam.txt"), os.path.join(args.calib, "calib_cam_to_cam.txt"))
-    return scan, frame, calib, cfg
+    return scan, frame, calib, cfg, words
 
 
 def host_ms(fn, reps=20, warmup=3):
@@ -185,6 +194,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--merge", action="store_true", help="predict over the demo's merged classes")
     ap.add_argument("--time", action="store_true")
+    ap.add_argument("--raw", action="store_true", help="feed the raw scan through frame_raw: filter and compaction on the device")
     ap.add_argument("--ego", metavar="CAMERA.json", help="also draw the 3-D ego view through this open3d PinholeCameraParameters file")
     ap.add_argument("--render-option", metavar="FILE.json", help="open3d RenderOption file: the ego view's point size and background colour")
     ap.add_argument("--root")
@@ -199,9 +209,9 @@ def main():
     if args.root:
         if not (args.calib and args.config):
             ap.error("--root needs --calib and --config")
-        scan, frame, calib, cfg = dataset_inputs(args)
+        scan, frame, calib, cfg, words = dataset_inputs(args)
     else:
-        scan, frame, calib, cfg = synthetic_inputs(args.seed)
+        scan, frame, calib, cfg, words = synthetic_inputs(args.seed)
     names, colors, _ = V.classes_from_config(cfg)
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
@@ -218,7 +228,16 @@ def main():
     option = V.RenderOption.from_json(args.render_option) if args.render_option else V.RenderOption()
     seg = V.FrameSegmenter(model, calib, colors if groups is None else groups.colors, npoints=args.npoints, image_size=size, groups=groups,
                            camera=camera, point_size=option.point_size, ego_background=option.background_color)
-    out = seg.frame(scan, background=frame)
+    if args.raw:
+        from pointnet12_amd import kitti
+        scan_filter = kitti.ScanFilter(cfg["learning_map"] if words is not None else None, "inview")
+        gen = torch.Generator(device="cuda")
+        gen.manual_seed(args.seed)
+        out = seg.frame_raw(scan, words, scan_filter=scan_filter, rng=gen, background=frame)
+        print("raw scan of %d rows, %d kept by the device filter; filter error flag %d"
+              % (len(scan), int(out["count"].item()), int(scan_filter.error_flag.item())))
+    else:
+        out = seg.frame(scan, background=frame)
     os.makedirs(args.out, exist_ok=True)
     Image.fromarray(out["image"].cpu().numpy()).save(os.path.join(args.out, "semantic.png"))
     Image.fromarray(out["top_view"].cpu().numpy()).save(os.path.join(args.out, "top_view.png"))
