@@ -799,6 +799,35 @@ int pn2_scan_filter(const float *raw, const uint32_t *raw_label, const int64_t *
                     float *out_points, int32_t *out_labels, int32_t *out_index, int64_t *out_count, int *err, void *workspace,
                     pn2_stream_t stream);
 
+/* ---- k nearest neighbours and the vote over them (csrc/knn.hip), added within ABI 15 (purely additive: no version change) ----------
+ * K nearest candidates of every query.  query [B,N,3], cand [B,M,3], 1 <= K <= 32, K <= M.
+ * d2 = pair_dist of geometry.hip (expanded form, the arithmetic of pn2_three_nn and pn2_square_distance, bit for bit).
+ * idx [B,N,K] int64, dist [B,N,K] float32 (may be NULL): ascending d2, equal d2 in ascending candidate index
+ * (= the first K of a stable sort of the row of distances).  A candidate whose d2 is NaN or +inf is never selected;
+ * slots left unfilled hold idx = M and dist = +inf (as pn2_ball_query writes N for an empty ball).
+ * n_query / n_cand (device int64 [B], either may be NULL = N / M): only the first n_query[b] queries are written and only
+ * the first n_cand[b] candidates searched (clamped to [0,N] / [0,M]); rows at and beyond n_query[b] are left untouched.
+ * K > 32: PN2_EUNSUPPORTED, nothing launched.  K < 1, K > M, null pointers, non-positive sizes: PN2_EINVAL.
+ * (B <= 65535, N <= 2^31 - 256: PN2_EINVAL beyond.) */
+int pn2_knn(const float *query, const float *cand, int B, int N, int M, int K, const int64_t *n_query, const int64_t *n_cand,
+            int64_t *idx, float *dist, pn2_stream_t stream);
+/* Majority label of each row's neighbours.  idx/dist [B,N,K] as pn2_knn wrote them, cand_label int64 [B,M].
+ * Slot k of a row VOTES iff 0 <= idx[k] < M and !(dist[k] > max_d2)   (max_d2 = +inf: no cut-off).
+ * Winner = the label with the most voting slots; among labels with equally many, the one whose first voting slot comes
+ * first (i.e. whose nearest voter is nearest).  No voting slot: the row's result is `fill`.
+ * lut (int32 [L], may be NULL): the result is lut[label]; a winning label outside [0,L) gives `fill` and sets *err |= 1.
+ * Without a lut the result is the label's low 32 bits.
+ * dst (int32 [B,N], may be NULL): row n of cloud b is written at out[b*out_stride + dst[b,n]] instead of out[b*out_stride + n];
+ * a dst outside [0,out_stride) is skipped and sets *err |= 2.  Only the first n_query[b] rows are processed (NULL = N).
+ * out int32.  err: device int32, may be NULL.  1 <= K <= 32 (larger: PN2_EUNSUPPORTED, nothing launched).
+ * Every candidate slot votes once: a candidate that appears several times among the M (a cloud drawn with replacement) votes
+ * once per appearance.  Integer arithmetic only: out is exact and the same from run to run.
+ * PN2_EINVAL: null idx / dist / cand_label / out, non-positive sizes, K < 1, out_stride < 1, out_stride < N without a dst,
+ * a lut with L < 1. */
+int pn2_knn_vote(const int64_t *idx, const float *dist, const int64_t *cand_label, int B, int N, int M, int K, float max_d2,
+                 const int64_t *n_query, int32_t fill, const int32_t *lut, int L, const int32_t *dst, int64_t out_stride,
+                 int32_t *out, int32_t *err, pn2_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

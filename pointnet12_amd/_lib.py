@@ -110,6 +110,8 @@ SIGNATURES = {
     "pn2_depth_resolve": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "pn2_scan_filter_workspace_bytes": (_i64, [_i, _i64]),
     "pn2_scan_filter": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pn2_knn": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "pn2_knn_vote": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _i, _vp, _i, _vp, _i64, _vp, _vp, _vp]),
 }
 
 
@@ -119,6 +121,8 @@ PN2_OK_SPLIT = 1                 # pn2_conv1x1_bwd_pair: done as two launches
 DWX_REPLICAS = 32        # PN2_DWX_REPLICAS of include/pn2.h
 SCAN_TILE = 1024         # PN2_SCAN_TILE of include/pn2.h: rows per workgroup of pn2_scan_filter
 SCAN_ERR_CLASS, SCAN_ERR_ROWS = 1, 2     # PN2_SCAN_ERR_* of include/pn2.h
+KNN_MAX_K = 32           # pn2_knn / pn2_knn_vote: larger K is PN2_EUNSUPPORTED
+KNN_ERR_LABEL, KNN_ERR_DST = 1, 2        # the err bits of pn2_knn_vote
 
 
 class BnLazy(ctypes.Structure):

@@ -7,14 +7,10 @@
 //                  d = ((-2*dot) + n(query)) + n(candidate)
 // so every fused step below is an explicit __builtin_fmaf and nothing else may contract.
 #include "pn2_common.h"
+#include "pair_dist.h"                    // sq_norm3, pair_dist (shared with knn.hip)
 #include <stdlib.h>
 
 namespace {
-
-__device__ __forceinline__ float sq_norm3(float x, float y, float z) {
-    float xx = x * x, yy = y * y, zz = z * z;
-    return (xx + yy) + zz;
-}
 
 // min of two non-NaN floats as ONE v_min_f32: __builtin_fminf adds a canonicalising v_max_f32 x, x per operand in IEEE
 // mode, and the FPS iteration is bound by its instruction count.
@@ -22,17 +18,6 @@ __device__ __forceinline__ float min_raw(float a, float b) {
     float r;
     asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
-}
-
-__device__ __forceinline__ float pair_dist(float qx, float qy, float qz, float nq, float px, float py, float pz,
-                                           float np) {
-    float dot = qx * px;
-    dot = __builtin_fmaf(qy, py, dot);
-    dot = __builtin_fmaf(qz, pz, dot);
-    float d = -2.0f * dot;
-    d = d + nq;
-    d = d + np;
-    return d;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -10,7 +10,9 @@ everything per batch happens on the device (loader.prepare_batch).
 ``ScanFilter`` / ``read_scan_device`` / ``load_scans(ingest="device")`` do the same five steps on the device
 (``pn2_scan_filter``, csrc/scan.hip): the raw ``.bin`` / ``.label`` words are uploaded as they are, and the kept rows,
 their classes, their row numbers and the kept COUNT stay in device memory, so a frame path or a live feed needs no host
-pass.  The device rule is the one of include/pn2.h; it differs from ``in_view`` in one place only: the two angles are
+pass.  ``inverse_label_lut`` / ``write_labels`` go the other way: predicted training classes back to the dataset's raw
+ids, and those into a ``.label`` file (``kitti_view.FrameSegmenter.label_scan`` produces them for every row of a scan).
+The device rule is the one of include/pn2.h; it differs from ``in_view`` in one place only: the two angles are
 fp64 ``atan2`` values rounded to float32, where numpy's float32 ``arctan2`` is a few ulp off the correctly rounded value
 (and differs between numpy builds), so a point within a few float32 steps of a field-of-view border may fall on the
 other side (tests/scan_filter_ref.py quantifies it).
@@ -196,6 +198,34 @@ class ScanFilter:
             raise KeyError("a raw class is missing from the learning map")
         if flag & _lib.SCAN_ERR_ROWS:
             raise ValueError("ScanFilter: a row_count is above max_rows")
+
+
+def inverse_label_lut(learning_map_inv, device="cuda"):
+    """int32 device table ``lut[c] = learning_map_inv[c + 1]`` for the training classes ``c = 0 .. K-1`` the network predicts:
+    ``Semantic_KITTI_Utils.get`` drops training class 0 and shifts the others down by one (kitti_utils.py:215-219), and this
+    undoes both -- predicted class ``c`` is the dataset's raw id ``learning_map_inv[c + 1]``.  ``learning_map_inv``: the block of
+    that name of the dataset's ``semantic-kitti.yaml`` (training class -> raw id; its entry 0 is "unlabeled")."""
+    inv = {int(k): int(v) for k, v in learning_map_inv.items()}
+    ids = sorted(i for i in inv if i != 0)
+    if not ids or ids != list(range(1, len(ids) + 1)):
+        raise ValueError("learning_map_inv must name the training classes 1..K")
+    if any(not 0 <= inv[i] <= 0xFFFF for i in ids):
+        raise ValueError("learning_map_inv: a raw id does not fit the 16 semantic bits of a .label word")
+    return torch.from_numpy(np.array([inv[i] for i in ids], np.int32)).to(torch.device(device))
+
+
+def write_labels(fn, labels):
+    """Write per-point semantic ids in the dataset's ``.label`` format: one little-endian uint32 word per point, the semantic
+    id in the low 16 bits and instance 0 in the high 16 (``np.fromfile(fn, np.uint32) & 0xFFFF`` gives the ids back).
+    ``labels``: an integer array or tensor (either side) of raw ids in 0 .. 65535; a device tensor is read back here."""
+    if isinstance(labels, torch.Tensor):
+        labels = labels.detach().cpu().numpy()
+    ids = np.asarray(labels).reshape(-1)
+    if ids.dtype.kind not in "iu":
+        raise ValueError("write_labels: labels must be integers (got %s)" % ids.dtype)
+    if ids.size and (int(ids.min()) < 0 or int(ids.max()) > 0xFFFF):
+        raise ValueError("write_labels: a semantic id lies outside 0 .. 65535")
+    ids.astype("<u4").tofile(fn)
 
 
 def _upload_words(words, device):

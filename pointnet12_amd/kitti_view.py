@@ -531,6 +531,9 @@ class FrameSegmenter:
     no colour or a ``choice`` lay outside the scan.  ``render(log_probs, raw_rows, points)`` is the post-network part alone: it allocates nothing, so it can be
     captured in a graph.
 
+    ``frame_raw`` starts from the RAW scan (``kitti.ScanFilter`` on the device); ``label_scan`` is ``frame_raw`` plus a label for
+    every row of the scan (the k nearest drawn rows vote: ``pointnet_util.propagate_labels``), for ``kitti.write_labels``.
+
     ``camera`` (a ``PinholeCamera``): ``render`` then also draws the 3-D ego view of the un-normalised points (pcdvis.py:143,
     ``render_points`` with ``point_size`` on ``ego_background``, a colour triple) into ``ego_view`` uint8
     ``[camera.height, camera.width, 3]``, and ``frame`` returns it under ``"ego_view"``.  Without a camera there is no such key, buffer or launch."""
@@ -716,4 +719,36 @@ class FrameSegmenter:
                "pn2_gather_rows")
         out = self._finish(normed, background)
         out.update({"count": count, "labels": labels, "index": index})
+        return out
+
+    def label_scan(self, raw_scan, raw_label=None, scan_filter=None, rng="numpy", k=5, max_dist=1.0, lut=None, background=None,
+                   choice=None, max_rows=None):
+        """``frame_raw``, then a label for EVERY row of the raw scan.  The network labels ``npoints`` rows drawn with
+        replacement (about ``exp(-npoints / count)`` of the kept rows are never drawn); here each kept row takes the majority
+        label of its ``k`` nearest drawn rows (``pointnet_util.propagate_labels``: queries = the kept rows' xyz with the
+        device-side count, candidates = ``raw_rows[:, :3]`` carrying ``pred``, un-normalised, so ``max_dist`` is in METRES;
+        ``max_dist=None``: no cut-off) and is written at its raw row (the filter's ``index``).  The result, ``"scan_labels"`` in
+        the returned dict, is int32 ``[M]``: ``lut[class]`` (``lut``: ``kitti.inverse_label_lut``, the dataset's raw ids; None: the
+        predicted class itself) for the kept rows, 0 -- "unlabeled" in SemanticKITTI -- for the rows the filter dropped and
+        for a kept row with no drawn row within ``max_dist``.  ``kitti.write_labels`` writes it as a ``.label`` file.
+
+        A row drawn several times is a candidate several times and votes once per copy: deliberate, the copies are the
+        draw's weights.  With a device generator nothing is read back.  A predicted class outside ``lut`` gives 0 and sets
+        ``error_flag``."""
+        from . import pointnet_util as U
+        out = self.frame_raw(raw_scan, raw_label, scan_filter, rng, background, choice, max_rows)
+        held = self._raw_state
+        rows, n, M = held["rows"], self.npoints, int(raw_scan.shape[0])
+        k = int(k)
+        work = held.get("knn")
+        if work is None or work[0] != (rows, k):
+            dev = self.device
+            work = held["knn"] = ((rows, k), torch.empty(rows, k, device=dev, dtype=torch.int64),
+                                  torch.empty(rows, k, device=dev, dtype=torch.float32), torch.empty(rows, device=dev, dtype=torch.int32))
+        _, idx, dist, scan_labels = work
+        scan_labels.zero_()
+        U.propagate_labels(held["out"].points[:, :3].contiguous().view(1, rows, 3), self.raw_rows[:, :3].contiguous().view(1, n, 3),
+                           self.pred.view(1, n), k=k, max_dist=max_dist, fill=0, lut=lut, dst=out["index"], out=scan_labels,
+                           n_query=out["count"], err=self.error_flag, work=(idx, dist))
+        out["scan_labels"] = scan_labels[:M]
         return out

@@ -422,6 +422,112 @@ def query_ball_point(radius, nsample, xyz, new_xyz):
     return _taped(lambda: out)
 
 
+def knn_point(nsample, xyz, new_xyz, return_dist=False):
+    """The ``nsample`` nearest points of ``xyz`` [B,N,3] for every centre of ``new_xyz`` [B,S,3] -> int64 [B,S,nsample]
+    (``return_dist``: also their squared distances, float32, the numbers of ``square_distance``): the ``knn_point`` of the
+    code bases derived from the same ``pointnet_util.py``, in the argument order of ``query_ball_point``.  Ascending
+    distance; equal distances in ascending index (the first ``nsample`` of a stable sort -- the forks' ``topk`` leaves
+    the order of ties undefined).  ``pn2_knn``; ``nsample > N`` or ``nsample > 32`` raises ``RuntimeError``."""
+    if _tape is not None and _tape.mode == "replay":
+        v = _taped(None)
+        return v if return_dist else v[0]
+    xyz, new_xyz = _gpu_f32(xyz, "xyz"), _gpu_f32(new_xyz, "new_xyz")
+    B, N, _ = xyz.shape
+    S = new_xyz.shape[1]
+    nsample = int(nsample)
+    if nsample < 1 or nsample > N:
+        raise RuntimeError("knn_point: nsample (%d) must lie in [1, N = %d]" % (nsample, N))
+    if nsample > _lib.KNN_MAX_K:
+        raise RuntimeError("knn_point: nsample (%d) > %d is not supported (there is no fallback path)" % (nsample, _lib.KNN_MAX_K))
+    dst = _dest(((B, S, nsample), torch.int64), ((B, S, nsample), torch.float32))
+    if dst:
+        idx, dist = dst
+    else:
+        idx = torch.empty(B, S, nsample, device=xyz.device, dtype=torch.int64)
+        dist = torch.empty(B, S, nsample, device=xyz.device, dtype=torch.float32)
+    _check(_lib.load().pn2_knn(_p(new_xyz), _p(xyz), B, S, N, nsample, None, None, _p(idx), _p(dist), _lib.stream()), "pn2_knn")
+    v = _taped(lambda: (idx, dist))
+    return v if return_dist else v[0]
+
+
+def _i64_counts(n, B, device, what):
+    """None, or the device int64 [B] tensor of a per-cloud count (``ScanFilter.filter``'s kept count is one already)."""
+    if n is None:
+        return None
+    if not isinstance(n, torch.Tensor):
+        n = torch.as_tensor(n, dtype=torch.int64).reshape(-1).to(device)
+    if not n.is_cuda or n.dtype != torch.int64 or n.numel() != B:
+        raise ValueError("propagate_labels: %s must hold B = %d int64 counts on the GPU" % (what, B))
+    return n.reshape(-1).contiguous()
+
+
+def propagate_labels(query_xyz, cand_xyz, cand_labels, k=5, max_dist=None, fill=-1, lut=None, dst=None, out=None, n_query=None,
+                     n_cand=None, err=None, work=None):
+    """Every query point takes the majority label of its ``k`` nearest labelled points: ``pn2_knn`` then ``pn2_knn_vote``.
+
+    ``query_xyz`` [B,N,3], ``cand_xyz`` [B,M,3] float32, ``cand_labels`` int64 [B,M] -> int32 [B,N] (or ``out``).  A neighbour
+    votes if it exists and lies within ``max_dist`` (a DISTANCE, in the units of the coordinates; the kernel compares the
+    squared distance with ``float32(max_dist ** 2)``; None: no cut-off).  The label with the most votes wins; among equals the
+    one whose nearest voter is nearest; no voter: ``fill``.  ``lut`` (int32 [L] on the device): the result is ``lut[label]``, a
+    winning label outside it gives ``fill`` and sets bit 1 of ``err``.  ``dst`` (int32 [B,N]): row n is written at
+    ``out[b, dst[b, n]]`` (``out`` may then be wider than N; an entry outside it is skipped and sets bit 2 of ``err``).
+    ``n_query`` / ``n_cand``: device int64 [B] counts (or host integers), only that many leading queries are labelled and
+    candidates searched; the other rows of ``out`` keep what they held.  ``err``: a zeroed device int32 tensor; nothing is read
+    back here.
+
+    DUPLICATE CANDIDATES VOTE ONCE EACH: a cloud drawn with replacement holds some points several times, and each copy is a
+    candidate of its own -- deliberately: the copies are the draw's weights.
+
+    With ``out`` the call allocates only the [B,N,k] neighbour scratch; ``work = (idx int64 [B,N,k], dist float32 [B,N,k])``
+    supplies that too, and a captured call then allocates nothing."""
+    query_xyz, cand_xyz = _gpu_f32(query_xyz, "query_xyz"), _gpu_f32(cand_xyz, "cand_xyz")
+    if query_xyz.dim() != 3 or cand_xyz.dim() != 3 or query_xyz.shape[2] != 3 or cand_xyz.shape[2] != 3 or \
+            query_xyz.shape[0] != cand_xyz.shape[0]:
+        raise RuntimeError("propagate_labels: query_xyz [B,N,3] and cand_xyz [B,M,3] are needed")
+    B, N, _ = query_xyz.shape
+    M = cand_xyz.shape[1]
+    dev = query_xyz.device
+    k = int(k)
+    if k < 1 or k > M:
+        raise RuntimeError("propagate_labels: k (%d) must lie in [1, M = %d]" % (k, M))
+    if k > _lib.KNN_MAX_K:
+        raise RuntimeError("propagate_labels: k (%d) > %d is not supported (there is no fallback path)" % (k, _lib.KNN_MAX_K))
+    if not cand_labels.is_cuda or cand_labels.dtype != torch.int64 or cand_labels.numel() != B * M:
+        raise ValueError("propagate_labels: cand_labels must be int64 [B, M] on the GPU")
+    cand_labels = cand_labels.contiguous()
+    if lut is not None and (not lut.is_cuda or lut.dtype != torch.int32 or lut.dim() != 1 or not lut.is_contiguous() or lut.numel() < 1):
+        raise ValueError("propagate_labels: lut must be a contiguous int32 [L] tensor on the GPU")
+    if dst is not None and (not dst.is_cuda or dst.dtype != torch.int32 or dst.numel() < B * N or not dst.is_contiguous()):
+        raise ValueError("propagate_labels: dst must be a contiguous int32 tensor of at least B * N entries on the GPU")
+    if out is None:
+        if dst is not None:
+            raise ValueError("propagate_labels: dst needs an out to scatter into")
+        out = torch.full((B, N), int(fill), device=dev, dtype=torch.int32) if n_query is not None else \
+            torch.empty(B, N, device=dev, dtype=torch.int32)
+    elif not out.is_cuda or out.dtype != torch.int32 or not out.is_contiguous() or out.numel() % B != 0 or \
+            (dst is None and out.numel() // B < N):
+        raise ValueError("propagate_labels: out must be a contiguous int32 tensor of B equal rows (at least N entries each "
+                         "without a dst) on the GPU")
+    stride = out.numel() // B
+    if work is None:
+        idx = torch.empty(B, N, k, device=dev, dtype=torch.int64)
+        dist = torch.empty(B, N, k, device=dev, dtype=torch.float32)
+    else:
+        idx, dist = work
+        if idx.dtype != torch.int64 or dist.dtype != torch.float32 or idx.numel() < B * N * k or dist.numel() < B * N * k or \
+                not idx.is_contiguous() or not dist.is_contiguous() or idx.device != dev or dist.device != dev:
+            raise ValueError("propagate_labels: work must be (int64, float32) contiguous tensors of at least B * N * k entries")
+    if err is not None and (not err.is_cuda or err.dtype != torch.int32 or err.numel() < 1):
+        raise ValueError("propagate_labels: err must be a device int32 tensor")
+    n_query, n_cand = _i64_counts(n_query, B, dev, "n_query"), _i64_counts(n_cand, B, dev, "n_cand")
+    max_d2 = float("inf") if max_dist is None else float(np.float32(float(max_dist) ** 2))
+    lib, st = _lib.load(), _lib.stream()
+    _check(lib.pn2_knn(_p(query_xyz), _p(cand_xyz), B, N, M, k, _p(n_query), _p(n_cand), _p(idx), _p(dist), st), "pn2_knn")
+    _check(lib.pn2_knn_vote(_p(idx), _p(dist), _p(cand_labels), B, N, M, k, max_d2, _p(n_query), int(fill), _p(lut),
+                            0 if lut is None else int(lut.numel()), _p(dst), stride, _p(out), _p(err), st), "pn2_knn_vote")
+    return out
+
+
 def three_nn(xyz1, xyz2):
     """3 nearest of xyz2 [B,S,3] for every point of xyz1 [B,N,3] -> (idx int64, raw dist, weights), each [B,N,3].
 
@@ -1278,13 +1384,14 @@ def _channel_last(t, name):
     return r
 
 
-def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False):
-    """pointnet_util.py:110-137: -> new_xyz [B,S,3], new_points [B,S,K,3+D] (xyz first)."""
+def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False, knn=False):
+    """pointnet_util.py:110-137: -> new_xyz [B,S,3], new_points [B,S,K,3+D] (xyz first).  ``knn=True``: the groups are the
+    ``nsample`` nearest points (``knn_point``) instead of the ball query; ``radius`` is ignored."""
     xyz = _gpu_f32(xyz, "xyz")
     B, N, C = xyz.shape
     fps_idx = farthest_point_sample(xyz, npoint)
     new_xyz = index_points(xyz, fps_idx, _checked=False)
-    idx = query_ball_point(radius, nsample, xyz, new_xyz)
+    idx = knn_point(nsample, xyz, new_xyz) if knn else query_ball_point(radius, nsample, xyz, new_xyz)
     grouped_xyz = index_points(xyz, idx)
     pts = None if points is None else _gpu_f32(points, "points")
     rows = _Group.apply(xyz, pts, new_xyz, idx, npoint, nsample, True)
@@ -1309,10 +1416,12 @@ def sample_and_group_all(xyz, points):
 # --------------------------------------------------------------------------------------- modules
 
 class PointNetSetAbstraction(nn.Module):
-    """Drop-in for model/pointnet_util.py:160-201 (same constructor, forward and state_dict)."""
+    """Drop-in for model/pointnet_util.py:160-201 (same constructor, forward and state_dict).  ``knn=True``: the groups are
+    the ``nsample`` nearest points (``knn_point``) instead of the ball query and ``radius`` is ignored; same ``state_dict``."""
 
-    def __init__(self, npoint, radius, nsample, in_channel, mlp, group_all):
+    def __init__(self, npoint, radius, nsample, in_channel, mlp, group_all, knn=False):
         super().__init__()
+        self.knn = bool(knn)
         self.npoint = npoint
         self.radius = radius
         self.nsample = nsample
@@ -1342,7 +1451,7 @@ class PointNetSetAbstraction(nn.Module):
             S, K = self.npoint, self.nsample
             fps_idx = farthest_point_sample(xyz, S, fps_start)
             new_xyz = _sampled_centres(xyz, fps_idx)
-            idx = query_ball_point(self.radius, K, xyz, new_xyz)
+            idx = knn_point(K, xyz, new_xyz) if self.knn else query_ball_point(self.radius, K, xyz, new_xyz)
             inv = _group_inverse(idx, N, 0 if pts is None else pts.shape[2], len(self.mlp_convs), self.training)
             rows = None
         c_in = 3 + (0 if pts is None else pts.shape[2])

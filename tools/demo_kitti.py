@@ -2,7 +2,7 @@
 """One frame of the reference's KITTI demo (``python pcdvis.py``) on the HIP library: scan -> labels -> pixels -> two images,
 three with ``--ego``.
 
-    python tools/demo_kitti.py [--out DIR] [--npoints 25000] [--seed 0] [--merge] [--time] [--raw] [--ego CAMERA.json [--render-option FILE.json]]
+    python tools/demo_kitti.py [--out DIR] [--npoints 25000] [--seed 0] [--merge] [--time] [--raw [--labels-out FILE]] [--ego CAMERA.json [--render-option FILE.json]]
     python tools/demo_kitti.py --root $KITTI_ROOT --part 01 --index 0 --calib DIR --config semantic-kitti.yaml [--checkpoint CKPT]
 
 Without ``--root`` the scan is synthetic (``synthetic.kitti_cloud``, un-normalised back to metres), the calibration is the one
@@ -19,6 +19,9 @@ file, the reference's ``config/render_option.json``) sets its point size and bac
 ``--raw`` feeds the RAW scan through ``FrameSegmenter.frame_raw``: the class map, the class drop, the view filter and the
 compaction run on the device (``kitti.ScanFilter``, ``pn2_scan_filter``) and the kept count never leaves it; the synthetic scan has
 no label file (a live feed), a dataset scan goes in with its ``.label`` words.  The choice is then drawn on the device.
+``--labels-out FILE`` (with ``--raw``, without ``--merge``) goes through ``FrameSegmenter.label_scan`` instead: every row of the
+raw scan takes the majority label of its 5 nearest drawn rows within 1 m, mapped back to the dataset's raw ids
+(``kitti.inverse_label_lut``), rows the filter dropped are 0, and FILE is written in the dataset's ``.label`` format.
 
 ``--time`` prints one JSON line with medians of 20 (device work included, host clock) for the post-network stages --
 predict + project + both images (``render_ms``), and the same as a captured graph (``render_graph_ms``) -- and beside them, in
@@ -195,6 +198,7 @@ def main():
     ap.add_argument("--merge", action="store_true", help="predict over the demo's merged classes")
     ap.add_argument("--time", action="store_true")
     ap.add_argument("--raw", action="store_true", help="feed the raw scan through frame_raw: filter and compaction on the device")
+    ap.add_argument("--labels-out", metavar="FILE", help="with --raw: label every row of the scan (label_scan) and write a .label file")
     ap.add_argument("--ego", metavar="CAMERA.json", help="also draw the 3-D ego view through this open3d PinholeCameraParameters file")
     ap.add_argument("--render-option", metavar="FILE.json", help="open3d RenderOption file: the ego view's point size and background colour")
     ap.add_argument("--root")
@@ -224,6 +228,8 @@ def main():
     size = (375, 1242) if frame is None else frame.shape[:2]
     if args.render_option and not args.ego:
         ap.error("--render-option needs --ego")
+    if args.labels_out and (not args.raw or args.merge):
+        ap.error("--labels-out needs --raw and does not go with --merge (merged classes have no raw id)")
     camera = V.PinholeCamera.from_json(args.ego) if args.ego else None
     option = V.RenderOption.from_json(args.render_option) if args.render_option else V.RenderOption()
     seg = V.FrameSegmenter(model, calib, colors if groups is None else groups.colors, npoints=args.npoints, image_size=size, groups=groups,
@@ -233,7 +239,13 @@ def main():
         scan_filter = kitti.ScanFilter(cfg["learning_map"] if words is not None else None, "inview")
         gen = torch.Generator(device="cuda")
         gen.manual_seed(args.seed)
-        out = seg.frame_raw(scan, words, scan_filter=scan_filter, rng=gen, background=frame)
+        if args.labels_out:
+            out = seg.label_scan(scan, words, scan_filter=scan_filter, rng=gen, lut=kitti.inverse_label_lut(cfg["learning_map_inv"]),
+                                 background=frame)
+            kitti.write_labels(args.labels_out, out["scan_labels"])
+            print("labelled %d of %d rows; wrote %s" % (int((out["scan_labels"] != 0).sum()), len(scan), args.labels_out))
+        else:
+            out = seg.frame_raw(scan, words, scan_filter=scan_filter, rng=gen, background=frame)
         print("raw scan of %d rows, %d kept by the device filter; filter error flag %d"
               % (len(scan), int(out["count"].item()), int(scan_filter.error_flag.item())))
     else:
