@@ -828,6 +828,53 @@ int pn2_knn_vote(const int64_t *idx, const float *dist, const int64_t *cand_labe
                  const int64_t *n_query, int32_t fill, const int32_t *lut, int L, const int32_t *dst, int64_t out_stride,
                  int32_t *out, int32_t *err, pn2_stream_t stream);
 
+/* ---- voxel-grid downsampling (csrc/voxel.hip), added within ABI 15 (purely additive: no version change) ------------------------------
+ * One row per occupied cell of a regular grid, for a batch of B clouds that lie back to back in device memory (the conventions
+ * of pn2_scan_filter: device-side row_begin / row_count / out_begin, a host bound max_rows that sizes the grid of workgroups and
+ * the workspace only).  At most six plain launches on the caller's stream; no host synchronisation, no allocation, no thread
+ * waits for another thread's write.
+ *   pts        [rows, ld] fp32, 3 <= ld <= 16, columns 0..2 = x, y, z; cloud b is rows [row_begin[b], row_begin[b] + row_count[b]).
+ *   labels_in  int32[rows] or NULL (out_labels then holds zeros).
+ *   max_rows   host upper bound of every row_count[b], 0 <= max_rows <= PN2_VOXEL_MAX_ROWS (2^29 rows per cloud).  Tiles of
+ *              PN2_VOXEL_TILE rows that start at or beyond the device-side row_count[b] do nothing, so a captured launch stays
+ *              valid when the count changes.  A negative row_count counts as 0.
+ *   origin, voxel   HOST double[3] each: voxel[a] finite and > 0, origin[a] finite (else PN2_EINVAL, nothing launched).
+ *   out_begin  int64[B] (device): where cloud b's voxels start in the outputs.  Outputs must not alias inputs.
+ * THE RULE, per row and per axis a:
+ *   q_a = floor(((double)p_a - origin[a]) / voxel[a])      IEEE fp64, each operation rounded on its own.
+ *   The row is VALID iff q_a >= -1048576.0 && q_a < 1048576.0 for all three axes, compared in fp64 before any conversion to an
+ *   integer (NaN and +-inf fail).  An invalid row is dropped, gets inverse = -1 and sets PN2_VOXEL_ERR_RANGE.  -0.0 lies in cell 0.
+ *   key = (q_x + 2^20) << 42 | (q_y + 2^20) << 21 | (q_z + 2^20): three biased 21-bit integers in 63 bits.
+ *   Valid rows of ONE cloud with equal keys form a voxel (clouds never share voxels, even at equal coordinates).  A voxel's
+ *   representative is its row with the lowest row number inside the cloud.  The representatives come in ascending row number:
+ *   a STABLE compaction, np.sort(np.unique(key, return_index=True)[1]).
+ * Outputs, for rank r = 0 .. out_count[b] - 1 of cloud b at position out_begin[b] + r (each may be NULL except out_count):
+ *   out_points fp32 [., ld]  the representative's row, all ld floats bit for bit;   out_labels int32  its label;
+ *   out_index  int32         its row inside the cloud, strictly increasing;         n_points   int32  valid rows in the voxel;
+ *   inverse    int32[rows]   inverse[row_begin[b] + i] = the rank, inside cloud b, of row i's voxel (-1: invalid row); rows outside
+ *                            the clouds are not written;                            out_count  int64[B]  the number of voxels.
+ *   Everything is the same from run to run, byte for byte: a lock-free hash table driven by integer atomics (64-bit
+ *   compare-and-swap on the key, minimum of the row number, sum of the population) decides WHICH rows stand for their voxels,
+ *   prefix sums decide WHERE they go; neither the hash function nor the probe order shows in any output.
+ * err (device int, caller zeroes, may be NULL) receives
+ *   PN2_VOXEL_ERR_RANGE  a row with a non-finite coordinate or a cell outside [-2^20, 2^20): dropped;
+ *   PN2_VOXEL_ERR_ROWS   a row_count[b] above max_rows: the rows beyond are ignored.
+ * workspace: pn2_voxel_grid_workspace_bytes(B, max_rows) bytes of device memory, 16-byte aligned; it may hold anything on entry
+ * and its content need not be kept (per cloud: a table of the power of two >= 2 * max_rows slots of 16 bytes, and 5 bytes per row).
+ * PN2_EINVAL without a launch for a null pts / row_begin / row_count / origin / voxel / out_begin / out_count / workspace, B < 1 or
+ * B > 65535, max_rows < 0 or > PN2_VOXEL_MAX_ROWS, ld outside 3..16, pts / out_points not 4-byte or workspace not 16-byte aligned;
+ * pn2_voxel_grid_workspace_bytes returns PN2_EINVAL for such B / max_rows.  (ld == 4 with 16-byte aligned pts and out_points
+ * moves rows as 16-byte words.) */
+#define PN2_VOXEL_TILE 1024
+#define PN2_VOXEL_MAX_ROWS ((int64_t)1 << 29)
+#define PN2_VOXEL_ERR_RANGE 1
+#define PN2_VOXEL_ERR_ROWS 2
+int64_t pn2_voxel_grid_workspace_bytes(int B, int64_t max_rows);
+int pn2_voxel_grid(const float *pts, int ld, const int32_t *labels_in, const int64_t *row_begin, const int64_t *row_count, int B,
+                   int64_t max_rows, const double *origin, const double *voxel, const int64_t *out_begin, float *out_points,
+                   int32_t *out_labels, int32_t *out_index, int64_t *out_count, int32_t *inverse, int32_t *n_points, int *err,
+                   void *workspace, pn2_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -246,8 +246,9 @@ def read_scan_device(fn_velo, fn_label, scan_filter):
     return pts[:m], (None if labels is None else labels[:m])
 
 
-def _ingest_chunk(chunk, scan_filter):
-    """One batched launch over the scans of ``chunk`` ([(points, words)], host arrays): (points, labels, counts) packed."""
+def _ingest_chunk(chunk, scan_filter, voxel=None):
+    """One batched launch over the scans of ``chunk`` ([(points, words)], host arrays): (points, labels, counts) packed.  With a
+    ``voxel.VoxelGrid`` the kept rows of every scan go through one batched ``pn2_voxel_grid`` launch before the pack."""
     dev = scan_filter.device
     counts = np.array([p.shape[0] for p, _ in chunk], np.int64)
     begins = np.cumsum(counts) - counts
@@ -257,8 +258,12 @@ def _ingest_chunk(chunk, scan_filter):
     lab = _upload_words(np.concatenate([w for _, w in chunk], 0), dev)
     begin_dev = torch.from_numpy(begins).to(dev)
     pts, labels, _, kept = scan_filter.filter(raw, lab, begin_dev, torch.from_numpy(counts).to(dev), int(counts.max()))
+    if voxel is not None:
+        pts, labels, _, kept, _, _ = voxel.downsample(pts, labels, begin_dev, kept, int(counts.max()))
     kept = kept.cpu().numpy()                                        # the one read-back of the chunk
     scan_filter.check()
+    if voxel is not None:
+        voxel.check()
     total = int(kept.sum())
     out_p = torch.empty(total, 4, device=dev, dtype=torch.float32)
     out_l = torch.empty(total, device=dev, dtype=torch.int32)
@@ -270,15 +275,18 @@ def _ingest_chunk(chunk, scan_filter):
     return out_p, out_l, kept
 
 
-def load_scans(pairs, learning_map, subset="inview", device="cuda", ingest="host", chunk_rows=1 << 22):
+def load_scans(pairs, learning_map, subset="inview", device="cuda", ingest="host", chunk_rows=1 << 22, voxel=None):
     """``ScanStore`` over the ``(bin_path, label_path)`` pairs (a sequence's scans, e.g. every second one for
     training as SemKITTI_Loader.py:62-66 selects them).  ``ingest="host"``: every scan through ``read_scan`` (numpy).
     ``ingest="device"``: the raw files are uploaded in chunks of about ``chunk_rows`` rows, each chunk goes through one
     batched ``pn2_scan_filter`` launch, its kept counts are read back once and the kept runs are packed into the store; the
     store equals the host one except where a point lies within a few float32 steps of a field-of-view border (module
-    docstring)."""
+    docstring).  ``voxel`` (a ``voxel.VoxelGrid``, ``ingest="device"`` only): every scan is downsampled to one row per occupied
+    cell after the filter and before it enters the store (``pn2_voxel_grid``, one batched launch per chunk)."""
     if ingest not in ("host", "device"):
         raise ValueError('load_scans: ingest must be "host" or "device"')
+    if voxel is not None and ingest != "device":
+        raise ValueError('load_scans: a voxel grid needs ingest="device"')
     if ingest == "device":
         pairs = list(pairs)
         if not pairs:
@@ -289,7 +297,7 @@ def load_scans(pairs, learning_map, subset="inview", device="cuda", ingest="host
             chunk.append(_read_files(fn_velo, fn_label))
             rows += chunk[-1][0].shape[0]
             if rows >= chunk_rows or k == len(pairs) - 1:
-                parts.append(_ingest_chunk(chunk, scan_filter))
+                parts.append(_ingest_chunk(chunk, scan_filter, voxel))
                 chunk, rows = [], 0
         return loader.ScanStore.from_device(torch.cat([p for p, _, _ in parts]), torch.cat([l for _, l, _ in parts]),
                                             np.concatenate([c for _, _, c in parts]))

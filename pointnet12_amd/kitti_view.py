@@ -571,14 +571,21 @@ class FrameSegmenter:
         """``np.random.choice(length, npoints, replace=True)`` (pcdvis.py:121: a seeded numpy run draws what the reference
         draws), or the same distribution from a device ``torch.Generator``.  With a generator ``length`` may be a device int64
         tensor of one element (``ScanFilter.filter``'s count): the draw is ``min((u * length).long(), length - 1)`` on the device,
-        nothing is read back, and a length of 0 gives -1 everywhere."""
+        nothing is read back, and a length of 0 gives -1 everywhere.  ``rng="cover"`` draws nothing: ``choice[i] = i % length``,
+        computed on the device (``length`` an int or such a tensor; 0 gives -1 everywhere) -- with ``length <= npoints`` every row
+        is taken at least once, which is what a voxel-grid subsample (``frame_raw(voxel=...)``) wants."""
+        if isinstance(rng, str) and rng == "cover":
+            i = torch.arange(self.npoints, device=self.device, dtype=torch.int64)
+            if isinstance(length, torch.Tensor):
+                return torch.where(length > 0, torch.remainder(i, length.clamp(min=1)), -1)
+            return torch.remainder(i, length) if length > 0 else torch.full_like(i, -1)
         if isinstance(rng, torch.Generator):
             u = torch.rand(self.npoints, device=self.device, dtype=torch.float64, generator=rng)
             if isinstance(length, torch.Tensor):
                 return torch.minimum((u * length).long(), length - 1)
             return torch.clamp((u * length).long(), max=length - 1)
         if rng != "numpy":
-            raise ValueError('FrameSegmenter: rng must be "numpy" or a device torch.Generator')
+            raise ValueError('FrameSegmenter: rng must be "numpy", "cover" or a device torch.Generator')
         return torch.from_numpy(np.random.choice(int(length), self.npoints, replace=True).astype(np.int64)).to(self.device)
 
     def render(self, log_probs, raw_rows, points, background=None):
@@ -657,7 +664,8 @@ class FrameSegmenter:
             self._raw_state = held
         return held
 
-    def frame_raw(self, raw_scan, raw_label=None, scan_filter=None, rng="numpy", background=None, choice=None, max_rows=None):
+    def frame_raw(self, raw_scan, raw_label=None, scan_filter=None, rng="numpy", background=None, choice=None, max_rows=None,
+                  voxel=None):
         """``frame`` for a RAW scan: ``raw_scan`` float32 ``[M, 4]`` (the ``.bin`` rows) and, if there is one, ``raw_label`` ``[M]``
         (the ``.label`` words, uint32 / int32; None: a live feed), as numpy arrays or tensors on either side.  ``scan_filter``: a
         ``kitti.ScanFilter`` (its class map, subset and ranges).  The stages are: upload into a static buffer of ``max_rows`` rows
@@ -674,7 +682,15 @@ class FrameSegmenter:
 
         A scan of which nothing survives the filter makes the device choice -1 everywhere: ``pn2_prepare_clouds`` flags that in
         ``error_flag`` (the frame then shows row 0 / zeros); with ``rng="numpy"`` it raises ``ValueError``, as ``frame`` does for
-        an empty scan.  A raw class outside the map or more rows than ``max_rows`` set ``scan_filter.error_flag``."""
+        an empty scan.  A raw class outside the map or more rows than ``max_rows`` set ``scan_filter.error_flag``.
+
+        ``voxel`` (a ``voxel.VoxelGrid``): the kept rows are downsampled to one row per occupied cell after the filter
+        (``pn2_voxel_grid``), and the choice, ``pn2_prepare_clouds`` and the row gather then read the DOWNSAMPLED rows: the choice is
+        drawn from the voxel count (on the device for a device generator and for ``rng="cover"``; ``rng="numpy"`` reads that one
+        count back), and an explicit ``choice`` names downsampled rows.  The result gains ``voxel_count`` (int64 ``[1]`` on the
+        device), ``voxel_index`` (int32: the RAW row of each voxel's representative, the grid's ``index`` composed with the
+        filter's; the first ``voxel_count`` entries mean something) and ``voxel_inverse`` (int32: for each KEPT row the rank of its
+        voxel, -1 for a row the grid dropped); ``count`` / ``labels`` / ``index`` stay the filter's."""
         lib = _lib.load()
         if scan_filter is None:
             raise ValueError("FrameSegmenter.frame_raw: a kitti.ScanFilter is needed")
@@ -699,11 +715,17 @@ class FrameSegmenter:
         held["count"].fill_(M)
         pts, labels, index, count = scan_filter.filter(held["raw"], held["words"] if raw_label is not None else None, held["begin"],
                                                        held["count"], held["rows"], out=held["out"])
+        src, src_count = pts, count
+        if voxel is not None:
+            vb = held.get("voxel")
+            if vb is None:
+                vb = held["voxel"] = voxel.buffers(held["rows"])
+            src, _, v_index, src_count, v_inverse, _ = voxel.downsample(pts, None, held["begin"], count, held["rows"], out=vb)
         if choice is None:
-            if isinstance(rng, torch.Generator):
-                choice = self.choice(count, rng)
+            if isinstance(rng, torch.Generator) or (isinstance(rng, str) and rng == "cover"):
+                choice = self.choice(src_count, rng)
             else:
-                kept = int(count.item())                             # the one read-back of the numpy draw
+                kept = int(src_count.item())                         # the one read-back of the numpy draw
                 if kept == 0:
                     raise ValueError("FrameSegmenter.frame_raw: nothing of the scan survives the filter")
                 choice = self.choice(kept, rng)
@@ -713,16 +735,20 @@ class FrameSegmenter:
         n = self.npoints
         normed = torch.empty(1, n, 4, device=self.device, dtype=torch.float32)
         # (a choice outside [0, count) sets error_flag and reads row 0: the count is the kernel's own, in device memory)
-        _check(lib.pn2_prepare_clouds(_p(pts), _p(held["begin"]), _p(count), None, None, None, _p(choice), 1, n, _p(normed), None,
+        _check(lib.pn2_prepare_clouds(_p(src), _p(held["begin"]), _p(src_count), None, None, None, _p(choice), 1, n, _p(normed), None,
                                       _p(self.error_flag), _lib.stream()), "pn2_prepare_clouds")
-        _check(lib.pn2_gather_rows(_p(pts), _p(choice), 1, held["rows"], 4, n, _p(self.raw_rows), _p(self.error_flag), _lib.stream()),
+        _check(lib.pn2_gather_rows(_p(src), _p(choice), 1, held["rows"], 4, n, _p(self.raw_rows), _p(self.error_flag), _lib.stream()),
                "pn2_gather_rows")
         out = self._finish(normed, background)
         out.update({"count": count, "labels": labels, "index": index})
+        if voxel is not None:
+            # (entries beyond the voxel count are whatever the buffer held: clamped, so that the gather stays inside `index`)
+            raw_row = torch.gather(index, 0, v_index.long().clamp_(0, held["rows"] - 1))
+            out.update({"voxel_count": src_count, "voxel_index": raw_row, "voxel_inverse": v_inverse})
         return out
 
     def label_scan(self, raw_scan, raw_label=None, scan_filter=None, rng="numpy", k=5, max_dist=1.0, lut=None, background=None,
-                   choice=None, max_rows=None):
+                   choice=None, max_rows=None, voxel=None):
         """``frame_raw``, then a label for EVERY row of the raw scan.  The network labels ``npoints`` rows drawn with
         replacement (about ``exp(-npoints / count)`` of the kept rows are never drawn); here each kept row takes the majority
         label of its ``k`` nearest drawn rows (``pointnet_util.propagate_labels``: queries = the kept rows' xyz with the
@@ -734,9 +760,10 @@ class FrameSegmenter:
 
         A row drawn several times is a candidate several times and votes once per copy: deliberate, the copies are the
         draw's weights.  With a device generator nothing is read back.  A predicted class outside ``lut`` gives 0 and sets
-        ``error_flag``."""
+        ``error_flag``.  ``voxel``: as in ``frame_raw`` -- the network sees the downsampled rows, the queries remain ALL kept
+        rows, so the result means what it meant."""
         from . import pointnet_util as U
-        out = self.frame_raw(raw_scan, raw_label, scan_filter, rng, background, choice, max_rows)
+        out = self.frame_raw(raw_scan, raw_label, scan_filter, rng, background, choice, max_rows, voxel)
         held = self._raw_state
         rows, n, M = held["rows"], self.npoints, int(raw_scan.shape[0])
         k = int(k)

@@ -22,6 +22,8 @@ no label file (a live feed), a dataset scan goes in with its ``.label`` words.  
 ``--labels-out FILE`` (with ``--raw``, without ``--merge``) goes through ``FrameSegmenter.label_scan`` instead: every row of the
 raw scan takes the majority label of its 5 nearest drawn rows within 1 m, mapped back to the dataset's raw ids
 (``kitti.inverse_label_lut``), rows the filter dropped are 0, and FILE is written in the dataset's ``.label`` format.
+``--voxel SIZE`` (with ``--raw``) downsamples the kept rows to one row per occupied cell of SIZE metres before the choice
+(``voxel.VoxelGrid``, ``pn2_voxel_grid``), which is then drawn from the voxel count.
 
 ``--time`` prints one JSON line with medians of 20 (device work included, host clock) for the post-network stages --
 predict + project + both images (``render_ms``), and the same as a captured graph (``render_graph_ms``) -- and beside them, in
@@ -199,6 +201,7 @@ def main():
     ap.add_argument("--time", action="store_true")
     ap.add_argument("--raw", action="store_true", help="feed the raw scan through frame_raw: filter and compaction on the device")
     ap.add_argument("--labels-out", metavar="FILE", help="with --raw: label every row of the scan (label_scan) and write a .label file")
+    ap.add_argument("--voxel", type=float, metavar="SIZE", help="with --raw: voxel-grid downsample the kept rows at SIZE metres")
     ap.add_argument("--ego", metavar="CAMERA.json", help="also draw the 3-D ego view through this open3d PinholeCameraParameters file")
     ap.add_argument("--render-option", metavar="FILE.json", help="open3d RenderOption file: the ego view's point size and background colour")
     ap.add_argument("--root")
@@ -230,6 +233,8 @@ def main():
         ap.error("--render-option needs --ego")
     if args.labels_out and (not args.raw or args.merge):
         ap.error("--labels-out needs --raw and does not go with --merge (merged classes have no raw id)")
+    if args.voxel is not None and not args.raw:
+        ap.error("--voxel needs --raw")
     camera = V.PinholeCamera.from_json(args.ego) if args.ego else None
     option = V.RenderOption.from_json(args.render_option) if args.render_option else V.RenderOption()
     seg = V.FrameSegmenter(model, calib, colors if groups is None else groups.colors, npoints=args.npoints, image_size=size, groups=groups,
@@ -239,15 +244,21 @@ def main():
         scan_filter = kitti.ScanFilter(cfg["learning_map"] if words is not None else None, "inview")
         gen = torch.Generator(device="cuda")
         gen.manual_seed(args.seed)
+        grid = None
+        if args.voxel is not None:
+            from pointnet12_amd import voxel
+            grid = voxel.VoxelGrid(args.voxel)
         if args.labels_out:
             out = seg.label_scan(scan, words, scan_filter=scan_filter, rng=gen, lut=kitti.inverse_label_lut(cfg["learning_map_inv"]),
-                                 background=frame)
+                                 background=frame, voxel=grid)
             kitti.write_labels(args.labels_out, out["scan_labels"])
             print("labelled %d of %d rows; wrote %s" % (int((out["scan_labels"] != 0).sum()), len(scan), args.labels_out))
         else:
-            out = seg.frame_raw(scan, words, scan_filter=scan_filter, rng=gen, background=frame)
+            out = seg.frame_raw(scan, words, scan_filter=scan_filter, rng=gen, background=frame, voxel=grid)
         print("raw scan of %d rows, %d kept by the device filter; filter error flag %d"
               % (len(scan), int(out["count"].item()), int(scan_filter.error_flag.item())))
+        if grid is not None:
+            print("%d voxels of %g m; grid error flag %d" % (int(out["voxel_count"].item()), args.voxel, int(grid.error_flag.item())))
     else:
         out = seg.frame(scan, background=frame)
     os.makedirs(args.out, exist_ok=True)
