@@ -875,6 +875,61 @@ int pn2_voxel_grid(const float *pts, int ld, const int32_t *labels_in, const int
                    int32_t *out_labels, int32_t *out_index, int64_t *out_count, int32_t *inverse, int32_t *n_points, int *err,
                    void *workspace, pn2_stream_t stream);
 
+/* ---- segment reductions: voxel mean, its backward pass, majority label (csrc/voxel_reduce.hip), added within ABI 15 (additive) ------
+ * Reductions over an `inverse`-style map, as pn2_voxel_grid writes it.  SEGMENTS are what pn2_voxel_grid calls voxels:
+ *   row row_begin[b] + i of cloud b (i < row_count[b]) belongs to output row out_begin[b] + seg[row_begin[b] + i];
+ *   seg         int32[rows]: the rank of the row's segment inside its cloud.  A NEGATIVE seg: the row takes no part.  A seg at or
+ *               beyond out_count[b] or max_rows: the row takes no part either and sets PN2_SEGMENT_ERR_RANGE; it never causes a
+ *               write outside the cloud's output range;
+ *   out_count   int64[B] (DEVICE): the segments of cloud b.  Output rows at or beyond it are not written;
+ *   row_begin, row_count, max_rows, out_begin follow pn2_voxel_grid; every count is read on the device and clamped to
+ *               [0, max_rows], so a captured call stays valid when the counts change.
+ * Plain launches on the caller's stream (mean 4, backward 1, mode 4); no host synchronisation, no allocation, no thread waits for
+ * another thread's write.  Everything that crosses threads is an integer atomic (max, add, compare-and-swap): integer maxima and
+ * sums commute, so every output is the same from run to run, byte for byte, whatever the order of the rows' arrival.
+ *
+ * THE MEAN, per segment and per column c < C (1 <= C <= PN2_SEGMENT_MAX_COLS; values fp32 of pitch ld >= C, out of pitch ld_out >= C):
+ *   1. a finite float32 is s * M * 2^(k - 150): for an exponent field e >= 1, M = 2^23 + fraction and k = e; for e = 0, M = fraction
+ *      and k = 1.  K is the largest k among the segment's terms in that column.
+ *   2. a term contributes the integer t = s * ((M << 10) >> (K - k)): the shift truncates the magnitude, t = 0 when K - k >= 34.
+ *      |t| < 2^34 and at most 2^29 rows: S = sum of t fits a signed 64-bit word exactly, whatever the order.
+ *   3. mean = float32(ldexp(double(S) / double(n), K - 160)): int64 -> fp64 to nearest even, ONE IEEE fp64 division, an exact
+ *      power-of-two scaling in fp64, ONE rounding to float32 (subnormal results included).  n is the number of rows that take part:
+ *      n_points[out row] (int32, e.g. pn2_voxel_grid's) or, with n_points NULL, counted by the call.  n_out (int32, may be NULL)
+ *      receives the n that was used.  A given n_points <= 0 gives +0.0.
+ *   4. a NaN or +-inf term: the column's mean is the quiet NaN 0x7FC00000 and PN2_SEGMENT_ERR_NONFINITE is set (a stated deviation:
+ *      numpy gives +-inf for infinities of one sign); the segment's other columns are not affected.
+ *   5. a segment without rows gives +0.0 (and S = 0 gives +0.0: x and -x cancel exactly).
+ *   Every term is truncated by less than one unit 2^(K - 160), at most 2^-33 of the column's largest magnitude, so
+ *   |mean - exact mean| <= 2^(K - 160) + 1/2 ulp32(mean) + |exact| * 2^-51; sums that would overflow float32 do not overflow here.
+ * THE MEAN, BACKWARD: grad_in[row, c] = grad_out[out_begin[b] + seg[row], c] / float(n_points[out row]), one IEEE float32 division;
+ *   a row that takes no part gets +0.0 (and so does a row whose n_points is <= 0); rows outside the clouds are not written.
+ * THE MAJORITY LABEL: a row votes iff it takes part and its int32 label is >= 0.  The label with the most votes wins, among equals
+ *   the LOWEST label; a segment with no voter gets `fill`.  votes (int32, may be NULL) receives the winner's count (0: no voter);
+ *   votes / n_points is the cell's purity.  No class limit: any label up to 2^31 - 1.  (out_labels may be NULL when votes is not.)
+ * err (device int, caller zeroes, may be NULL) receives PN2_SEGMENT_ERR_RANGE and PN2_SEGMENT_ERR_NONFINITE; the bits are disjoint
+ * from PN2_VOXEL_ERR_*, so one word can serve a pn2_voxel_grid call and the reductions that follow it.
+ * workspace: pn2_segment_reduce_workspace_bytes(B, max_rows, C) bytes of device memory, 16-byte aligned, enough for EITHER
+ * pn2_segment_mean with up to C columns OR pn2_segment_mode (calls on one stream may share it); it may hold anything on entry.
+ * Per cloud: 12 bytes per (row, column) + 4 per row for the mean; a table of the power of two >= 2 * max_rows 16-byte slots + 8 bytes
+ * per row for the mode.
+ * PN2_EINVAL without a launch: a null required pointer, C outside 1..16, ld / ld_out / ld_in < C, B < 1 or B > 65535, max_rows < 0
+ * or > PN2_VOXEL_MAX_ROWS, a pointer that is not 4-byte (workspace: 16-byte) aligned; pn2_segment_reduce_workspace_bytes returns
+ * PN2_EINVAL for such B / max_rows / C. */
+#define PN2_SEGMENT_MAX_COLS 16
+#define PN2_SEGMENT_ERR_RANGE 4
+#define PN2_SEGMENT_ERR_NONFINITE 8
+int64_t pn2_segment_reduce_workspace_bytes(int B, int64_t max_rows, int C);
+int pn2_segment_mean(const float *values, int ld, int C, const int32_t *seg, const int64_t *row_begin, const int64_t *row_count, int B,
+                     int64_t max_rows, const int64_t *out_begin, const int64_t *out_count, const int32_t *n_points, float *out, int ld_out,
+                     int32_t *n_out, int *err, void *workspace, pn2_stream_t stream);
+int pn2_segment_mean_bwd(const float *grad_out, int ld_out, int C, const int32_t *seg, const int64_t *row_begin, const int64_t *row_count,
+                         int B, int64_t max_rows, const int64_t *out_begin, const int64_t *out_count, const int32_t *n_points,
+                         float *grad_in, int ld_in, int *err, pn2_stream_t stream);
+int pn2_segment_mode(const int32_t *labels, const int32_t *seg, const int64_t *row_begin, const int64_t *row_count, int B, int64_t max_rows,
+                     const int64_t *out_begin, const int64_t *out_count, int32_t fill, int32_t *out_labels, int32_t *votes, int *err,
+                     void *workspace, pn2_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

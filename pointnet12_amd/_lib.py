@@ -114,6 +114,10 @@ SIGNATURES = {
     "pn2_knn_vote": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _i, _vp, _i, _vp, _i64, _vp, _vp, _vp]),
     "pn2_voxel_grid_workspace_bytes": (_i64, [_i, _i64]),
     "pn2_voxel_grid": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pn2_segment_reduce_workspace_bytes": (_i64, [_i, _i64, _i]),
+    "pn2_segment_mean": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "pn2_segment_mean_bwd": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "pn2_segment_mode": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
 
@@ -128,6 +132,8 @@ KNN_ERR_LABEL, KNN_ERR_DST = 1, 2        # the err bits of pn2_knn_vote
 VOXEL_TILE = 1024        # PN2_VOXEL_TILE of include/pn2.h: rows per workgroup of pn2_voxel_grid's compaction passes
 VOXEL_MAX_ROWS = 1 << 29                 # PN2_VOXEL_MAX_ROWS: the largest max_rows of pn2_voxel_grid
 VOXEL_ERR_RANGE, VOXEL_ERR_ROWS = 1, 2   # PN2_VOXEL_ERR_* of include/pn2.h
+SEGMENT_MAX_COLS = 16    # PN2_SEGMENT_MAX_COLS: the widest pn2_segment_mean / pn2_segment_mean_bwd call
+SEGMENT_ERR_RANGE, SEGMENT_ERR_NONFINITE = 4, 8      # PN2_SEGMENT_ERR_* (disjoint from VOXEL_ERR_*: they share VoxelGrid.error_flag)
 
 
 class BnLazy(ctypes.Structure):
@@ -185,7 +191,8 @@ class _Timed:
                                                    "pn2_conv1x1_wgrad_cf_scratch_bytes", "pn2_conv1x1_bwd_cf_supported", "pn2_conv1x1_bwd_first_supported", "pn2_conv1x1_bwd_cf_scratch_bytes", "pn2_last_kernel", "pn2_clear_last_kernel",
                                                    "pn2_ball_query_workspace_bytes", "pn2_point_transform_workspace_bytes",
                                                    "pn2_group_colsum_workspace_bytes", "pn2_chamfer_nn_workspace_bytes",
-                                                   "pn2_scan_filter_workspace_bytes", "pn2_voxel_grid_workspace_bytes"):
+                                                   "pn2_scan_filter_workspace_bytes", "pn2_voxel_grid_workspace_bytes",
+                                                   "pn2_segment_reduce_workspace_bytes"):
             return fn
 
         def timed(*args):

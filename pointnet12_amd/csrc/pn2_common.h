@@ -79,7 +79,9 @@ static inline int64_t pn2_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
     X(WIDE_WGRAD_MIN_ROWS, 131072) /* rows from which it takes a layer */ \
     X(WGRAD_TWO_PHASE, 0) /* two-phase dW flush through caller scratch (256 x 196) */ \
     X(WGRAD_TWO_PHASE_ALL, 0) /* ... for all three full-tile shapes */ \
-    X(SEG_CHUNK, 0) /* segmented scatter: members per lane group (0: automatic) */
+    X(SEG_CHUNK, 0) /* segmented scatter: members per lane group (0: automatic) */ \
+    X(SEGRED_COMBINE, 1) /* segment mean / mode (csrc/voxel_reduce.hip): runs of equal segment combined inside the wave before the atomic (same bytes either way; tools/bench_voxel_reduce.py times both) */ \
+    X(SEGRED_LANES, 1) /* segment mean: 1 = lane L holds column L % C of row L / C (one wave instruction touches adjacent words of an accumulator row), 0 = one row per lane, its columns in a loop */
 
 enum Pn2Option {
 #define PN2_X(name, dflt) PN2_OPT_##name,

@@ -690,7 +690,10 @@ class FrameSegmenter:
         count back), and an explicit ``choice`` names downsampled rows.  The result gains ``voxel_count`` (int64 ``[1]`` on the
         device), ``voxel_index`` (int32: the RAW row of each voxel's representative, the grid's ``index`` composed with the
         filter's; the first ``voxel_count`` entries mean something) and ``voxel_inverse`` (int32: for each KEPT row the rank of its
-        voxel, -1 for a row the grid dropped); ``count`` / ``labels`` / ``index`` stay the filter's."""
+        voxel, -1 for a row the grid dropped); ``count`` / ``labels`` / ``index`` stay the filter's.  The grid carries its own
+        choice of representative: with ``VoxelGrid(reduce="mean")`` the rows the network sees (and ``raw_rows``, ``pts_3d``, the
+        pixels) are the voxels' MEAN rows, no rows of the scan; ``voxel_index`` still names each voxel's lowest raw row, and nothing
+        here reads a downsampled row back through it."""
         lib = _lib.load()
         if scan_filter is None:
             raise ValueError("FrameSegmenter.frame_raw: a kitti.ScanFilter is needed")
@@ -718,7 +721,7 @@ class FrameSegmenter:
         src, src_count = pts, count
         if voxel is not None:
             vb = held.get("voxel")
-            if vb is None:
+            if vb is None or (voxel.reduces and vb.reduce_workspace is None):       # (a reducing grid brings a workspace of its own)
                 vb = held["voxel"] = voxel.buffers(held["rows"])
             src, _, v_index, src_count, v_inverse, _ = voxel.downsample(pts, None, held["begin"], count, held["rows"], out=vb)
         if choice is None:

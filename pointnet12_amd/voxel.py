@@ -6,8 +6,13 @@ row learns which output row stands for it (``inverse``).  The kept COUNT stays i
 the device-side choice read it; nothing is read back or allocated by a call with ``out=``, so it captures into a graph, and the
 result is byte-identical from run to run.  The rule is stated in include/pn2.h (and, in numpy, in tests/voxel_ref.py).
 
-Out of scope: the MEAN of a voxel's rows (a run-to-run identical mean needs a fixed-order segmented sum; ``inverse`` and
-``n_points`` are what it would be built from) and grids over more than three key columns.
+``VoxelGrid(reduce="mean", label_reduce="mode")`` returns the voxel's MEAN row (centroid and mean remission) and its MAJORITY label
+instead of the lowest row's: order-free integer segment reductions over ``inverse`` (``pn2_segment_mean`` / ``pn2_segment_mode``,
+csrc/voxel_reduce.hip; the rules are in include/pn2.h and, in numpy, in tests/voxel_reduce_ref.py), byte-identical from run to run
+like everything else here.  ``segment_mean`` / ``segment_mode`` run them over any ``inverse``-style map, ``pool_mean`` is the mean as
+an autograd function.
+
+Out of scope: more than 16 columns per reduction, per-column max / min pooling and grids over more than three key columns.
 """
 import ctypes
 
@@ -28,9 +33,11 @@ def _triple(v, what):
 
 class VoxelBuffers:
     """The static buffers of one ``VoxelGrid.downsample`` call shape (``VoxelGrid.buffers``): ``points`` float32 ``[rows, ld]``,
-    ``labels`` / ``index`` / ``inverse`` / ``n_points`` int32 ``[rows]``, ``count`` int64 ``[B]`` and the kernel's ``workspace``."""
+    ``labels`` / ``index`` / ``inverse`` / ``n_points`` int32 ``[rows]``, ``count`` int64 ``[B]`` and the kernel's ``workspace``.
+    ``reduce=True`` (what a grid with ``reduce="mean"`` or ``label_reduce="mode"`` asks for) adds ``reduce_workspace``, the segment
+    reductions' workspace, and ``votes`` int32 ``[rows]``; both are None otherwise."""
 
-    def __init__(self, rows, B, max_rows, ld, device):
+    def __init__(self, rows, B, max_rows, ld, device, reduce=False):
         nbytes = _lib.load().pn2_voxel_grid_workspace_bytes(int(B), int(max_rows))
         if nbytes < 0:
             raise _lib.Pn2Error("VoxelBuffers: B = %d, max_rows = %d are not supported" % (B, max_rows))
@@ -40,6 +47,13 @@ class VoxelBuffers:
         self.labels, self.index, self.inverse, self.n_points = i32(), i32(), i32(), i32()
         self.count = torch.zeros(self.B, device=device, dtype=torch.int64)
         self.workspace = torch.empty(nbytes, device=device, dtype=torch.uint8)
+        self.reduce_workspace = self.votes = None
+        if reduce:
+            nbytes = _lib.load().pn2_segment_reduce_workspace_bytes(self.B, self.max_rows, self.ld)
+            if nbytes < 0:
+                raise _lib.Pn2Error("VoxelBuffers: B = %d, max_rows = %d, ld = %d are not supported" % (B, max_rows, ld))
+            self.reduce_workspace = torch.empty(nbytes, device=device, dtype=torch.uint8)
+            self.votes = i32()
 
 
 class VoxelGrid:
@@ -48,9 +62,20 @@ class VoxelGrid:
 
     ``error_flag`` (device int32, cleared at the start of every ``downsample``) collects ``_lib.VOXEL_ERR_RANGE`` (a row with a
     non-finite coordinate or outside the grid: it is dropped and its ``inverse`` is -1) and ``_lib.VOXEL_ERR_ROWS`` (a
-    ``row_count`` above ``max_rows``: the rows beyond are ignored); ``check()`` reads it back and raises ``ValueError``."""
+    ``row_count`` above ``max_rows``: the rows beyond are ignored); ``check()`` reads it back and raises ``ValueError``.
 
-    def __init__(self, voxel_size, origin=0.0, device="cuda"):
+    ``reduce``: what ``downsample`` returns as a voxel's ``points`` row -- ``"first"``: its lowest row, bit for bit; ``"mean"``: the
+    mean of ALL ``ld`` columns over the voxel's rows (the centroid plus mean remission; ``pn2_segment_mean``'s rule, include/pn2.h).
+    ``label_reduce``: its label -- ``"first"``: the lowest row's; ``"mode"``: the majority label of the voxel's rows with a label
+    >= 0, the lowest label among equals, -1 without one (``pn2_segment_mode``; the winner's count is left in the buffers'
+    ``votes``).  ``index`` / ``count`` / ``inverse`` / ``n_points`` do not depend on either.  The reductions add
+    ``_lib.SEGMENT_ERR_NONFINITE`` to ``error_flag`` (a NaN / inf in a column that is no coordinate: that voxel's mean of that column is
+    NaN) and ``_lib.SEGMENT_ERR_RANGE`` (cannot happen with the grid's own ``inverse``)."""
+
+    def __init__(self, voxel_size, origin=0.0, device="cuda", reduce="first", label_reduce="first"):
+        if reduce not in ("first", "mean") or label_reduce not in ("first", "mode"):
+            raise ValueError('VoxelGrid: reduce is "first" or "mean", label_reduce "first" or "mode"')
+        self.reduce, self.label_reduce = reduce, label_reduce
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.Pn2Error("VoxelGrid: the HIP device is the only implementation")
@@ -62,7 +87,12 @@ class VoxelGrid:
     def buffers(self, rows, B=1, max_rows=None, ld=4):
         """``VoxelBuffers`` for calls of ``B`` clouds of at most ``max_rows`` rows each (default ``rows``) whose inputs and outputs
         fit ``rows`` rows of ``ld`` floats."""
-        return VoxelBuffers(rows, B, rows if max_rows is None else max_rows, ld, self.device)
+        return VoxelBuffers(rows, B, rows if max_rows is None else max_rows, ld, self.device, self.reduces)
+
+    @property
+    def reduces(self):
+        """Whether ``downsample`` runs a segment reduction (its buffers then carry ``reduce_workspace``)."""
+        return self.reduce == "mean" or self.label_reduce == "mode"
 
     def downsample(self, points, labels=None, row_begin=None, row_count=None, max_rows=None, out=None, out_begin=None):
         """``(points, labels, index, count, inverse, n_points)`` as device tensors.  ``points``: float32 on the device, ``[M, ld]``
@@ -73,7 +103,8 @@ class VoxelGrid:
 
         Cloud b's voxels are rows ``out_begin[b] : out_begin[b] + count[b]`` of the outputs (``out_begin``: int64 ``[B]`` on the
         device, None: ``row_begin``), in the order of their representatives -- each voxel's lowest row: ``points`` (that row, all
-        ``ld`` floats bit for bit), ``labels`` (its label), ``index`` int32 (its row inside the cloud, strictly increasing) and
+        ``ld`` floats bit for bit; with ``reduce="mean"`` the mean of the voxel's rows), ``labels`` (its label; with
+        ``label_reduce="mode"`` the voxel's majority label), ``index`` int32 (its row inside the cloud, strictly increasing) and
         ``n_points`` int32 (the valid rows in the voxel); rows outside those ranges are not written.  ``inverse`` int32 ``[rows]``:
         for row ``row_begin[b] + i`` the rank of its voxel inside cloud b (-1: the row was dropped).  ``count`` is int64 ``[B]`` and
         stays on the device.  With ``out`` (a ``VoxelBuffers`` of this shape) and ``row_begin`` / ``row_count`` given (or the
@@ -103,29 +134,46 @@ class VoxelGrid:
                 raise ValueError("VoxelGrid.downsample: row_begin, row_count and out_begin must be int64 [B] device tensors")
         max_rows = M if max_rows is None else int(max_rows)
         if out is None:
-            out = VoxelBuffers(rows, B, max_rows, ld, self.device)
+            out = VoxelBuffers(rows, B, max_rows, ld, self.device, self.reduces)
         elif out.B != B or out.max_rows < max_rows or out.ld != ld or out.rows < rows:
             raise ValueError("VoxelGrid.downsample: out was made for B = %d, max_rows = %d, ld = %d, %d rows"
                              % (out.B, out.max_rows, out.ld, out.rows))
+        mean, mode = self.reduce == "mean", self.label_reduce == "mode" and labels is not None
+        if (mean or mode) and out.reduce_workspace is None:
+            raise ValueError("VoxelGrid.downsample: out was made without the reductions' workspace (VoxelGrid.buffers of THIS grid has it)")
         p = _lib.ptr
         dp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        ob = row_begin if out_begin is None else out_begin
         self.error_flag.zero_()                                      # an async fill, nothing is read back
         # (max_rows as the buffers were made for: the workspace layout follows it)
         _lib.check(_lib.load().pn2_voxel_grid(p(points), ld, p(labels), p(row_begin), p(row_count), B, out.max_rows, dp(self.origin),
-                                              dp(self.voxel_size), p(row_begin if out_begin is None else out_begin), p(out.points),
-                                              p(out.labels) if labels is not None else None, p(out.index), p(out.count),
+                                              dp(self.voxel_size), p(ob), None if mean else p(out.points),
+                                              p(out.labels) if labels is not None and not mode else None, p(out.index), p(out.count),
                                               p(out.inverse), p(out.n_points), p(self.error_flag), p(out.workspace), _lib.stream()),
                    "pn2_voxel_grid")
+        # the reductions read `inverse`, `count` and `n_points` where the launches above left them: device memory, nothing read back
+        if mean:
+            _lib.check(_lib.load().pn2_segment_mean(p(points), ld, ld, p(out.inverse), p(row_begin), p(row_count), B, out.max_rows, p(ob),
+                                                    p(out.count), p(out.n_points), p(out.points), ld, None, p(self.error_flag),
+                                                    p(out.reduce_workspace), _lib.stream()), "pn2_segment_mean")
+        if mode:
+            _lib.check(_lib.load().pn2_segment_mode(p(labels), p(out.inverse), p(row_begin), p(row_count), B, out.max_rows, p(ob),
+                                                    p(out.count), -1, p(out.labels), p(out.votes), p(self.error_flag),
+                                                    p(out.reduce_workspace), _lib.stream()), "pn2_segment_mode")
         return out.points, (out.labels if labels is not None else None), out.index, out.count, out.inverse, out.n_points
 
     def check(self):
-        """Reads ``error_flag`` back: ``ValueError`` for a row outside the grid (or not finite) and for a ``row_count`` above
-        ``max_rows``."""
+        """Reads ``error_flag`` back: ``ValueError`` for a row outside the grid (or not finite), for a ``row_count`` above
+        ``max_rows`` and for the reductions' two bits."""
         flag = int(self.error_flag.item())
         if flag & _lib.VOXEL_ERR_RANGE:
             raise ValueError("VoxelGrid: a row has a non-finite coordinate or lies outside the grid's 2**21 cells per axis")
         if flag & _lib.VOXEL_ERR_ROWS:
             raise ValueError("VoxelGrid: a row_count is above max_rows")
+        if flag & _lib.SEGMENT_ERR_NONFINITE:
+            raise ValueError("VoxelGrid: a voxel's mean met a NaN or an infinity (that column of that voxel is NaN)")
+        if flag & _lib.SEGMENT_ERR_RANGE:
+            raise ValueError("VoxelGrid: a row names a voxel at or beyond the voxel count")
 
 
 def expand(values, inverse, fill):
@@ -137,3 +185,137 @@ def expand(values, inverse, fill):
     picked = values.index_select(0, inv.clamp(min=0))
     mask = (inv < 0).view((-1,) + (1,) * (values.dim() - 1))
     return picked.masked_fill(mask, fill)
+
+
+def _segment_args(what, rows, inverse, count, row_begin, row_count, max_rows, out_begin, dev):
+    """The batched conventions of the segment reductions: ``(inverse, count, row_begin, row_count, B, max_rows, out_begin)``.  ONE
+    cloud without ``row_begin`` / ``row_count``: every row, outputs from row 0."""
+    if not inverse.is_cuda or inverse.dtype != torch.int32 or inverse.numel() != rows or not inverse.is_contiguous():
+        raise ValueError("%s: inverse must be a contiguous int32 device tensor, one entry per row" % what)
+    if (row_begin is None) != (row_count is None):
+        raise ValueError("%s: row_begin and row_count go together" % what)
+    if not isinstance(count, torch.Tensor):
+        count = torch.full((1,), int(count), device=dev, dtype=torch.int64)
+    count = count.reshape(-1)
+    B = int(count.numel())
+    if row_begin is None:
+        if B != 1:
+            raise ValueError("%s: several clouds need row_begin and row_count" % what)
+        row_begin = torch.zeros(1, device=dev, dtype=torch.int64)
+        row_count = torch.full((1,), rows, device=dev, dtype=torch.int64)
+    out_begin = row_begin if out_begin is None else out_begin
+    for t in (count, row_begin, row_count, out_begin):
+        if not t.is_cuda or t.dtype != torch.int64 or t.numel() != B or not t.is_contiguous():
+            raise ValueError("%s: count, row_begin, row_count and out_begin must be int64 [B] device tensors" % what)
+    return inverse, count, row_begin, row_count, B, (rows if max_rows is None else int(max_rows)), out_begin
+
+
+def _values_2d(what, values):
+    if not isinstance(values, torch.Tensor) or not values.is_cuda:
+        raise _lib.Pn2Error("%s: the values must live on the GPU: this package has no CPU path" % what)
+    if values.dtype != torch.float32 or values.dim() != 2 or not 1 <= values.shape[1] <= _lib.SEGMENT_MAX_COLS or not values.is_contiguous():
+        raise ValueError("%s: a contiguous float32 [rows, C] tensor, 1 <= C <= %d" % (what, _lib.SEGMENT_MAX_COLS))
+    return int(values.shape[0]), int(values.shape[1])
+
+
+def _workspace(workspace, B, max_rows, C, dev):
+    nbytes = _lib.load().pn2_segment_reduce_workspace_bytes(B, max_rows, C)
+    if nbytes < 0:
+        raise _lib.Pn2Error("segment reduction: B = %d, max_rows = %d, C = %d are not supported" % (B, max_rows, C))
+    if workspace is None:
+        return torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    if not workspace.is_cuda or workspace.dtype != torch.uint8 or workspace.numel() < nbytes:
+        raise ValueError("segment reduction: the workspace must be a uint8 device tensor of at least %d bytes" % nbytes)
+    return workspace
+
+
+def segment_mean(values, inverse, count, n_points=None, row_begin=None, row_count=None, max_rows=None, out_begin=None, out_rows=None,
+                 out=None, n_out=None, error_flag=None, workspace=None):
+    """The mean of ``values``' rows per segment (``pn2_segment_mean``; the rule of include/pn2.h: a 64-bit integer sum of fixed-point
+    terms, so the result does not depend on the order of the rows and is byte-identical from run to run).
+
+    ``values``: float32 ``[rows, C]`` on the device, C <= 16; ``inverse``: int32 ``[rows]``, the segment (rank inside its cloud) of
+    every row, negative = the row takes no part; ``count``: the number of segments, an int or an int64 ``[B]`` DEVICE tensor
+    (``VoxelGrid.downsample``'s ``count``); ``n_points``: int32, the rows per segment (``downsample``'s) or None (counted here).
+    One cloud, or B clouds with ``row_begin`` / ``row_count`` / ``max_rows`` / ``out_begin`` as ``VoxelGrid.downsample`` takes them.
+    Returns float32 ``[out_rows, C]`` (default ``rows``; ``out``: a tensor to write into): segment s of cloud b is row
+    ``out_begin[b] + s``; rows at or beyond the count are not written (zeros in a tensor made here).  ``n_out`` (int32): receives the
+    rows per segment that were used.  ``error_flag`` (device int32, not cleared here) collects ``_lib.SEGMENT_ERR_*``.  With ``out``,
+    ``workspace`` (``pn2_segment_reduce_workspace_bytes``) and device-side counts the call allocates nothing and can be captured."""
+    rows, C = _values_2d("segment_mean", values)
+    dev = values.device
+    inverse, count, row_begin, row_count, B, max_rows, out_begin = _segment_args("segment_mean", rows, inverse, count, row_begin, row_count,
+                                                                                max_rows, out_begin, dev)
+    if out is None:
+        out = torch.zeros(rows if out_rows is None else int(out_rows), C, device=dev, dtype=torch.float32)
+    elif not out.is_cuda or out.dtype != torch.float32 or out.dim() != 2 or out.shape[1] != C or not out.is_contiguous():
+        raise ValueError("segment_mean: out must be a contiguous float32 [out_rows, C] device tensor")
+    p = _lib.ptr
+    _lib.check(_lib.load().pn2_segment_mean(p(values), C, C, p(inverse), p(row_begin), p(row_count), B, max_rows, p(out_begin), p(count),
+                                            p(n_points), p(out), C, p(n_out), p(error_flag), p(_workspace(workspace, B, max_rows, C, dev)),
+                                            _lib.stream()), "pn2_segment_mean")
+    return out
+
+
+def segment_mode(labels, inverse, count, fill=-1, return_votes=False, row_begin=None, row_count=None, max_rows=None, out_begin=None,
+                 out_rows=None, out=None, votes=None, error_flag=None, workspace=None):
+    """The majority label per segment (``pn2_segment_mode``): of the rows that take part and carry a label >= 0 the label with the
+    most votes, the LOWEST label among equals, ``fill`` for a segment without a voter.  ``labels``: int32 ``[rows]`` on the device;
+    the other arguments as ``segment_mean``'s.  Returns int32 ``[out_rows]`` (rows at or beyond the count hold ``fill`` in a tensor
+    made here), with ``return_votes`` also the winners' counts (``votes / n_points`` is a cell's purity).  Integer arithmetic, no class
+    limit: the result is identical from run to run."""
+    if not isinstance(labels, torch.Tensor) or not labels.is_cuda:
+        raise _lib.Pn2Error("segment_mode: the labels must live on the GPU: this package has no CPU path")
+    if labels.dtype != torch.int32 or labels.dim() != 1 or not labels.is_contiguous():
+        raise ValueError("segment_mode: labels must be a contiguous int32 [rows] device tensor")
+    rows, dev = int(labels.numel()), labels.device
+    inverse, count, row_begin, row_count, B, max_rows, out_begin = _segment_args("segment_mode", rows, inverse, count, row_begin, row_count,
+                                                                                max_rows, out_begin, dev)
+    n_out = rows if out_rows is None else int(out_rows)
+    if out is None:
+        out = torch.full((n_out,), int(fill), device=dev, dtype=torch.int32)
+    if votes is None and return_votes:
+        votes = torch.zeros(n_out, device=dev, dtype=torch.int32)
+    p = _lib.ptr
+    _lib.check(_lib.load().pn2_segment_mode(p(labels), p(inverse), p(row_begin), p(row_count), B, max_rows, p(out_begin), p(count), int(fill),
+                                            p(out), p(votes), p(error_flag), p(_workspace(workspace, B, max_rows, 1, dev)), _lib.stream()),
+               "pn2_segment_mode")
+    return (out, votes) if return_votes else out
+
+
+class _PoolMean(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, values, inverse, count, n_points, row_begin, row_count, max_rows, out_begin, out_rows, error_flag):
+        rows, C = _values_2d("pool_mean", values)
+        dev = values.device
+        inverse, count, row_begin, row_count, B, max_rows, out_begin = _segment_args("pool_mean", rows, inverse, count, row_begin, row_count,
+                                                                                    max_rows, out_begin, dev)
+        out_rows = rows if out_rows is None else int(out_rows)
+        n_used = torch.zeros(out_rows, device=dev, dtype=torch.int32)
+        out = segment_mean(values, inverse, count, n_points, row_begin, row_count, max_rows, out_begin, out_rows, n_out=n_used,
+                           error_flag=error_flag)
+        ctx.save_for_backward(inverse, count, row_begin, row_count, out_begin, n_used)
+        ctx.shape = (rows, C, B, max_rows)
+        ctx.error_flag = error_flag
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        inverse, count, row_begin, row_count, out_begin, n_used = ctx.saved_tensors
+        rows, C, B, max_rows = ctx.shape
+        grad_out = grad_out.contiguous()
+        grad_in = torch.zeros(rows, C, device=grad_out.device, dtype=torch.float32)      # (rows outside the clouds are not written)
+        p = _lib.ptr
+        _lib.check(_lib.load().pn2_segment_mean_bwd(p(grad_out), C, C, p(inverse), p(row_begin), p(row_count), B, max_rows, p(out_begin),
+                                                    p(count), p(n_used), p(grad_in), C, p(ctx.error_flag), _lib.stream()),
+                   "pn2_segment_mean_bwd")
+        return (grad_in,) + (None,) * 9
+
+
+def pool_mean(values, inverse, count, n_points=None, row_begin=None, row_count=None, max_rows=None, out_begin=None, out_rows=None,
+              error_flag=None):
+    """``segment_mean`` as a ``torch.autograd.Function`` on the two mean kernels: per-point features ``[rows, C]`` pooled to their
+    voxels inside a model and trained through.  Forward ``pn2_segment_mean``, backward ``pn2_segment_mean_bwd``
+    (``grad_in[row] = grad_out[segment of row] / float32(n)``, zeros for a row that takes no part).  Arguments as ``segment_mean``'s;
+    features wider than 16 columns are pooled 16 columns at a time by the caller."""
+    return _PoolMean.apply(values, inverse, count, n_points, row_begin, row_count, max_rows, out_begin, out_rows, error_flag)

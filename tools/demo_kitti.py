@@ -23,7 +23,8 @@ no label file (a live feed), a dataset scan goes in with its ``.label`` words.  
 raw scan takes the majority label of its 5 nearest drawn rows within 1 m, mapped back to the dataset's raw ids
 (``kitti.inverse_label_lut``), rows the filter dropped are 0, and FILE is written in the dataset's ``.label`` format.
 ``--voxel SIZE`` (with ``--raw``) downsamples the kept rows to one row per occupied cell of SIZE metres before the choice
-(``voxel.VoxelGrid``, ``pn2_voxel_grid``), which is then drawn from the voxel count.
+(``voxel.VoxelGrid``, ``pn2_voxel_grid``), which is then drawn from the voxel count.  ``--voxel-reduce mean`` shows each cell's mean row
+(centroid and mean remission, ``pn2_segment_mean``) instead of its first, ``--voxel-labels mode`` takes the cell's majority label.
 
 ``--time`` prints one JSON line with medians of 20 (device work included, host clock) for the post-network stages --
 predict + project + both images (``render_ms``), and the same as a captured graph (``render_graph_ms``) -- and beside them, in
@@ -202,6 +203,10 @@ def main():
     ap.add_argument("--raw", action="store_true", help="feed the raw scan through frame_raw: filter and compaction on the device")
     ap.add_argument("--labels-out", metavar="FILE", help="with --raw: label every row of the scan (label_scan) and write a .label file")
     ap.add_argument("--voxel", type=float, metavar="SIZE", help="with --raw: voxel-grid downsample the kept rows at SIZE metres")
+    ap.add_argument("--voxel-reduce", choices=("first", "mean"), default="first",
+                    help="with --voxel: a cell is shown by its first row or by the mean of its rows")
+    ap.add_argument("--voxel-labels", choices=("first", "mode"), default="first",
+                    help="with --voxel: a cell's label is its first row's or the majority of its rows'")
     ap.add_argument("--ego", metavar="CAMERA.json", help="also draw the 3-D ego view through this open3d PinholeCameraParameters file")
     ap.add_argument("--render-option", metavar="FILE.json", help="open3d RenderOption file: the ego view's point size and background colour")
     ap.add_argument("--root")
@@ -233,6 +238,8 @@ def main():
         ap.error("--render-option needs --ego")
     if args.labels_out and (not args.raw or args.merge):
         ap.error("--labels-out needs --raw and does not go with --merge (merged classes have no raw id)")
+    if args.voxel is None and (args.voxel_reduce != "first" or args.voxel_labels != "first"):
+        ap.error("--voxel-reduce / --voxel-labels need --voxel")
     if args.voxel is not None and not args.raw:
         ap.error("--voxel needs --raw")
     camera = V.PinholeCamera.from_json(args.ego) if args.ego else None
@@ -247,7 +254,7 @@ def main():
         grid = None
         if args.voxel is not None:
             from pointnet12_amd import voxel
-            grid = voxel.VoxelGrid(args.voxel)
+            grid = voxel.VoxelGrid(args.voxel, reduce=args.voxel_reduce, label_reduce=args.voxel_labels)
         if args.labels_out:
             out = seg.label_scan(scan, words, scan_filter=scan_filter, rng=gen, lut=kitti.inverse_label_lut(cfg["learning_map_inv"]),
                                  background=frame, voxel=grid)
