@@ -11,9 +11,7 @@ constexpr int KNN_TILE = 1024;
 constexpr int KNN_THREADS = 256;
 
 __device__ __forceinline__ int knn_count(const int64_t *__restrict__ n, int b, int full) {
-    if (n == nullptr) return full;
-    const int64_t v = n[b];
-    return v < 0 ? 0 : (v > full ? full : (int)v);
+    return n == nullptr ? full : pn2_clamped_rows(n, b, full);         // (no count: every row)
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -30,6 +30,18 @@ static inline hipStream_t pn2_s(pn2_stream_t s) { return reinterpret_cast<hipStr
 
 static inline int64_t pn2_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+static inline int64_t pn2_round16(int64_t v) { return (v + 15) / 16 * 16; }
+
+// p lies on a multiple of `bytes` (a power of two; a null pointer counts as aligned)
+static inline bool pn2_aligned(const void *p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+
+// rows of cloud b a launch looks at: the device-side count[b] clamped to [0, max_rows] (a captured launch sized by max_rows
+// stays valid when the count changes)
+__device__ __forceinline__ int pn2_clamped_rows(const int64_t *count, int b, int max_rows) {
+    const int64_t n = count[b];
+    return n < 0 ? 0 : (n > max_rows ? max_rows : (int)n);
+}
+
 // ----------------------------------------------------------------------------- library options
 // Dispatch / tuning switches of the library.  They are set EXPLICITLY through pn2_set_option() (include/pn2.h): the library
 // never reads the process environment, so an external caller's results depend on its arguments and on the options it set,

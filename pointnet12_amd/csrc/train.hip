@@ -269,8 +269,6 @@ __global__ __launch_bounds__(kThreads) void shapes_kernel(const float *__restric
     if (labels && col == 0) labels[p] = raw_label ? (int64_t)raw_label[lo + c] : 0;
 }
 
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -282,7 +280,7 @@ int pn2_adam_step(float *param, float *grad, float *exp_avg, float *exp_avg_sq, 
     PN2_CHECK_ARG(step_dev || step >= 1);
     PN2_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0 && weight_decay >= 0.0);
     PN2_CHECK_ARG(lr_dev || lr >= 0.0);
-    const bool vec = aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq);
+    const bool vec = pn2_aligned(param, 16) && pn2_aligned(grad, 16) && pn2_aligned(exp_avg, 16) && pn2_aligned(exp_avg_sq, 16);
     int64_t blocks = pn2_cdiv(vec ? pn2_cdiv(n, 4) : n, kThreads);
     if (blocks > 8192) blocks = 8192;
     if (vec)
@@ -305,7 +303,7 @@ int pn2_sgd_step(float *param, float *grad, float *momentum_buf, int64_t n, doub
     const bool mom = momentum != 0.0;
     PN2_CHECK_ARG(!mom || momentum_buf);
     if (!mom) momentum_buf = nullptr;                           // never touched without momentum
-    const bool vec = aligned16(param) && aligned16(grad) && aligned16(momentum_buf);
+    const bool vec = pn2_aligned(param, 16) && pn2_aligned(grad, 16) && pn2_aligned(momentum_buf, 16);
     int64_t blocks = pn2_cdiv(vec ? pn2_cdiv(n, 4) : n, kThreads);
     if (blocks > 8192) blocks = 8192;
 #define PN2_SGD_LAUNCH(M, V)                                                                                                  \
@@ -324,7 +322,7 @@ int pn2_prepare_clouds(const float *raw, const int64_t *row_begin, const int64_t
                        const float *noise, const int64_t *noise_begin, const int64_t *choice, int B, int N,
                        float *points, int64_t *labels, int *bad_index, pn2_stream_t stream) {
     PN2_CHECK_ARG(raw && row_begin && row_count && choice && points && B > 0 && N > 0);
-    PN2_CHECK_ARG(aligned16(raw) && aligned16(points) && (!noise || aligned16(noise)));
+    PN2_CHECK_ARG(pn2_aligned(raw, 16) && pn2_aligned(points, 16) && (!noise || pn2_aligned(noise, 16)));
     hipLaunchKernelGGL(prepare_kernel, dim3((unsigned)pn2_cdiv((int64_t)B * N, kThreads)), dim3(kThreads), 0, pn2_s(stream),
                        reinterpret_cast<const float4 *>(raw), row_begin, row_count, raw_label, reinterpret_cast<const float4 *>(noise),
                        noise_begin, choice, B, N, reinterpret_cast<float4 *>(points), labels, bad_index);

@@ -50,8 +50,6 @@ struct Pinhole {
 constexpr int kMaxPointSize = 16;
 constexpr unsigned long long kEmptyKey = ~0ull;
 
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // ------------------------------------------------------------------------------------------------------------------ predict
 // Tensor.max(dim) of a group's members: the largest, NaN if any member is NaN (the first one met is returned).
 template <bool QUADS>
@@ -231,7 +229,7 @@ int pn2_seg_predict(const float *logp, int ld, int64_t R, int C, const int32_t *
     if (R == 0 || (pred == nullptr && merged == nullptr)) return PN2_OK;
     const int64_t blocks = pn2_cdiv(R, kThreads);
     PN2_CHECK_ARG(blocks <= 0x7fffffff);
-    const bool quads = G == 0 && ld % 4 == 0 && aligned16(logp);
+    const bool quads = G == 0 && ld % 4 == 0 && pn2_aligned(logp, 16);
     if (quads)
         hipLaunchKernelGGL(seg_predict_kernel<true>, dim3((unsigned)blocks), dim3(kThreads), 0, pn2_s(stream), logp, ld, R, C, G, tab,
                            pred, merged, ldm);

@@ -17,15 +17,15 @@
 //   associative: the bytes are the same either way).  64-bit integer atomics at these shapes are unmeasured in the hardware notes
 //   this project follows (their prices are for float atomics): tools/bench_voxel_reduce.py times every form (README: the table).
 //   pn2_segment_mean_bwd  one gather-and-divide launch.
-//   pn2_segment_mode   four launches: a second open-addressing table in voxel.hip's style -- 16-byte slots, a power of two >= twice
-//     the cloud's rows, 64-bit atomicCAS on the key (rank << 32 | label), atomicAdd of the pair's count (runs of equal pairs
-//     are added once per wave run) -- then every occupied slot does a 64-bit atomicMax on its segment's winner word
-//     (count << 32 | 0x7FFFFFFF - label: most votes, then the LOWEST label), and a last launch decodes it.
-//   No thread waits for another thread's write; every probe loop is bounded by the table's capacity.
+//   pn2_segment_mode   four launches: the open-addressing table of slot_table.h with the key (rank << 32 | label) and atomicAdd of
+//     the pair's count (runs of equal pairs are added once per wave run), used at the capacity of the cloud's device-side row
+//     count; then every occupied slot does a 64-bit atomicMax on its segment's winner word (count << 32 | 0x7FFFFFFF - label:
+//     most votes, then the LOWEST label), and a last launch decodes it.
+//   No thread waits for another thread's write.
 //
 // This file is built with -ffp-contract=off: the division and the power-of-two scaling are separately rounded operations.
 #include <cmath>
-#include "pn2_common.h"
+#include "slot_table.h"
 
 namespace {
 
@@ -33,7 +33,6 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / PN2_WAVE;
 constexpr int kNonFinite = 255;
 constexpr unsigned kQuietNan = 0x7FC00000u;
-constexpr unsigned long long kEmpty = ~0ull;                        // no key: a key is below 2^61
 constexpr unsigned kGridCap = 1u << 16;                             // workgroups per cloud of the grid-stride clears
 
 struct alignas(16) Pair {
@@ -42,33 +41,7 @@ struct alignas(16) Pair {
     int unused;
 };
 static_assert(sizeof(Pair) == 16, "one slot is one 16-byte word");
-
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-inline int64_t round16(int64_t v) { return (v + 15) / 16 * 16; }
-inline bool shape_ok(int B, int64_t max_rows) { return B >= 1 && B <= 65535 && max_rows >= 0 && max_rows <= PN2_VOXEL_MAX_ROWS; }
-inline int64_t table_capacity(int64_t max_rows) {                  // a power of two >= 2 * max_rows (and >= 64)
-    int64_t cap = 64;
-    while (cap < 2 * max_rows) cap <<= 1;
-    return cap;
-}
-
-__device__ __forceinline__ int clamped(const int64_t *count, int b, int max_rows) {
-    const int64_t n = count[b];
-    return n < 0 ? 0 : (n > max_rows ? max_rows : (int)n);
-}
-
-// the capacity cloud b's table is USED at: the power of two >= 2 * its rows (>= 64), never above the host's table_capacity(max_rows)
-__device__ __forceinline__ unsigned capacity_of(int rows) { return rows <= 32 ? 64u : 1u << (32 - __clz(2 * rows - 1)); }
-
-__device__ __forceinline__ unsigned mix(unsigned long long k) {    // (murmur3's finaliser; the choice shows in no output)
-    k ^= k >> 33;
-    k *= 0xff51afd7ed558ccdull;
-    k ^= k >> 33;
-    k *= 0xc4ceb9fe1a85ec53ull;
-    k ^= k >> 33;
-    return (unsigned)k;
-}
+static_assert(kThreads == kSlotThreads, "mode_clear_kernel fills its table with pn2_slot_fill");
 
 // ----------------------------------------------------------------------------------------------------------------- the mean
 // What a lane of the two row passes works on: row i of cloud b (column c), its segment (-1: the lane takes no part) and, for the
@@ -87,7 +60,7 @@ __device__ __forceinline__ bool load_term(Term &t, const int32_t *__restrict__ s
                                           const int64_t *__restrict__ row_count, int max_rows, const int64_t *__restrict__ out_count,
                                           int C, int R, bool by_row) {
     const int b = blockIdx.y;
-    const int n = clamped(row_count, b, max_rows), m = clamped(out_count, b, max_rows);
+    const int n = pn2_clamped_rows(row_count, b, max_rows), m = pn2_clamped_rows(out_count, b, max_rows);
     const int64_t first = (int64_t)blockIdx.x * (kWaves * R);
     if (first >= n) return false;                                   // (uniform over the workgroup)
     const int lane = threadIdx.x & (PN2_WAVE - 1), wave = threadIdx.x / PN2_WAVE;
@@ -197,7 +170,7 @@ __global__ __launch_bounds__(kThreads) void mean_add_kernel(const float *__restr
 __global__ __launch_bounds__(kThreads) void mean_clear_kernel(const int64_t *__restrict__ out_count, int max_rows, int C,
                                                               int *__restrict__ K, long long *__restrict__ S, int *__restrict__ rows_of) {
     const int b = blockIdx.y;
-    const int64_t words = (int64_t)clamped(out_count, b, max_rows) * C;
+    const int64_t words = (int64_t)pn2_clamped_rows(out_count, b, max_rows) * C;
     const int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (e >= words) return;
     const int64_t at = (int64_t)b * max_rows * C + e;
@@ -212,7 +185,7 @@ __global__ __launch_bounds__(kThreads) void mean_final_kernel(const int64_t *__r
                                                               const int32_t *__restrict__ n_points, float *__restrict__ out, int ld_out,
                                                               int32_t *__restrict__ n_out, int *__restrict__ err) {
     const int b = blockIdx.y;
-    const int64_t words = (int64_t)clamped(out_count, b, max_rows) * C;
+    const int64_t words = (int64_t)pn2_clamped_rows(out_count, b, max_rows) * C;
     if ((int64_t)blockIdx.x * kThreads >= words) return;            // (uniform over the workgroup)
     const int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     bool nonfinite = false;
@@ -244,12 +217,12 @@ __global__ __launch_bounds__(kThreads) void mean_bwd_kernel(const float *__restr
                                                             const int32_t *__restrict__ n_points, float *__restrict__ grad_in, int ld_in,
                                                             int *__restrict__ err) {
     const int b = blockIdx.y;
-    const int64_t words = (int64_t)clamped(row_count, b, max_rows) * C;
+    const int64_t words = (int64_t)pn2_clamped_rows(row_count, b, max_rows) * C;
     if ((int64_t)blockIdx.x * kThreads >= words) return;            // (uniform over the workgroup)
     const int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     bool bad = false;
     if (e < words) {
-        const int m = clamped(out_count, b, max_rows);
+        const int m = pn2_clamped_rows(out_count, b, max_rows);
         const int64_t i = e / C;
         const int c = (int)(e - i * C);
         const int64_t row = row_begin[b] + i;
@@ -272,14 +245,10 @@ __global__ __launch_bounds__(kThreads) void mode_clear_kernel(const int64_t *__r
                                                               int max_rows, uint4 *__restrict__ table, int64_t cap,
                                                               unsigned long long *__restrict__ winner) {
     const int b = blockIdx.y;
-    const int64_t slots = capacity_of(clamped(row_count, b, max_rows));               // <= cap
-    const int64_t m = clamped(out_count, b, max_rows);
-    const int64_t end = slots > m ? slots : m;
-    const uint4 empty = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u);
-    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < end; i += (int64_t)gridDim.x * kThreads) {
-        if (i < slots) table[(int64_t)b * cap + i] = empty;
-        if (i < m) winner[(int64_t)b * max_rows + i] = 0ull;
-    }
+    pn2_slot_fill(table + (int64_t)b * cap, pn2_slot_capacity(pn2_clamped_rows(row_count, b, max_rows)), pn2_slot_empty(0u, 0u));     // the slots in USE: <= cap
+    const int64_t m = pn2_clamped_rows(out_count, b, max_rows);
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < m; i += (int64_t)gridDim.x * kThreads)
+        winner[(int64_t)b * max_rows + i] = 0ull;
 }
 
 template <bool kCombine>
@@ -289,14 +258,14 @@ __global__ __launch_bounds__(kThreads) void mode_insert_kernel(const int32_t *__
                                                                const int64_t *__restrict__ out_count, Pair *__restrict__ table, int64_t cap,
                                                                int *__restrict__ err) {
     const int b = blockIdx.y;
-    const int n = clamped(row_count, b, max_rows);
+    const int n = pn2_clamped_rows(row_count, b, max_rows);
     if ((int64_t)blockIdx.x * kThreads >= n) return;                // (uniform over the workgroup)
     const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     const int lane = threadIdx.x & (PN2_WAVE - 1);
     unsigned long long key = kEmpty;                                // no vote
     bool bad = false;
     if (i < n) {
-        const int m = clamped(out_count, b, max_rows);
+        const int m = pn2_clamped_rows(out_count, b, max_rows);
         const int64_t row = row_begin[b] + i;
         const int s = seg[row];
         if (s >= m) {
@@ -317,18 +286,9 @@ __global__ __launch_bounds__(kThreads) void mode_insert_kernel(const int32_t *__
         issue = issue && head;
     }
     if (issue) {
-        const unsigned mask = capacity_of(n) - 1u;
         Pair *tab = table + (int64_t)b * cap;
-        unsigned s = mix(key) & mask;
-        for (unsigned probe = 0; probe <= mask; ++probe) {          // bounded: at most one pass over the table
-            const unsigned long long seen = atomicCAS(&tab[s].key, kEmpty, key);
-            if (seen == kEmpty || seen == key) {
-                atomicAdd(&tab[s].votes, votes);
-                break;
-            }
-            s = (s + 1) & mask;                                     // another pair's slot: move on, never wait
-        }
-        // (the loop cannot run out: the table has at least twice as many slots as the cloud has rows)
+        const int slot = pn2_slot_claim(tab, (unsigned)pn2_slot_capacity(n) - 1u, key);
+        if (slot >= 0) atomicAdd(&tab[slot].votes, votes);          // (always: the cloud has at most half as many rows as slots)
     }
     if (err != nullptr && __any(bad) && lane == 0) atomicOr(err, PN2_SEGMENT_ERR_RANGE);
 }
@@ -337,13 +297,13 @@ __global__ __launch_bounds__(kThreads) void mode_vote_kernel(const int64_t *__re
                                                              int max_rows, const Pair *__restrict__ table, int64_t cap,
                                                              unsigned long long *__restrict__ winner) {
     const int b = blockIdx.y;
-    const int64_t slots = capacity_of(clamped(row_count, b, max_rows));
+    const int64_t slots = pn2_slot_capacity(pn2_clamped_rows(row_count, b, max_rows));
     const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (i >= slots) return;
     const Pair p = table[(int64_t)b * cap + i];
     if (p.key == kEmpty) return;
     const unsigned rank = (unsigned)(p.key >> 32), label = (unsigned)p.key;
-    if ((int)rank >= clamped(out_count, b, max_rows)) return;       // (cannot happen: the insert checked it)
+    if ((int)rank >= pn2_clamped_rows(out_count, b, max_rows)) return;       // (cannot happen: the insert checked it)
     // most votes first, then the LOWEST label: the word is never 0, a vote count is at least 1
     atomicMax(winner + (int64_t)b * max_rows + rank, ((unsigned long long)(unsigned)p.votes << 32) | (0x7FFFFFFFu - label));
 }
@@ -353,7 +313,7 @@ __global__ __launch_bounds__(kThreads) void mode_decode_kernel(const int64_t *__
                                                                int32_t *__restrict__ out_labels, int32_t *__restrict__ votes) {
     const int b = blockIdx.y;
     const int64_t s = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (s >= clamped(out_count, b, max_rows)) return;
+    if (s >= pn2_clamped_rows(out_count, b, max_rows)) return;
     const unsigned long long w = winner[(int64_t)b * max_rows + s];
     const int64_t o = out_begin[b] + s;
     if (out_labels != nullptr) out_labels[o] = w == 0ull ? fill : (int32_t)(0x7FFFFFFFu - (unsigned)w);
@@ -362,10 +322,10 @@ __global__ __launch_bounds__(kThreads) void mode_decode_kernel(const int64_t *__
 
 inline int64_t mean_bytes(int B, int64_t max_rows, int C) {
     const int64_t words = (int64_t)B * max_rows * C;
-    return round16(words * 8) + round16(words * 4) + round16((int64_t)B * max_rows * 4);
+    return pn2_round16(words * 8) + pn2_round16(words * 4) + pn2_round16((int64_t)B * max_rows * 4);
 }
 inline int64_t mode_bytes(int B, int64_t max_rows) {
-    return (int64_t)B * table_capacity(max_rows) * (int64_t)sizeof(Pair) + round16((int64_t)B * max_rows * 8);
+    return (int64_t)B * pn2_slot_capacity(max_rows) * (int64_t)sizeof(Pair) + pn2_round16((int64_t)B * max_rows * 8);
 }
 inline unsigned blocks_for(int64_t items) { return (unsigned)(items <= 0 ? 1 : pn2_cdiv(items, kThreads)); }
 
@@ -374,7 +334,7 @@ inline unsigned blocks_for(int64_t items) { return (unsigned)(items <= 0 ? 1 : p
 extern "C" {
 
 int64_t pn2_segment_reduce_workspace_bytes(int B, int64_t max_rows, int C) {
-    if (!shape_ok(B, max_rows) || C < 1 || C > PN2_SEGMENT_MAX_COLS) return PN2_EINVAL;
+    if (!pn2_slot_shape_ok(B, max_rows) || C < 1 || C > PN2_SEGMENT_MAX_COLS) return PN2_EINVAL;
     const int64_t mean = mean_bytes(B, max_rows, C), mode = mode_bytes(B, max_rows);
     return mean > mode ? mean : mode;
 }
@@ -383,14 +343,14 @@ int pn2_segment_mean(const float *values, int ld, int C, const int32_t *seg, con
                      int64_t max_rows, const int64_t *out_begin, const int64_t *out_count, const int32_t *n_points, float *out, int ld_out,
                      int32_t *n_out, int *err, void *workspace, pn2_stream_t stream) {
     PN2_CHECK_ARG(values && seg && row_begin && row_count && out_begin && out_count && out && workspace);
-    PN2_CHECK_ARG(shape_ok(B, max_rows) && C >= 1 && C <= PN2_SEGMENT_MAX_COLS && ld >= C && ld_out >= C);
-    PN2_CHECK_ARG(aligned4(values) && aligned4(out) && aligned4(seg) && aligned16(workspace));
+    PN2_CHECK_ARG(pn2_slot_shape_ok(B, max_rows) && C >= 1 && C <= PN2_SEGMENT_MAX_COLS && ld >= C && ld_out >= C);
+    PN2_CHECK_ARG(pn2_aligned(values, 4) && pn2_aligned(out, 4) && pn2_aligned(seg, 4) && pn2_aligned(workspace, 16));
     const int64_t words = (int64_t)B * max_rows * C;
     unsigned char *at = static_cast<unsigned char *>(workspace);
     long long *S = reinterpret_cast<long long *>(at);
-    at += round16(words * 8);
+    at += pn2_round16(words * 8);
     int *K = reinterpret_cast<int *>(at);
-    at += round16(words * 4);
+    at += pn2_round16(words * 4);
     int *rows_of = reinterpret_cast<int *>(at);
     const bool row_per_lane = pn2_opt(PN2_OPT_SEGRED_LANES) == 0;   // (A/B: one row per lane, its columns in a loop)
     const int R = row_per_lane ? PN2_WAVE : PN2_WAVE / C;           // rows per wave of the two row passes
@@ -418,8 +378,8 @@ int pn2_segment_mean_bwd(const float *grad_out, int ld_out, int C, const int32_t
                          int B, int64_t max_rows, const int64_t *out_begin, const int64_t *out_count, const int32_t *n_points,
                          float *grad_in, int ld_in, int *err, pn2_stream_t stream) {
     PN2_CHECK_ARG(grad_out && seg && row_begin && row_count && out_begin && out_count && n_points && grad_in);
-    PN2_CHECK_ARG(shape_ok(B, max_rows) && C >= 1 && C <= PN2_SEGMENT_MAX_COLS && ld_out >= C && ld_in >= C);
-    PN2_CHECK_ARG(aligned4(grad_out) && aligned4(grad_in) && aligned4(seg) && aligned4(n_points));
+    PN2_CHECK_ARG(pn2_slot_shape_ok(B, max_rows) && C >= 1 && C <= PN2_SEGMENT_MAX_COLS && ld_out >= C && ld_in >= C);
+    PN2_CHECK_ARG(pn2_aligned(grad_out, 4) && pn2_aligned(grad_in, 4) && pn2_aligned(seg, 4) && pn2_aligned(n_points, 4));
     hipLaunchKernelGGL(mean_bwd_kernel, dim3(blocks_for(max_rows * C), (unsigned)B), dim3(kThreads), 0, pn2_s(stream), grad_out, ld_out, C,
                        seg, row_begin, row_count, (int)max_rows, out_begin, out_count, n_points, grad_in, ld_in, err);
     return pn2_launch_status();
@@ -429,8 +389,8 @@ int pn2_segment_mode(const int32_t *labels, const int32_t *seg, const int64_t *r
                      const int64_t *out_begin, const int64_t *out_count, int32_t fill, int32_t *out_labels, int32_t *votes, int *err,
                      void *workspace, pn2_stream_t stream) {
     PN2_CHECK_ARG(labels && seg && row_begin && row_count && out_begin && out_count && workspace && (out_labels || votes));
-    PN2_CHECK_ARG(shape_ok(B, max_rows) && aligned4(labels) && aligned4(seg) && aligned16(workspace));
-    const int64_t cap = table_capacity(max_rows);
+    PN2_CHECK_ARG(pn2_slot_shape_ok(B, max_rows) && pn2_aligned(labels, 4) && pn2_aligned(seg, 4) && pn2_aligned(workspace, 16));
+    const int64_t cap = pn2_slot_capacity(max_rows);
     Pair *table = static_cast<Pair *>(workspace);
     unsigned long long *winner = reinterpret_cast<unsigned long long *>(static_cast<unsigned char *>(workspace) + (int64_t)B * cap * (int64_t)sizeof(Pair));
     const hipStream_t s = pn2_s(stream);

@@ -100,6 +100,49 @@ def test_argument_checks_need_no_gpu():
         assert wb(1, m) >= 2 * m * 16 + 5 * m
 
 
+# pn2_scan_filter_workspace_bytes, pn2_voxel_grid_workspace_bytes and pn2_segment_reduce_workspace_bytes as the library returned them
+# BEFORE the three files shared compact.h / slot_table.h (recorded from that build, not computed): callers size allocations by them.
+WS_MAX_ROWS = (0, 1, 1023, 1024, 1025, 120000, 1 << 29)
+WS_SCAN = {
+    1: [1056, 1056, 1056, 1056, 2080, 121792, 541065216],
+    3: [3104, 3104, 3104, 3104, 6208, 365344, 1623195648],
+    16: [16512, 16512, 16512, 16512, 33024, 1948416, 8657043456],
+}
+WS_VOXEL = {
+    1: [6176, 6176, 37920, 37920, 75808, 4799424, 19868418048],
+    3: [18464, 18464, 113696, 113696, 227392, 14398240, 59605254144],
+    16: [98432, 98432, 606336, 606336, 1212672, 76790528, 317894688768],
+}
+WS_SEGMENT = {                                                        # (B, C)
+    (1, 1): [1024, 1040, 40960, 40960, 73744, 5154304, 21474836480],
+    (1, 4): [1024, 1040, 53200, 53248, 73744, 6240000, 27917287424],
+    (1, 16): [1024, 1040, 200512, 200704, 200912, 23520000, 105226698752],
+    (3, 1): [3072, 3104, 122864, 122880, 221216, 15462912, 64424509440],
+    (3, 4): [3072, 3104, 159600, 159744, 221216, 18720000, 83751862272],
+    (3, 16): [3072, 3104, 601536, 602112, 602704, 70560000, 315680096256],
+    (16, 1): [16384, 16512, 655232, 655360, 1179776, 82468864, 343597383680],
+    (16, 4): [16384, 16512, 851136, 851968, 1179776, 99840000, 446676598784],
+    (16, 16): [16384, 16512, 3208128, 3211264, 3214400, 376320000, 1683627180032],
+}
+
+
+def test_workspace_sizes_are_the_recorded_ones():
+    lib = _lib.load()
+    scan, voxel, segment = lib.pn2_scan_filter_workspace_bytes, lib.pn2_voxel_grid_workspace_bytes, lib.pn2_segment_reduce_workspace_bytes
+    for B, want in WS_SCAN.items():
+        assert [scan(B, m) for m in WS_MAX_ROWS] == want
+    for B, want in WS_VOXEL.items():
+        assert [voxel(B, m) for m in WS_MAX_ROWS] == want
+    for (B, C), want in WS_SEGMENT.items():
+        assert [segment(B, m, C) for m in WS_MAX_ROWS] == want
+    EINVAL = -1
+    assert scan(0, 16) == EINVAL and scan(65536, 16) == EINVAL and scan(1, 1 << 31) == EINVAL
+    assert scan(1, (1 << 31) - 1) == 2164260864 and scan(1, (1 << 29) + 1) == 541066272      # (the filter's own limit is 2^31 - 1)
+    assert voxel(0, 16) == EINVAL and voxel(65536, 16) == EINVAL and voxel(1, (1 << 29) + 1) == EINVAL
+    assert segment(0, 16, 4) == EINVAL and segment(65536, 16, 4) == EINVAL and segment(1, (1 << 29) + 1, 4) == EINVAL
+    assert segment(1, 16, 0) == EINVAL and segment(1, 16, 17) == EINVAL
+
+
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="no hipcc")
 def test_voxel_kernels_use_no_scratch():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_isa.py"), "scratch", "voxel.hip"], capture_output=True,

@@ -30,14 +30,32 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "pointnet12_amd", "csrc")
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-DPN2_BUILD"]
-FP_STRICT = {"geometry.hip", "knn.hip", "train.hip", "voxel.hip", "voxel_reduce.hip"}         # built with -ffp-contract=off (csrc/Makefile)
+
+
+def fp_strict_files():
+    """The .hip files csrc/Makefile builds with -ffp-contract=off: the rule whose recipe line carries the flag."""
+    out, target = set(), None
+    for ln in open(os.path.join(CSRC, "Makefile")):
+        m = re.match(r"(\w+)\.o:", ln)
+        if m:
+            target = m.group(1) + ".hip"
+        elif ln.startswith("\t") and "-ffp-contract=off" in ln and target:
+            out.add(target)
+    return out
+
+
+FP_STRICT = fp_strict_files()
+
+
+def flags_for(src):
+    """hipcc flags of one source file, as the library's build gives them."""
+    return FLAGS + (["-ffp-contract=off"] if os.path.basename(src) in FP_STRICT else [])
 
 
 def device_asm(src):
     with tempfile.TemporaryDirectory() as d:
         out = os.path.join(d, "k.s")
-        flags = FLAGS + (["-ffp-contract=off"] if os.path.basename(src) in FP_STRICT else [])
-        subprocess.run(["hipcc"] + flags + ["--cuda-device-only", "-S", src, "-o", out], check=True,
+        subprocess.run(["hipcc"] + flags_for(src) + ["--cuda-device-only", "-S", src, "-o", out], check=True,
                        stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
         return open(out).read()
 
@@ -142,8 +160,7 @@ def check_scratch(files=None):
     for f in sorted(os.listdir(CSRC)):
         if not f.endswith(".hip") or (files and f not in files):
             continue
-        flags = FLAGS + (["-ffp-contract=off"] if f in FP_STRICT else [])
-        err = subprocess.run(["hipcc"] + flags + ["-c", os.path.join(CSRC, f), "-o", os.devnull,
+        err = subprocess.run(["hipcc"] + flags_for(f) + ["-c", os.path.join(CSRC, f), "-o", os.devnull,
                                                   "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True).stderr
         cur = None
         for ln in err.splitlines():

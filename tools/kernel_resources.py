@@ -3,15 +3,19 @@
 
     python tools/kernel_resources.py pointnet12_amd/csrc/mlp_res.hip [extra hipcc flags]
 
+The file is compiled with the flags the library's build gives it (-ffp-contract=off where csrc/Makefile has it).
 Exit status 1 when a kernel uses scratch beyond the allow-list of tools/check_isa.py (a spill in a hand-scheduled kernel).
 """
+import os
 import re
 import subprocess
 import sys
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from check_isa import ALLOWED_SCRATCH, flags_for          # noqa: E402  (the documented spillers and their ceilings; the build's flags)
+
 src = sys.argv[1]
-cmd = ["hipcc", "-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-DPN2_BUILD", "-c", src, "-o", "/dev/null",
-       "-Rpass-analysis=kernel-resource-usage"] + sys.argv[2:]
+cmd = ["hipcc"] + flags_for(src) + ["-c", src, "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"] + sys.argv[2:]
 out = subprocess.run(cmd, capture_output=True, text=True).stderr
 rows, cur = [], None
 for ln in out.splitlines():
@@ -23,9 +27,6 @@ for ln in out.splitlines():
     m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", ln)
     if m and cur is not None:
         cur[m.group(1).strip()] = int(m.group(2))
-import os
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from check_isa import ALLOWED_SCRATCH          # noqa: E402  (the documented spillers and their ceilings)
 bad = 0
 for r in rows:
     name = re.sub(r"\(anonymous namespace\)::", "", r["name"])
