@@ -930,6 +930,63 @@ int pn2_segment_mode(const int32_t *labels, const int32_t *seg, const int64_t *r
                      const int64_t *out_begin, const int64_t *out_count, int32_t fill, int32_t *out_labels, int32_t *votes, int *err,
                      void *workspace, pn2_stream_t stream);
 
+/* ---- Euclidean clustering on the voxel grid (csrc/voxel_cluster.hip), added within ABI 15 (purely additive: no version change) ---------
+ * Connected components of the occupied cells of a pn2_voxel_grid result: an instance id for every voxel and every row.  B clouds in
+ * that call's conventions (device-side row_begin / row_count for the rows, out_begin / out_count for the voxels, a host bound
+ * max_rows of both; every count is read on the device and clamped to [0, max_rows]).  At most eight plain launches on the caller's
+ * stream sized by max_rows; no host synchronisation, no allocation, no thread waits for another thread's write.
+ *   pts, ld, origin, voxel   as pn2_voxel_grid took them;
+ *   out_index  int32  per voxel: its representative row inside the cloud;     n_points  int32 per voxel: its rows;
+ *   vox_labels int32  per voxel or NULL;        inverse  int32 per row (needed for row_component);      row_labels  int32 per row or NULL
+ *              (needs vox_labels);              member   int32[L] on the device or NULL (needs vox_labels and L >= 1).
+ * THE RULE.
+ *   CELL.  A voxel's cell is the cell of its representative row under pn2_voxel_grid's rule (fp64, each operation rounded on its own).
+ *   TAKING PART.  A voxel takes part iff vox_labels is NULL, or vox_labels[v] >= 0 and member is NULL, or vox_labels[v] >= 0 and
+ *     member[vox_labels[v]] != 0.  A label at or beyond L takes no part and raises no error.
+ *   ADJACENCY.  Two voxels of ONE cloud are adjacent iff both take part and their cells differ by a vector d in {-1,0,1}^3 \ {0} with at
+ *     most 1 (connectivity 6), 2 (18) or 3 (26) non-zero entries; with same_label != 0 and vox_labels given their labels must be equal
+ *     too.  A neighbour cell exists only if -2^20 <= q_a + d_a < 2^20 on every axis, checked per axis before a key is formed: the
+ *     cells at the two ends of an axis are no neighbours.  Clouds never share components.
+ *   COMPONENTS.  A component is a connected component of that graph.  Its ROOT is its lowest voxel rank (also its lowest row: ranks
+ *     ascend with the row), its points the sum of n_points over its voxels, its voxels their number, its label the root's label (0
+ *     without vox_labels).  It is KEPT iff points >= min_points and voxels >= min_voxels (host ints >= 1).
+ *   IDS.  The kept components of cloud b get the ids 0 .. comp_count[b] - 1 in ASCENDING ORDER OF THEIR ROOT: a stable compaction.
+ * Outputs (each may be NULL except comp_count; rows and voxels outside the clouds' ranges are not written):
+ *   vox_component int32 per voxel (at out_begin[b] + v): the id, -1 for "takes no part" or "component not kept";
+ *   row_component int32 per row: -1 when inverse < 0, else the voxel's id; with row_labels, a row whose label differs from its voxel's
+ *                 label gets -1.  An `inverse`-style map: pn2_segment_mean / pn2_segment_mode reduce over it with comp_count;
+ *   comp_root (the root's voxel rank), comp_points, comp_voxels, comp_label   int32 per component at comp_begin[b] + id;
+ *   comp_count    int64[B], left on the device.
+ *   Everything is the same from run to run, byte for byte.  Which voxel links to which in the lock-free forest depends on the
+ *   schedule; what is written does not: the partition is a property of the graph, a root is the minimum rank of its part, the counters
+ *   are integer sums and the ids are prefix sums over ranks.
+ * err (device int, caller zeroes, may be NULL) receives bits disjoint from PN2_VOXEL_ERR_* and PN2_SEGMENT_ERR_*:
+ *   PN2_CLUSTER_ERR_INDEX  an out_index outside the cloud's rows (the voxel takes no part) or an inverse at or beyond the voxel count
+ *                          (the row gets -1): skipped, never addressed;
+ *   PN2_CLUSTER_ERR_CELL   a representative row whose cell is invalid: the voxel takes no part;
+ *   PN2_CLUSTER_ERR_CAP    a walk of the forest took more steps than the cloud has voxels (cannot happen: entries only decrease); the
+ *                          thread stopped, the result is not to be used;
+ *   PN2_CLUSTER_ERR_ROWS   an out_count[b] (or, with row_component, a row_count[b]) above max_rows: what lies beyond is ignored.
+ * workspace: pn2_voxel_components_workspace_bytes(B, max_rows) bytes of device memory, 16-byte aligned; it may hold anything on entry
+ * (per cloud: a table of the power of two >= 2 * max_rows slots of 16 bytes, and 25 bytes per voxel).
+ * PN2_EINVAL without a launch: a null pts / row_begin / row_count / origin / voxel / out_begin / out_count / out_index / n_points /
+ * comp_begin / comp_count / workspace, B < 1 or B > 65535, max_rows < 0 or > PN2_VOXEL_MAX_ROWS, ld outside 3..16, a connectivity
+ * other than 6, 18, 26, min_points < 1, min_voxels < 1, member without vox_labels or with L < 1, row_labels without vox_labels,
+ * row_component without inverse, a voxel size that is not finite and > 0, an origin that is not finite, pts not 4-byte or workspace
+ * not 16-byte aligned; pn2_voxel_components_workspace_bytes returns PN2_EINVAL for such B / max_rows. */
+#define PN2_CLUSTER_ERR_INDEX 16
+#define PN2_CLUSTER_ERR_CELL 32
+#define PN2_CLUSTER_ERR_CAP 64
+#define PN2_CLUSTER_ERR_ROWS 128
+int64_t pn2_voxel_components_workspace_bytes(int B, int64_t max_rows);
+int pn2_voxel_components(const float *pts, int ld, const int64_t *row_begin, const int64_t *row_count, int B, int64_t max_rows,
+                         const double *origin, const double *voxel, const int64_t *out_begin, const int64_t *out_count,
+                         const int32_t *out_index, const int32_t *n_points, const int32_t *vox_labels, const int32_t *inverse,
+                         const int32_t *row_labels, int connectivity, int same_label, const int32_t *member, int L, int min_points,
+                         int min_voxels, const int64_t *comp_begin, int32_t *vox_component, int32_t *row_component, int32_t *comp_root,
+                         int32_t *comp_points, int32_t *comp_voxels, int32_t *comp_label, int64_t *comp_count, int *err, void *workspace,
+                         pn2_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

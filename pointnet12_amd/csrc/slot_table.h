@@ -47,6 +47,22 @@ __device__ __forceinline__ int pn2_slot_claim(SlotT *__restrict__ table, unsigne
     return -1;
 }
 
+// The slot that holds `key`, -1 when the table has none: a read-only probe for a LATER launch than the claims (the launch boundary
+// orders it behind them).  It stops at the first empty slot -- a claimed key lies before the first empty slot of its probe sequence,
+// nothing is ever removed -- and is bounded by one pass over the table.
+template <class SlotT>
+__device__ __forceinline__ int pn2_slot_find(const SlotT *__restrict__ table, unsigned mask, unsigned long long key) {
+    static_assert(sizeof(SlotT) == 16 && alignof(SlotT) == 16 && offsetof(SlotT, key) == 0, "one slot is one 16-byte word, the key first");
+    unsigned s = pn2_slot_mix(key) & mask;
+    for (unsigned probe = 0; probe <= mask; ++probe) {
+        const unsigned long long seen = table[s].key;
+        if (seen == key) return (int)s;
+        if (seen == kEmpty) return -1;
+        s = (s + 1) & mask;
+    }
+    return -1;
+}
+
 // an empty slot with the caller's two payload words (the workspace arrives holding garbage)
 __host__ __device__ inline uint4 pn2_slot_empty(unsigned word2, unsigned word3) { return make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, word2, word3); }
 

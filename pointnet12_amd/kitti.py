@@ -214,18 +214,32 @@ def inverse_label_lut(learning_map_inv, device="cuda"):
     return torch.from_numpy(np.array([inv[i] for i in ids], np.int32)).to(torch.device(device))
 
 
-def write_labels(fn, labels):
+def write_labels(fn, labels, instances=None):
     """Write per-point semantic ids in the dataset's ``.label`` format: one little-endian uint32 word per point, the semantic
-    id in the low 16 bits and instance 0 in the high 16 (``np.fromfile(fn, np.uint32) & 0xFFFF`` gives the ids back).
-    ``labels``: an integer array or tensor (either side) of raw ids in 0 .. 65535; a device tensor is read back here."""
-    if isinstance(labels, torch.Tensor):
-        labels = labels.detach().cpu().numpy()
-    ids = np.asarray(labels).reshape(-1)
-    if ids.dtype.kind not in "iu":
-        raise ValueError("write_labels: labels must be integers (got %s)" % ids.dtype)
+    id in the low 16 bits and the instance id in the high 16 (``np.fromfile(fn, np.uint32) & 0xFFFF`` gives the semantic ids back,
+    ``>> 16`` the instances).  ``labels``: an integer array or tensor (either side) of raw ids in 0 .. 65535; ``instances``: None
+    (instance 0 everywhere) or as many integers in 0 .. 65535, e.g. ``label_scan(..., instances=)``'s ``scan_instances``.  A device
+    tensor is read back here."""
+    def host(values, what):
+        if isinstance(values, torch.Tensor):
+            values = values.detach().cpu().numpy()
+        ids = np.asarray(values).reshape(-1)
+        if ids.dtype.kind not in "iu":
+            raise ValueError("write_labels: %s must be integers (got %s)" % (what, ids.dtype))
+        return ids
+
+    ids = host(labels, "labels")
     if ids.size and (int(ids.min()) < 0 or int(ids.max()) > 0xFFFF):
         raise ValueError("write_labels: a semantic id lies outside 0 .. 65535")
-    ids.astype("<u4").tofile(fn)
+    words = ids.astype("<u4")
+    if instances is not None:
+        inst = host(instances, "instances")
+        if inst.size != ids.size:
+            raise ValueError("write_labels: %d instances for %d labels" % (inst.size, ids.size))
+        if inst.size and (int(inst.min()) < 0 or int(inst.max()) > 0xFFFF):
+            raise ValueError("write_labels: an instance id lies outside 0 .. 65535")
+        words = (inst.astype("<u4") << np.uint32(16)) | words
+    words.astype("<u4").tofile(fn)
 
 
 def _upload_words(words, device):

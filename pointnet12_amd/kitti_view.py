@@ -517,6 +517,28 @@ def render_points(pts_3d, labels, colors, camera, point_size=2, background=(0, 0
 
 
 # -------------------------------------------------------------------------------------------------------------------- frame
+class InstanceSpec:
+    """How ``FrameSegmenter.label_scan(instances=)`` makes instances: cells ``voxel_size`` METRES wide (a scalar), ``things`` -- the
+    predicted classes that get instance ids (for SemanticKITTI's shifted training classes ``range(8)``: car .. motorcyclist) --,
+    ``connectivity`` 6 / 18 / 26 and ``min_points``, the fewest rows of an instance (smaller components get no id)."""
+
+    def __init__(self, voxel_size, things, connectivity=26, min_points=1):
+        self.voxel_size, self.things = float(voxel_size), sorted(set(int(t) for t in things))
+        self.connectivity, self.min_points = int(connectivity), int(min_points)
+        if not self.things or self.things[0] < 0 or connectivity not in (6, 18, 26) or self.min_points < 1 or not self.voxel_size > 0:
+            raise ValueError("InstanceSpec: voxel_size > 0, at least one class >= 0 in things, connectivity 6 / 18 / 26, min_points >= 1")
+        self._member = {}
+
+    def member(self, device):
+        """The class set as ``VoxelGrid.components``' ``member``: int32 ``[max(things) + 1]`` on ``device`` (made once)."""
+        key = str(device)
+        if key not in self._member:
+            flags = torch.zeros(self.things[-1] + 1, dtype=torch.int32)
+            flags[self.things] = 1
+            self._member[key] = flags.to(device)
+        return self._member[key]
+
+
 class FrameSegmenter:
     """The body of the reference's frame loop (pcdvis.py:116-144) for one scan ``[M, 4]`` (x, y, z, intensity, as
     ``kitti.read_scan`` returns it): resample to ``npoints`` rows, normalise (``pn2_prepare_clouds``), run ``model`` in eval
@@ -751,7 +773,7 @@ class FrameSegmenter:
         return out
 
     def label_scan(self, raw_scan, raw_label=None, scan_filter=None, rng="numpy", k=5, max_dist=1.0, lut=None, background=None,
-                   choice=None, max_rows=None, voxel=None):
+                   choice=None, max_rows=None, voxel=None, instances=None):
         """``frame_raw``, then a label for EVERY row of the raw scan.  The network labels ``npoints`` rows drawn with
         replacement (about ``exp(-npoints / count)`` of the kept rows are never drawn); here each kept row takes the majority
         label of its ``k`` nearest drawn rows (``pointnet_util.propagate_labels``: queries = the kept rows' xyz with the
@@ -764,7 +786,19 @@ class FrameSegmenter:
         A row drawn several times is a candidate several times and votes once per copy: deliberate, the copies are the
         draw's weights.  With a device generator nothing is read back.  A predicted class outside ``lut`` gives 0 and sets
         ``error_flag``.  ``voxel``: as in ``frame_raw`` -- the network sees the downsampled rows, the queries remain ALL kept
-        rows, so the result means what it meant."""
+        rows, so the result means what it meant.
+
+        ``instances`` (an ``InstanceSpec``): an INSTANCE id for every row as well -- Euclidean clustering per predicted "thing"
+        class, the usual panoptic post-process.  Each kept row's predicted class (the same vote, BEFORE ``lut``; -1 without a voter)
+        is gridded in metres at ``instances.voxel_size`` with the majority class per cell (``VoxelGrid(label_reduce="mode")``), the
+        cells are clustered with ``same_label=True``, ``member=instances.things`` and ``row_labels=`` those classes
+        (``VoxelGrid.components``), and the result gains ``"scan_instances"`` int32 ``[M]``, written at the raw rows like
+        ``scan_labels``: ``id + 1``, 0 for the rows the filter dropped and for rows without an instance (a class outside ``things``, a
+        row that disagrees with its cell's majority, a component below ``min_points``); ``"instance_count"`` (int64 ``[1]`` on the
+        device); ``"kept_classes"`` (int32: the kept rows' predicted classes, the first ``count`` entries mean something) and
+        ``"kept_instances"`` (int32: their ids, -1 for none -- an ``inverse``-style map for ``voxel.segment_mean``).  Ids are numbered by
+        each instance's lowest kept row.  With a device generator nothing is read back.  ``kitti.write_labels(fn, scan_labels,
+        scan_instances)`` writes both halves of the ``.label`` words.  ``instances=None`` leaves this call exactly as it was."""
         from . import pointnet_util as U
         out = self.frame_raw(raw_scan, raw_label, scan_filter, rng, background, choice, max_rows, voxel)
         held = self._raw_state
@@ -781,4 +815,37 @@ class FrameSegmenter:
                            self.pred.view(1, n), k=k, max_dist=max_dist, fill=0, lut=lut, dst=out["index"], out=scan_labels,
                            n_query=out["count"], err=self.error_flag, work=(idx, dist))
         out["scan_labels"] = scan_labels[:M]
+        if instances is not None:
+            self._scan_instances(out, instances, held, idx, dist, k, max_dist, M)
         return out
+
+    def _scan_instances(self, out, spec, held, idx, dist, k, max_dist, M):
+        """``label_scan(instances=)``: the kept rows' classes from the neighbours ``propagate_labels`` left in ``idx`` / ``dist``, the
+        grid, the components, the scatter to the raw rows.  Buffers are kept with the raw state; nothing is read back."""
+        from . import voxel as VX
+        lib, dev = _lib.load(), self.device
+        rows, n = held["rows"], self.npoints
+        work = held.get("instances")
+        if work is None or work["key"] != (rows, spec.voxel_size):
+            grid = VX.VoxelGrid(spec.voxel_size, device=dev, label_reduce="mode")
+            work = held["instances"] = {"key": (rows, spec.voxel_size), "grid": grid, "down": grid.buffers(rows),
+                                        "comp": grid.component_buffers(rows), "classes": torch.empty(rows, device=dev, dtype=torch.int32),
+                                        "scan": torch.empty(rows + 1, device=dev, dtype=torch.int32),
+                                        "row": torch.arange(rows, device=dev, dtype=torch.int64)}
+        classes, grid = work["classes"], work["grid"]
+        classes.fill_(-1)
+        max_d2 = float("inf") if max_dist is None else float(np.float32(float(max_dist) ** 2))
+        # the vote of propagate_labels again, without the lut and the scatter: class per KEPT row (the neighbours are still in idx / dist)
+        _check(lib.pn2_knn_vote(_p(idx), _p(dist), _p(self.pred.view(1, n)), 1, rows, n, k, max_d2, _p(out["count"]), -1, None, 0, None, rows,
+                                _p(classes), _p(self.error_flag), _lib.stream()), "pn2_knn_vote")
+        pts = held["out"].points
+        down = grid.downsample(pts, classes, held["begin"], out["count"], rows, out=work["down"])
+        comps = grid.components(pts, down, row_labels=classes, connectivity=spec.connectivity, same_label=True, member=spec.member(dev),
+                                min_points=spec.min_points, row_begin=held["begin"], row_count=out["count"], max_rows=rows, out=work["comp"])
+        # id + 1 at the raw rows; the kept rows beyond the count go to a spare last entry
+        live = work["row"] < out["count"]
+        scan = work["scan"]
+        scan.zero_()
+        scan.scatter_(0, torch.where(live, out["index"].long().clamp_(0, rows - 1), rows), torch.where(live, comps.row_component + 1, 0))
+        out.update({"scan_instances": scan[:M], "instance_count": comps.count, "kept_classes": classes,
+                    "kept_instances": comps.row_component})

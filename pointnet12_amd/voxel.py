@@ -12,8 +12,16 @@ csrc/voxel_reduce.hip; the rules are in include/pn2.h and, in numpy, in tests/vo
 like everything else here.  ``segment_mean`` / ``segment_mode`` run them over any ``inverse``-style map, ``pool_mean`` is the mean as
 an autograd function.
 
-Out of scope: more than 16 columns per reduction, per-column max / min pooling and grids over more than three key columns.
+``VoxelGrid.components`` / ``euclidean_cluster`` give every voxel and every row an INSTANCE id: Euclidean clustering, the connected
+components of the occupied cells under 6 / 18 / 26 connectivity, optionally per label and per class set (``pn2_voxel_components``,
+csrc/voxel_cluster.hip; the rule is in include/pn2.h and, in numpy, in tests/cluster_ref.py).  The ids are numbered by the
+components' lowest row, the count stays on the device and ``row_component`` is an ``inverse``-style map again:
+``segment_mean(points, row_component, count)`` gives the instances' centroids.
+
+Out of scope: a search radius beyond the 26 neighbouring cells, clustering without a grid (DBSCAN with a density test), ids tracked
+across frames, more than 16 columns per reduction, per-column max / min pooling and grids over more than three key columns.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -56,6 +64,29 @@ class VoxelBuffers:
             self.votes = i32()
 
 
+Components = collections.namedtuple("Components", "row_component voxel_component count root n_points n_voxels label")
+Components.__doc__ = """What ``VoxelGrid.components`` returns, all device tensors: ``row_component`` int32 per row and ``voxel_component``
+int32 per voxel (the id inside the cloud, -1 for none), ``count`` int64 ``[B]``, and per component at ``comp_begin[b] + id``: ``root`` (the
+rank of its lowest voxel), ``n_points``, ``n_voxels`` and ``label`` (int32)."""
+
+
+class ComponentBuffers:
+    """The static buffers of one ``VoxelGrid.components`` call shape (``VoxelGrid.component_buffers``): ``row_component`` /
+    ``voxel_component`` / ``root`` / ``n_points`` / ``n_voxels`` / ``label`` int32 ``[rows]``, ``count`` int64 ``[B]`` and the kernel's
+    ``workspace``."""
+
+    def __init__(self, rows, B, max_rows, device):
+        nbytes = _lib.load().pn2_voxel_components_workspace_bytes(int(B), int(max_rows))
+        if nbytes < 0:
+            raise _lib.Pn2Error("ComponentBuffers: B = %d, max_rows = %d are not supported" % (B, max_rows))
+        self.rows, self.B, self.max_rows = int(rows), int(B), int(max_rows)
+        i32 = lambda: torch.full((self.rows,), -1, device=device, dtype=torch.int32)
+        self.row_component, self.voxel_component = i32(), i32()
+        self.root, self.n_points, self.n_voxels, self.label = i32(), i32(), i32(), i32()
+        self.count = torch.zeros(self.B, device=device, dtype=torch.int64)
+        self.workspace = torch.empty(nbytes, device=device, dtype=torch.uint8)
+
+
 class VoxelGrid:
     """A regular grid of cells ``voxel_size`` wide (a scalar or one size per axis) whose cell 0 starts at ``origin`` (likewise):
     a point p lies in cell ``floor((float64(p) - origin) / voxel_size)`` per axis, and cells from -2**20 to 2**20 - 1 exist.
@@ -70,7 +101,8 @@ class VoxelGrid:
     >= 0, the lowest label among equals, -1 without one (``pn2_segment_mode``; the winner's count is left in the buffers'
     ``votes``).  ``index`` / ``count`` / ``inverse`` / ``n_points`` do not depend on either.  The reductions add
     ``_lib.SEGMENT_ERR_NONFINITE`` to ``error_flag`` (a NaN / inf in a column that is no coordinate: that voxel's mean of that column is
-    NaN) and ``_lib.SEGMENT_ERR_RANGE`` (cannot happen with the grid's own ``inverse``)."""
+    NaN) and ``_lib.SEGMENT_ERR_RANGE`` (cannot happen with the grid's own ``inverse``); ``components`` adds ``_lib.CLUSTER_ERR_*``
+    (none can happen with the grid's own ``downsample`` result and counts within ``max_rows``)."""
 
     def __init__(self, voxel_size, origin=0.0, device="cuda", reduce="first", label_reduce="first"):
         if reduce not in ("first", "mean") or label_reduce not in ("first", "mode"):
@@ -93,6 +125,18 @@ class VoxelGrid:
     def reduces(self):
         """Whether ``downsample`` runs a segment reduction (its buffers then carry ``reduce_workspace``)."""
         return self.reduce == "mean" or self.label_reduce == "mode"
+
+    def _regular_rows(self, points):
+        """``row_begin`` / ``row_count`` of ``[M, ld]`` (one cloud) or ``[B, M, ld]`` points (kept: a second call of the same shape
+        allocates nothing)."""
+        M = int(points.shape[-2])
+        held = getattr(self, "_regular", None)
+        if held is None or held[0] != (points.dim(), int(points.shape[0]), M):
+            nb = 1 if points.dim() == 2 else int(points.shape[0])
+            held = self._regular = ((points.dim(), int(points.shape[0]), M),
+                                    torch.arange(nb, device=self.device, dtype=torch.int64) * M,
+                                    torch.full((nb,), M, device=self.device, dtype=torch.int64))
+        return held[1], held[2]
 
     def downsample(self, points, labels=None, row_begin=None, row_count=None, max_rows=None, out=None, out_begin=None):
         """``(points, labels, index, count, inverse, n_points)`` as device tensors.  ``points``: float32 on the device, ``[M, ld]``
@@ -121,13 +165,7 @@ class VoxelGrid:
         if (row_begin is None) != (row_count is None):
             raise ValueError("VoxelGrid.downsample: row_begin and row_count go together")
         if row_begin is None:
-            held = getattr(self, "_regular", None)                   # (kept: a second call of the same shape allocates nothing)
-            if held is None or held[0] != (points.dim(), int(points.shape[0]), M):
-                nb = 1 if points.dim() == 2 else int(points.shape[0])
-                held = self._regular = ((points.dim(), int(points.shape[0]), M),
-                                        torch.arange(nb, device=self.device, dtype=torch.int64) * M,
-                                        torch.full((nb,), M, device=self.device, dtype=torch.int64))
-            row_begin, row_count = held[1], held[2]
+            row_begin, row_count = self._regular_rows(points)
         B = int(row_begin.numel())
         for t in (row_begin, row_count) + (() if out_begin is None else (out_begin,)):
             if not t.is_cuda or t.dtype != torch.int64 or t.numel() != B or not t.is_contiguous():
@@ -162,9 +200,90 @@ class VoxelGrid:
                                                     p(out.reduce_workspace), _lib.stream()), "pn2_segment_mode")
         return out.points, (out.labels if labels is not None else None), out.index, out.count, out.inverse, out.n_points
 
+    def component_buffers(self, rows, B=1, max_rows=None):
+        """``ComponentBuffers`` for ``components`` calls of ``B`` clouds of at most ``max_rows`` rows each (default ``rows``) whose
+        rows, voxels and components fit ``rows`` entries."""
+        return ComponentBuffers(rows, B, rows if max_rows is None else max_rows, self.device)
+
+    def components(self, points, down, row_labels=None, connectivity=26, same_label=True, member=None, min_points=1, min_voxels=1,
+                   row_begin=None, row_count=None, max_rows=None, out_begin=None, comp_begin=None, out=None):
+        """Euclidean clustering of a ``downsample`` result (``pn2_voxel_components``; the rule of include/pn2.h): the connected
+        components of the occupied cells, as ``Components`` of device tensors.
+
+        ``points``, ``row_begin`` / ``row_count`` / ``max_rows`` / ``out_begin``: what ``downsample`` was called with; ``down``: what it
+        returned (its ``labels``, if any, are the voxels' labels).  Two voxels of one cloud are adjacent iff both TAKE PART and their
+        cells differ by at most 1 on every axis, in at most 1 / 2 / 3 axes for ``connectivity`` 6 / 18 / 26, and -- with
+        ``same_label`` and labelled voxels -- carry the same label.  A labelled voxel takes part iff its label is >= 0 and, with
+        ``member`` (int32 ``[L]`` on the device, or a host sequence of L flags that is uploaded here), ``member[label] != 0``; a label
+        at or beyond L takes no part.  A component is kept iff it has at least ``min_points`` rows and ``min_voxels`` voxels; the kept
+        ones get ids 0 .. ``count[b]`` - 1 in ascending order of their lowest voxel (= lowest row).
+
+        ``voxel_component`` (int32 at ``out_begin[b] + v``): the id, -1 for a voxel that takes no part or whose component is not kept.
+        ``row_component`` (int32 per row): its voxel's id, -1 for a row the grid dropped and, with ``row_labels`` (int32 per row;
+        needs labelled voxels), for a row whose label differs from its voxel's.  It is an ``inverse``-style map:
+        ``segment_mean(points, row_component, count)`` gives the centroids, ``segment_mode`` the majority class.  ``root`` /
+        ``n_points`` / ``n_voxels`` / ``label`` (int32 at ``comp_begin[b] + id``; ``comp_begin``: int64 ``[B]`` on the device, None:
+        ``out_begin``): the component's lowest voxel rank, its rows, its voxels and its root's label (0 without labels).  ``count`` is
+        int64 ``[B]`` and stays on the device.  Entries outside those ranges are not written (-1 in buffers made here).
+
+        With ``out`` (``component_buffers``), device-side ``member`` and ``row_begin`` / ``row_count`` given (or the ``[B, M, ld]``
+        form) the call allocates nothing, reads nothing back and can be captured in a graph that stays valid when the counts
+        change.  ``error_flag`` is NOT cleared here: it goes on collecting after ``downsample``.  Byte-identical from run to run."""
+        if not isinstance(points, torch.Tensor) or not points.is_cuda:
+            raise _lib.Pn2Error("VoxelGrid.components: points must live on the GPU: this package has no CPU path")
+        if points.dtype != torch.float32 or points.dim() not in (2, 3) or not 3 <= points.shape[-1] <= 16 or not points.is_contiguous():
+            raise ValueError("VoxelGrid.components: points must be a contiguous float32 [M, ld] or [B, M, ld] tensor, 3 <= ld <= 16")
+        if connectivity not in (6, 18, 26):
+            raise ValueError("VoxelGrid.components: connectivity is 6, 18 or 26")
+        if int(min_points) < 1 or int(min_voxels) < 1:
+            raise ValueError("VoxelGrid.components: min_points and min_voxels are at least 1")
+        ld, M = int(points.shape[-1]), int(points.shape[-2])
+        rows = M if points.dim() == 2 else int(points.shape[0]) * M
+        _, vox_labels, index, count, inverse, n_points = down
+        if (row_begin is None) != (row_count is None):
+            raise ValueError("VoxelGrid.components: row_begin and row_count go together")
+        if row_begin is None:
+            row_begin, row_count = self._regular_rows(points)
+        B = int(row_begin.numel())
+        out_begin = row_begin if out_begin is None else out_begin
+        comp_begin = out_begin if comp_begin is None else comp_begin
+        for t in (row_begin, row_count, out_begin, comp_begin, count):
+            if not t.is_cuda or t.dtype != torch.int64 or t.numel() != B or not t.is_contiguous():
+                raise ValueError("VoxelGrid.components: row_begin, row_count, out_begin, comp_begin and the voxel count must be "
+                                 "int64 [B] device tensors")
+        for name, t, need in (("index", index, True), ("inverse", inverse, True), ("n_points", n_points, True),
+                              ("the voxels' labels", vox_labels, False), ("row_labels", row_labels, False)):
+            if t is None and not need:
+                continue
+            if t is None or not t.is_cuda or t.dtype != torch.int32 or t.numel() < rows or not t.is_contiguous():
+                raise ValueError("VoxelGrid.components: %s must be a contiguous int32 device tensor of at least %d entries" % (name, rows))
+        if vox_labels is None and (row_labels is not None or member is not None):
+            raise ValueError("VoxelGrid.components: row_labels and member need labelled voxels (downsample with labels)")
+        if member is not None and not isinstance(member, torch.Tensor):
+            member = torch.tensor([1 if m else 0 for m in member], device=self.device, dtype=torch.int32)
+        if member is not None and (not member.is_cuda or member.dtype != torch.int32 or member.dim() != 1 or member.numel() < 1 or
+                                   not member.is_contiguous()):
+            raise ValueError("VoxelGrid.components: member must be a contiguous int32 [L] device tensor")
+        max_rows = M if max_rows is None else int(max_rows)
+        if out is None:
+            out = ComponentBuffers(rows, B, max_rows, self.device)
+        elif out.B != B or out.max_rows < max_rows or out.rows < rows:
+            raise ValueError("VoxelGrid.components: out was made for B = %d, max_rows = %d, %d rows" % (out.B, out.max_rows, out.rows))
+        p = _lib.ptr
+        dp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        # (max_rows as the buffers were made for: the workspace layout follows it)
+        _lib.check(_lib.load().pn2_voxel_components(p(points), ld, p(row_begin), p(row_count), B, out.max_rows, dp(self.origin),
+                                                    dp(self.voxel_size), p(out_begin), p(count), p(index), p(n_points), p(vox_labels),
+                                                    p(inverse), p(row_labels), int(connectivity), 1 if same_label else 0, p(member),
+                                                    0 if member is None else int(member.numel()), int(min_points), int(min_voxels),
+                                                    p(comp_begin), p(out.voxel_component), p(out.row_component), p(out.root),
+                                                    p(out.n_points), p(out.n_voxels), p(out.label), p(out.count), p(self.error_flag),
+                                                    p(out.workspace), _lib.stream()), "pn2_voxel_components")
+        return Components(out.row_component, out.voxel_component, out.count, out.root, out.n_points, out.n_voxels, out.label)
+
     def check(self):
         """Reads ``error_flag`` back: ``ValueError`` for a row outside the grid (or not finite), for a ``row_count`` above
-        ``max_rows`` and for the reductions' two bits."""
+        ``max_rows``, for the reductions' two bits and for the clustering's four."""
         flag = int(self.error_flag.item())
         if flag & _lib.VOXEL_ERR_RANGE:
             raise ValueError("VoxelGrid: a row has a non-finite coordinate or lies outside the grid's 2**21 cells per axis")
@@ -174,6 +293,31 @@ class VoxelGrid:
             raise ValueError("VoxelGrid: a voxel's mean met a NaN or an infinity (that column of that voxel is NaN)")
         if flag & _lib.SEGMENT_ERR_RANGE:
             raise ValueError("VoxelGrid: a row names a voxel at or beyond the voxel count")
+        if flag & _lib.CLUSTER_ERR_INDEX:
+            raise ValueError("VoxelGrid.components: a voxel names a row outside its cloud, or a row a voxel at or beyond the voxel count")
+        if flag & _lib.CLUSTER_ERR_CELL:
+            raise ValueError("VoxelGrid.components: a voxel's representative row lies outside the grid (or is not finite)")
+        if flag & _lib.CLUSTER_ERR_CAP:
+            raise ValueError("VoxelGrid.components: a walk of the component forest hit its cap: the result is not to be used")
+        if flag & _lib.CLUSTER_ERR_ROWS:
+            raise ValueError("VoxelGrid.components: a voxel count or row_count is above max_rows")
+
+
+def euclidean_cluster(points, labels=None, voxel_size=0.1, origin=0.0, label_reduce="mode", connectivity=26, same_label=True, member=None,
+                      min_points=1, min_voxels=1, row_begin=None, row_count=None, max_rows=None):
+    """Euclidean clustering in one call: ``VoxelGrid(voxel_size, origin, label_reduce=).downsample(points, labels, ...)``, then
+    ``components`` with ``row_labels=labels``.  ``points``: float32 ``[M, ld]`` on the device (one cloud, or B clouds back to back with
+    ``row_begin`` / ``row_count`` / ``max_rows``) or ``[B, M, ld]``; ``labels``: int32 per row or None (then every voxel takes part and
+    ``member`` must be None).  Returns ``(components, down, grid)``: the ``Components``, what ``downsample`` returned and the grid (its
+    ``check()`` reads the error bits back).  A row's instance id is ``components.row_component``; every call allocates its buffers --
+    a loop over frames holds a ``VoxelGrid`` and its two buffer sets instead."""
+    if not isinstance(points, torch.Tensor) or not points.is_cuda:
+        raise _lib.Pn2Error("euclidean_cluster: points must live on the GPU: this package has no CPU path")
+    grid = VoxelGrid(voxel_size, origin, device=points.device, label_reduce=label_reduce)
+    down = grid.downsample(points, labels, row_begin, row_count, max_rows)
+    comps = grid.components(points, down, row_labels=labels, connectivity=connectivity, same_label=same_label, member=member,
+                            min_points=min_points, min_voxels=min_voxels, row_begin=row_begin, row_count=row_count, max_rows=max_rows)
+    return comps, down, grid
 
 
 def expand(values, inverse, fill):

@@ -2,7 +2,7 @@
 """One frame of the reference's KITTI demo (``python pcdvis.py``) on the HIP library: scan -> labels -> pixels -> two images,
 three with ``--ego``.
 
-    python tools/demo_kitti.py [--out DIR] [--npoints 25000] [--seed 0] [--merge] [--time] [--raw [--labels-out FILE]] [--ego CAMERA.json [--render-option FILE.json]]
+    python tools/demo_kitti.py [--out DIR] [--npoints 25000] [--seed 0] [--merge] [--time] [--raw [--labels-out FILE [--instances SIZE]]] [--ego CAMERA.json [--render-option FILE.json]]
     python tools/demo_kitti.py --root $KITTI_ROOT --part 01 --index 0 --calib DIR --config semantic-kitti.yaml [--checkpoint CKPT]
 
 Without ``--root`` the scan is synthetic (``synthetic.kitti_cloud``, un-normalised back to metres), the calibration is the one
@@ -22,6 +22,10 @@ no label file (a live feed), a dataset scan goes in with its ``.label`` words.  
 ``--labels-out FILE`` (with ``--raw``, without ``--merge``) goes through ``FrameSegmenter.label_scan`` instead: every row of the
 raw scan takes the majority label of its 5 nearest drawn rows within 1 m, mapped back to the dataset's raw ids
 (``kitti.inverse_label_lut``), rows the filter dropped are 0, and FILE is written in the dataset's ``.label`` format.
+``--instances SIZE`` (with ``--labels-out``) fills the words' HIGH halves too: the kept rows' predicted classes are gridded at SIZE
+metres and the cells of the "thing" classes (training classes 0 .. 7: car .. motorcyclist) are clustered per class under 26
+connectivity (``kitti_view.InstanceSpec``, ``voxel.VoxelGrid.components``, ``pn2_voxel_components``); a row's instance is ``id + 1``, 0
+for none, and the low halves are what they are without the option, byte for byte.
 ``--voxel SIZE`` (with ``--raw``) downsamples the kept rows to one row per occupied cell of SIZE metres before the choice
 (``voxel.VoxelGrid``, ``pn2_voxel_grid``), which is then drawn from the voxel count.  ``--voxel-reduce mean`` shows each cell's mean row
 (centroid and mean remission, ``pn2_segment_mean``) instead of its first, ``--voxel-labels mode`` takes the cell's majority label.
@@ -202,6 +206,8 @@ def main():
     ap.add_argument("--time", action="store_true")
     ap.add_argument("--raw", action="store_true", help="feed the raw scan through frame_raw: filter and compaction on the device")
     ap.add_argument("--labels-out", metavar="FILE", help="with --raw: label every row of the scan (label_scan) and write a .label file")
+    ap.add_argument("--instances", type=float, metavar="SIZE",
+                    help="with --labels-out: Euclidean clustering of the thing classes on a grid of SIZE metres; instance ids in the high halves")
     ap.add_argument("--voxel", type=float, metavar="SIZE", help="with --raw: voxel-grid downsample the kept rows at SIZE metres")
     ap.add_argument("--voxel-reduce", choices=("first", "mean"), default="first",
                     help="with --voxel: a cell is shown by its first row or by the mean of its rows")
@@ -238,6 +244,8 @@ def main():
         ap.error("--render-option needs --ego")
     if args.labels_out and (not args.raw or args.merge):
         ap.error("--labels-out needs --raw and does not go with --merge (merged classes have no raw id)")
+    if args.instances is not None and not args.labels_out:
+        ap.error("--instances needs --labels-out")
     if args.voxel is None and (args.voxel_reduce != "first" or args.voxel_labels != "first"):
         ap.error("--voxel-reduce / --voxel-labels need --voxel")
     if args.voxel is not None and not args.raw:
@@ -257,9 +265,13 @@ def main():
             grid = voxel.VoxelGrid(args.voxel, reduce=args.voxel_reduce, label_reduce=args.voxel_labels)
         if args.labels_out:
             out = seg.label_scan(scan, words, scan_filter=scan_filter, rng=gen, lut=kitti.inverse_label_lut(cfg["learning_map_inv"]),
-                                 background=frame, voxel=grid)
-            kitti.write_labels(args.labels_out, out["scan_labels"])
+                                 background=frame, voxel=grid,
+                                 instances=None if args.instances is None else V.InstanceSpec(args.instances, range(8)))
+            kitti.write_labels(args.labels_out, out["scan_labels"], out.get("scan_instances"))
             print("labelled %d of %d rows; wrote %s" % (int((out["scan_labels"] != 0).sum()), len(scan), args.labels_out))
+            if args.instances is not None:
+                print("%d instances of the thing classes on %d rows (cells of %g m)"
+                      % (int(out["instance_count"].item()), int((out["scan_instances"] != 0).sum()), args.instances))
         else:
             out = seg.frame_raw(scan, words, scan_filter=scan_filter, rng=gen, background=frame, voxel=grid)
         print("raw scan of %d rows, %d kept by the device filter; filter error flag %d"
