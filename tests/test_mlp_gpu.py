@@ -9,6 +9,8 @@ import torch.nn.functional as F
 from pointnet12_amd import _lib
 from pointnet12_amd import pointnet_util as U
 
+from mlp_ref import fixed_layer_case as _fixed_layer_case, rel as _rel
+
 pytestmark = pytest.mark.gpu
 
 
@@ -593,59 +595,6 @@ def _pooled_cf_case(dev, lib, st, P, co, ci, Kp):
                            affp.data_ptr(), dX.data_ptr(), ci, red.data_ptr(), dW2.data_ptr(), ci, P, co, ci, None, scratch.data_ptr(), st)
     torch.cuda.synchronize()
     assert torch.equal(dW, dW2)
-
-
-def _fixed_layer_case(dev, P, co, ci, Kp, seed):
-    """Fixed operands of ONE layer's backward with no decision in the path that rounding could flip: dZ (dense, or the pooled pair),
-    Y, the coefficient block, the weight, the previous layer's pre-BN output and affine block -- and the fp64 statement of
-    dY = c0 dZ + q1 (y - mean) + q0, dX = (dY W) o mask, dW = dY^T X, the two reductions of the masked dX."""
-    g = torch.Generator(device=dev).manual_seed(seed)
-    rnd = lambda *s_: torch.randn(*s_, device=dev, generator=g)
-    ldc, ldp = (co + 3) & ~3, (ci + 3) & ~3
-    Y = torch.zeros(P, ldc, device=dev)
-    Y[:, :co] = rnd(P, co)
-    Yp = torch.zeros(P, ldp, device=dev)
-    Yp[:, :ci] = rnd(P, ci) * 1.5 + 0.3
-    affp = torch.zeros(4 * ldp, device=dev)
-    affp[:ci] = rnd(ci) * 0.2
-    affp[ldp:ldp + ci] = (rnd(ci) * 0.5).abs() + 0.3
-    affp[2 * ldp:2 * ldp + ci] = rnd(ci) * 0.3
-    affp[3 * ldp:3 * ldp + ci] = (rnd(ci) * 0.2).abs() + 0.8
-    W = rnd(co, ci) * 0.2
-    coef = torch.zeros(4 * ldc, device=dev)
-    coef[:co] = rnd(co) * 0.5 + 1.0
-    coef[ldc:ldc + co] = rnd(co) * 1e-3
-    coef[2 * ldc:2 * ldc + co] = rnd(co) * 1e-3
-    coef[3 * ldc:3 * ldc + co] = rnd(co) * 0.3
-    if Kp:
-        G = P // Kp
-        dzp = torch.zeros(G, ldc, device=dev)
-        dzp[:, :co] = rnd(G, co)
-        arg = torch.randint(0, Kp, (G, ldc), device=dev, dtype=torch.int32, generator=g)
-        D = torch.zeros(G, Kp, co, device=dev, dtype=torch.float64)
-        D.scatter_(1, arg[:, :co].long().unsqueeze(1), dzp[:, :co].double().unsqueeze(1))
-        D = D.view(P, co)
-        dz_args = (None, 0, dzp.data_ptr(), ldc, arg.data_ptr(), Kp)
-        keep = (dzp, arg)
-    else:
-        dZ = torch.zeros(P, ldc, device=dev)
-        dZ[:, :co] = rnd(P, co)
-        D = dZ[:, :co].double()
-        dz_args = (dZ.data_ptr(), ldc, None, 0, None, 0)
-        keep = (dZ,)
-    mean, scale, beta, invstd = (affp[i * ldp:i * ldp + ci] for i in range(4))
-    z = (Yp[:, :ci] - mean).double() * scale.double() + beta.double()
-    X = torch.clamp(z, min=0).float().double()
-    c0, q1, q0, mu = (coef[i * ldc:i * ldc + co].double() for i in range(4))
-    dY = c0 * D + q1 * (Y[:, :co].double() - mu) + q0
-    dX = (dY @ W.double()) * (z > 0)
-    xhat = (Yp[:, :ci] - mean).double() * invstd.double()
-    ref = {"dX": dX, "dW": dY.t() @ X, "r0": dX.sum(0), "r1": (dX * xhat).sum(0)}
-    return dict(Y=Y, Yp=Yp, affp=affp, W=W, coef=coef, dz_args=dz_args, keep=keep, ldc=ldc, ldp=ldp), ref
-
-
-def _rel(a, b):
-    return float((a.double() - b).abs().max()) / max(float(b.abs().max()), 1e-30)
 
 
 @pytest.mark.gpu
