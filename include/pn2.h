@@ -168,6 +168,9 @@ int pn2_group_bwd(const float *grad_rows, const int64_t *idx, int B, int N, int 
  * or 64, B*S*K a multiple of 64; otherwise PN2_EUNSUPPORTED and nothing is launched): X [B*S*K, ldx] receives the grouped
  * rows exactly as pn2_group writes them (the backward's weight gradient reads them), Y [B*S*K, ldy] = X W^T + bias with
  * W [C_out, 3 + D] as stored (pitch ldw), stats (may be NULL) the per-channel sums like pn2_conv1x1_fwd.
+ * Refused as well: ldx > 12, idx or new_xyz NULL.  Every column of X up to the pitch is written: the centred coordinates are
+ * fp32(xyz_j - c_s), one rounding, the features copies, the pad columns [3 + D, ldx) zero.  Of Y only the columns [0, C_out)
+ * are written; [C_out, ldy) are left alone.  Y has the same bits with and without stats.
  * model/pointnet_util.py:127-131 + :197, :243-247 + :254. */
 int pn2_group_conv_fwd(const float *xyz, const float *points, const float *new_xyz, const int64_t *idx, int B, int N, int S,
                        int K, int D, int xyz_first, const float *W, int ldw, const float *bias, float *X, int ldx, float *Y, int ldy,
@@ -425,10 +428,17 @@ int pn2_conv1x1_bwd(const float *dZ, int ldz, const float *dZp, int ldo, const i
  * Input: X != NULL: plain rows [P, ldx] with P passed in `B` (FP modules, heads);  X == NULL: grouped rows formed on the
  * fly from idx [B,S,Knb] (xyz [B,N,3] minus new_xyz [B,S,3], cat with points [B,N,D]; xyz_first as pn2_group;
  * idx == NULL with S == 1, Knb == N, new_xyz == NULL: group_all, un-centred).  pool: 0 (out [P, ldo], ReLU applied) or
- * Knb (out [P / Knb, ldo]); Knb must be 16 or a multiple of 32.  L <= 4; activations of a 32-row tile stay in LDS.
- * Deviation from the reference: ReLU is fmaxf(x, 0) and the pooling an integer atomicMax on the bits of the non-negative
- * result, both of which DROP a NaN activation (torch.relu / torch.max propagate it).  A diverged model therefore shows
- * finite pooled features here; the training-mode path (pn2_bn_relu_max) and the un-pooled outputs keep NaNs visible. */
+ * Knb (out [P / Knb, ldo]); Knb must be 16 or a multiple of 32.  L <= 4; activations of a 32-row tile stay in LDS: two
+ * tiles of 32 x LP floats in 160 KiB, LP the least pitch = 4 mod 8 that holds round4(widest layer input) columns, i.e.
+ * every K_l <= 636 (LP 636); wider chains are PN2_EINVAL.
+ * Columns written: pool == 0, 16 and 32 write the columns [0, N_L) of their rows and nothing else.  pool > 32 first
+ * zero-fills the WHOLE rows, (P / pool) * ldo floats (the target of the integer atomicMax), so there the columns
+ * [N_L, ldo) end as 0.  Rows behind P (pool == 0) or P / pool are never touched.
+ * NaN.  The hidden layers and the un-pooled store (pool == 0) apply ReLU as x < 0 ? 0 : x, which keeps a NaN like
+ * torch.relu: a NaN in an input row makes that whole output row NaN and moves no other row.  Deviation from the reference,
+ * pooled outputs only: the max over the neighbours is fmaxf followed by an integer atomicMax on the bits of the non-negative
+ * result, both of which DROP a NaN (torch.max propagates it).  A diverged model therefore shows finite pooled features
+ * here; the training-mode path (pn2_bn_relu_max) and the un-pooled outputs keep NaNs visible. */
 typedef struct {
     const float *W;
     const float *bias;

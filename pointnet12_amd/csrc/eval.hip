@@ -30,14 +30,18 @@ struct EvalInput {
 
 extern __shared__ __attribute__((aligned(16))) float ev_lds[];
 
+// ReLU as torch.relu has it: a NaN stays a NaN (fmaxf(x, 0) would return 0).  Hidden layers and the un-pooled store use this
+// form, so a NaN input row shows as a NaN output row; the pooled epilogue keeps fmaxf (its integer atomicMax needs v >= 0).
+__device__ __forceinline__ float ev_relu(float x) { return x < 0.f ? 0.f : x; }
+
 __global__ __launch_bounds__(EV_THREADS) void fused_eval_kernel(EvalInput in, EvalArgs ar, int pool, float *__restrict__ out, int ldo,
                                                                int64_t P, int LP) {
     float *bufA = ev_lds, *bufB = ev_lds + EV_ROWS * LP;           // [32][LP], LP = 4 mod 8: conflict-free ds_read_b128
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, lh = lane >> 5;
     const int64_t m0 = (int64_t)blockIdx.x * EV_ROWS;
 
-    // ---- input rows -> bufA, zero padded to round8(K_0) columns
-    const int K0 = ar.K[0], K0p = (K0 + 7) & ~7;
+    // ---- input rows -> bufA, zero padded to round4(K_0) columns (a row holds no more: LP may equal round4(K_0))
+    const int K0 = ar.K[0], K0p = (K0 + 3) & ~3;
     {
         const int r = t >> 3, c0 = t & 7;                          // 8 threads per row
         const int64_t m = m0 + r;
@@ -68,7 +72,7 @@ __global__ __launch_bounds__(EV_THREADS) void fused_eval_kernel(EvalInput in, Ev
 
     float *src = bufA, *dstb = bufB;
     for (int l = 0; l < ar.L; ++l) {
-        const int K8 = (ar.K[l] + 7) & ~7, N = ar.N[l], ldw = ar.ldw[l];
+        const int K4 = (ar.K[l] + 3) & ~3, nfull = K4 >> 3, N = ar.N[l], ldw = ar.ldw[l];   // a row holds round4(K) columns
         const bool last = l == ar.L - 1;
         const float *W = ar.W[l], *bias = ar.bias[l];
         const int nblk = (N + 31) >> 5;
@@ -80,7 +84,7 @@ __global__ __launch_bounds__(EV_THREADS) void fused_eval_kernel(EvalInput in, Ev
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.f;
             int kb = 0;
-            for (; kb + 4 <= K8 / 8; kb += 4) {                    // four weight quads in flight per lane
+            for (; kb + 4 <= nfull; kb += 4) {                      // four weight quads in flight per lane
                 float4 b[4], a[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) b[u] = ld4(wrow + 8 * (kb + u));
@@ -94,7 +98,7 @@ __global__ __launch_bounds__(EV_THREADS) void fused_eval_kernel(EvalInput in, Ev
                     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u].w, b[u].w, acc, 0, 0, 0);
                 }
             }
-            for (; kb < K8 / 8; ++kb) {
+            for (; kb < nfull; ++kb) {
                 const float4 b = ld4(wrow + 8 * kb);
                 const float4 a = *reinterpret_cast<const float4 *>(arow + 8 * kb);
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
@@ -102,18 +106,26 @@ __global__ __launch_bounds__(EV_THREADS) void fused_eval_kernel(EvalInput in, Ev
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
             }
+            if (K4 & 4) {                                          // a last step of four columns: the upper half-wave's quad would
+                const float4 b = ld4(wrow + 8 * kb);               // lie behind the row (all padding), so it multiplies by zero unread
+                const float4 a = lh == 0 ? *reinterpret_cast<const float4 *>(arow + 8 * kb) : make_float4(0.f, 0.f, 0.f, 0.f);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
+            }
             const float bc = col < N ? bias[col] : 0.f;
-            if (!last) {                                           // relu -> the other buffer (pad columns up to round8(N): zero)
+            if (!last) {                                           // relu -> the other buffer (pad columns up to round4(N): zero)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    if (col < ((N + 7) & ~7)) dstb[row * LP + col] = col < N ? fmaxf(acc[r] + bc, 0.f) : 0.f;   // (a row holds round8(N) columns)
+                    if (col < ((N + 3) & ~3)) dstb[row * LP + col] = col < N ? ev_relu(acc[r] + bc) : 0.f;   // (a row holds round4(N) columns)
                 }
             } else if (pool == 0) {                                // FP / head: rows out
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int64_t m = m0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    if (m < P && col < N) out[m * ldo + col] = fmaxf(acc[r] + bc, 0.f);
+                    if (m < P && col < N) out[m * ldo + col] = ev_relu(acc[r] + bc);
                 }
             } else {                                               // SA: max over the rows of a group (relu(max) = max(relu))
                 float m_lo = -INFINITY, m_hi = -INFINITY;          // rows 0..15 / 16..31 of the tile (registers 0..7 / 8..15)
@@ -150,19 +162,18 @@ extern "C" int pn2_fused_eval(const float *X, int ldx, const float *xyz, const f
     PN2_CHECK_ARG(pool == 0 || (pool == Knb && (pool == 16 || pool % 32 == 0)));
     EvalArgs ar;
     ar.L = L;
-    int cmax = 8;
+    int cmax = 4;                                                  // widest layer input, rounded up to 4 columns
     for (int l = 0; l < L; ++l) {
         PN2_CHECK_ARG(layers[l].W && layers[l].bias && layers[l].K > 0 && layers[l].N > 0 && layers[l].ldw >= ((layers[l].K + 7) & ~7) &&
                       (reinterpret_cast<uintptr_t>(layers[l].W) & 15) == 0 && layers[l].ldw % 4 == 0);
         PN2_CHECK_ARG(l == 0 || layers[l].K == layers[l - 1].N);
         ar.W[l] = layers[l].W; ar.bias[l] = layers[l].bias; ar.K[l] = layers[l].K; ar.N[l] = layers[l].N; ar.ldw[l] = layers[l].ldw;
-        const int k8 = (layers[l].K + 7) & ~7;
-        if (k8 > cmax) cmax = k8;
-        if (l + 1 < L && ((layers[l].N + 7) & ~7) > cmax) cmax = (layers[l].N + 7) & ~7;
+        const int k4 = (layers[l].K + 3) & ~3;                     // (K_l = N_{l-1}: the hidden outputs are covered)
+        if (k4 > cmax) cmax = k4;
     }
     PN2_CHECK_ARG(X != nullptr ? layers[0].K <= ldx : layers[0].K == 3 + D);
     PN2_CHECK_ARG(ldo >= layers[L - 1].N);
-    const int LP = cmax + 4;
+    const int LP = cmax % 8 == 4 ? cmax : cmax + 4;                // the least pitch = 4 mod 8 that holds a row
     const size_t lds = sizeof(float) * 2 * EV_ROWS * LP;
     PN2_CHECK_ARG(lds <= 160 * 1024);
     const int64_t P = X ? (int64_t)B : (int64_t)B * S * Knb;      // plain rows: the caller passes the row count in B

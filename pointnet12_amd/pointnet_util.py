@@ -1290,7 +1290,8 @@ def _fused_eval_ok(c_in, convs, pool):
     if pool not in (0, 16) and pool % 32:
         return False
     widths = [c_in] + [c.weight.shape[0] for c in convs[:-1]]
-    return max((w + 7) & ~7 for w in widths) + 4 <= 160 * 1024 // (2 * 32 * 4)
+    c4 = max((w + 3) & ~3 for w in widths)         # as the launcher: two [32][LP] tiles, LP the least pitch = 4 mod 8
+    return (c4 if c4 % 8 == 4 else c4 + 4) <= 160 * 1024 // (2 * 32 * 4)
 
 
 def fused_eval_rows(rows, c_in, convs, bns, pool):

@@ -772,9 +772,10 @@ def test_fused_eval_follows_training(dev):
 
 @pytest.mark.parametrize("K,co,D,xyz_first", [(16, 32, 6, False), (32, 64, 6, True), (64, 64, 3, False), (32, 64, 9, False)])
 def test_gather_conv_first_layer_equals_group_then_gemm(dev, K, co, D, xyz_first):
-    """pn2_group_conv_fwd (gather + first conv in one launch, the sa1 stacks) against pn2_group followed by the GEMM: same
-    grouped rows bit for bit, outputs and every gradient (weights, BatchNorm, the gathered features) within the GEMM-vs-fma
-    rounding of the first layer."""
+    """pn2_group_conv_fwd (gather + first conv in one launch, the sa1 stacks) against pn2_group followed by the GEMM, through
+    the module: outputs and every gradient (weights, BatchNorm, the gathered features) within the GEMM-vs-fma rounding of the
+    first layer.  The grouped rows themselves are not compared here: that X is bit-equal to the float32 statement, and Y within
+    an fp64 bound at every trip count of the persistent loop, is asserted in tests/test_group_conv_gpu.py."""
     import torch.nn as nn
     from pointnet12_amd import _lib
     gen = torch.Generator().manual_seed(K + co + D)
