@@ -261,9 +261,11 @@ def _pruned_case(N, S, kind):
 
 
 def test_fps_spatially_pruned_kernel_small_clouds_forced():
-    """The pruned kernel is slower than the plain one up to N = 8192 and not dispatched there; PN2_FPS_PRUNE=2 (read once
-    per process: a child process) forces it, so its 512-thread / 8-points-per-thread instantiations and clouds with EMPTY
-    waves (N far below the capacity) are checked against the oracle too."""
+    """The pruned kernel is slower than the plain one up to N = 8192 and not dispatched there; option FPS_PRUNE = 2 forces it,
+    so its 512-thread / 8-points-per-thread instantiations and clouds with EMPTY waves (N far below the capacity) are checked
+    against the oracle too.  The library never reads the environment and an option takes effect with the next call: the
+    child process is there for the Python binding, which forwards PN2_FPS_PRUNE=2 from ITS environment to pn2_set_option
+    once, when it loads the library (_lib.forward_env_options) -- the way A/B runs select a route."""
     import subprocess
     import sys
     import torch

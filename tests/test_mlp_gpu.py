@@ -71,7 +71,7 @@ def test_shared_mlp_negative_and_zero_gamma(dev, P, pool, chans):
     gamma in U(-1.5, 1.5) every branch of both selections is taken by some channel, and all of them are held to the fp64
     evaluation (not to each other)."""
     old = _lib.options()["PN2_POOL_CF"]
-    _lib.set_option("PN2_POOL_CF", 2)               # (the 128 x 64 output-free form too: off by default, measured slower than the Y-reading one)
+    _lib.set_option("PN2_POOL_CF", 2)               # (the 128 x 64 output-free form too: the default, PN2_POOL_CF = 2; set here so that the test says what it tests)
     try:
         _check_shared_mlp(dev, P, pool, chans, "signed")
     finally:
