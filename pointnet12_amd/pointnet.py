@@ -20,7 +20,7 @@ import torch.nn.functional as F
 from . import _lib
 from ._lib import check as _check, ptr as _p
 from .loss import nll_loss
-from .pointnet_util import (_REPL, _channel_last, _contig_weight, _empty_rows, _gpu_f32, _ident_coef, _r4, _zeros_small,
+from .pointnet_util import (_REPL, _UpGrad, _carve, _channel_last, _contig_weight, _empty_rows, _gpu_f32, _r4,
                             bump_param_generation, conv1x1, log_softmax_rows, shared_mlp)
 
 
@@ -93,9 +93,7 @@ class _ConvBnMax(torch.autograd.Function):
         co, ci = w.shape[0], w.shape[1]
         G = P // N
         eps, mom = cfg
-        zb = _zeros_small(8 * _REPL * 2 * co + 16 * _r4(co), dev)
-        stats = zb[:8 * _REPL * 2 * co].view(torch.float64)
-        aff = zb[8 * _REPL * 2 * co:].view(torch.float32)
+        stats, aff = _carve(dev, [(torch.float64, _REPL * 2 * co), (torch.float32, 4 * _r4(co))])
         y = _empty_rows(P, co, dev)
         _check(lib.pn2_conv1x1_fwd(_p(x), ldx, None, _p(_contig_weight(w)), ci, _p(b), _p(y), y.shape[1], P, ci, co,
                                    _p(stats) if training else None, None, st), "pn2_conv1x1_fwd")
@@ -120,12 +118,9 @@ class _ConvBnMax(torch.autograd.Function):
         ldo = arg.shape[1]
         if grad.stride(-1) != 1 or grad.dtype != torch.float32:
             grad = grad.contiguous().float()
-        zb = _zeros_small(8 * _REPL * 2 * co + 16 * _r4(co) + 4 * (co * ci + co), dev)
-        red = zb[:8 * _REPL * 2 * co].view(torch.float64)
-        rest = zb[8 * _REPL * 2 * co:].view(torch.float32)
-        coef = rest[:4 * _r4(co)]
-        dW = rest[4 * _r4(co):4 * _r4(co) + co * ci].view(co, ci)
-        db = rest[4 * _r4(co) + co * ci:]
+        red, coef, dW, db = _carve(dev, [(torch.float64, _REPL * 2 * co), (torch.float32, 4 * _r4(co)), (torch.float32, co * ci),
+                                         (torch.float32, co)])
+        dW = dW.view(co, ci)
         dzp = torch.empty(G, ldo, device=dev, dtype=torch.float32)
         _check(lib.pn2_pool_bwd_reduce_noact(_p(grad), grad.stride(0), _p(arg), ldo, _p(y), y.shape[1], _p(aff), G, N, co, _p(dzp),
                                              _p(red), st), "pn2_pool_bwd_reduce_noact")
@@ -133,13 +128,14 @@ class _ConvBnMax(torch.autograd.Function):
         dbeta = torch.empty(co, device=dev, dtype=torch.float32)
         _check(lib.pn2_bn_bwd_coef(_p(red), P, co, _p(gamma), _p(aff), int(training), _p(coef), _p(dgamma), _p(dbeta), 0, st),
                "pn2_bn_bwd_coef")
-        _check(lib.pn2_conv1x1_wgrad(None, 0, _p(dzp), ldo, _p(arg), N, _p(y), y.shape[1], _p(coef), _p(x), x.shape[1], None, _p(dW), ci,
-                                     None if training else _p(db), P, co, ci, None, st), "pn2_conv1x1_wgrad")
+        dy = _UpGrad.pooled(dzp, ldo, arg, N, y, coef)
+        _check(lib.pn2_conv1x1_wgrad(*dy, _p(x), x.shape[1], None, _p(dW), ci, None if training else _p(db), P, co, ci, None, st),
+               "pn2_conv1x1_wgrad")
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty(P, x.shape[1], device=dev, dtype=torch.float32)
-            _check(lib.pn2_conv1x1_dgrad(None, 0, _p(dzp), ldo, _p(arg), N, _p(y), y.shape[1], _p(coef), _p(_contig_weight(w)), ci,
-                                         None, 0, None, _p(dx), dx.shape[1], None, P, co, ci, None, st), "pn2_conv1x1_dgrad")
+            _check(lib.pn2_conv1x1_dgrad(*dy, _p(_contig_weight(w)), ci, None, 0, None, _p(dx), dx.shape[1], None, P, co, ci, None, st),
+                   "pn2_conv1x1_dgrad")
         return dx, None, None, None, dW.view_as(w), db, dgamma, dbeta, None, None, None
 
 
@@ -169,10 +165,7 @@ class _GlobalConcatConv(torch.autograd.Function):
         cp = ct - cg
         eps, mom = cfg
         wc = _contig_weight(w)
-        zb = _zeros_small(8 * _REPL * 2 * co + 16 * _r4(co) + 4 * co, dev)
-        stats = zb[:8 * _REPL * 2 * co].view(torch.float64)
-        aff = zb[8 * _REPL * 2 * co:8 * _REPL * 2 * co + 16 * _r4(co)].view(torch.float32)
-        zero_bias = zb[8 * _REPL * 2 * co + 16 * _r4(co):].view(torch.float32)
+        stats, aff, zero_bias = _carve(dev, [(torch.float64, _REPL * 2 * co), (torch.float32, 4 * _r4(co)), (torch.float32, co)])
         gterm = _empty_rows(B, co, dev)                # W_g g_b: one row per cloud
         _check(lib.pn2_conv1x1_fwd(_p(g), cg, None, _p(wc), ct, _p(zero_bias), _p(gterm), gterm.shape[1], B, cg, co, None, None, st),
                "pn2_conv1x1_fwd")
@@ -200,12 +193,9 @@ class _GlobalConcatConv(torch.autograd.Function):
         grad = grad.contiguous().float()
         if grad.shape[1] != ldz:
             grad = F.pad(grad, (0, ldz - grad.shape[1]))
-        zb = _zeros_small(8 * _REPL * 2 * co + 16 * _r4(co) + 4 * (co * ct + co), dev)
-        red = zb[:8 * _REPL * 2 * co].view(torch.float64)
-        rest = zb[8 * _REPL * 2 * co:].view(torch.float32)
-        coef = rest[:4 * _r4(co)]
-        dW = rest[4 * _r4(co):4 * _r4(co) + co * ct].view(co, ct)
-        db = rest[4 * _r4(co) + co * ct:]
+        red, coef, dW, db = _carve(dev, [(torch.float64, _REPL * 2 * co), (torch.float32, 4 * _r4(co)), (torch.float32, co * ct),
+                                         (torch.float32, co)])
+        dW = dW.view(co, ct)
         dZ = _empty_rows(P, co, dev)
         _check(lib.pn2_relu_bwd_reduce(_p(grad), ldz, _p(z), _p(y), y.shape[1], _p(aff), P, co, _p(dZ), dZ.shape[1], _p(red), st),
                "pn2_relu_bwd_reduce")
@@ -215,25 +205,24 @@ class _GlobalConcatConv(torch.autograd.Function):
                "pn2_bn_bwd_coef")
         ldy = y.shape[1]
         # per-point part: dW_p += dY^T pointfeat, d pointfeat = dY W_p  (W_p: columns cg.. of the weight, pitch ct)
-        _check(lib.pn2_conv1x1_wgrad(_p(dZ), dZ.shape[1], None, 0, None, 0, _p(y), ldy, _p(coef), _p(pf), pf.shape[1], None,
-                                     dW.data_ptr() + 4 * cg, ct, None, P, co, cp, None, st), "pn2_conv1x1_wgrad")
+        dy = _UpGrad.dense(dZ, y, coef)
+        _check(lib.pn2_conv1x1_wgrad(*dy, _p(pf), pf.shape[1], None, dW.data_ptr() + 4 * cg, ct, None, P, co, cp, None, st),
+               "pn2_conv1x1_wgrad")
         dpf = None
         if ctx.needs_input_grad[0]:
             dpf = torch.empty(P, pf.shape[1], device=dev, dtype=torch.float32)
-            _check(lib.pn2_conv1x1_dgrad(_p(dZ), dZ.shape[1], None, 0, None, 0, _p(y), ldy, _p(coef), wc.data_ptr() + 4 * cg, ct, None, 0,
-                                         None, _p(dpf), dpf.shape[1], None, P, co, cp, None, st), "pn2_conv1x1_dgrad")
+            _check(lib.pn2_conv1x1_dgrad(*dy, wc.data_ptr() + 4 * cg, ct, None, 0, None, _p(dpf), dpf.shape[1], None, P, co, cp, None, st),
+                   "pn2_conv1x1_dgrad")
         # per-cloud part: s_b = sum_{p in b} dY_p, then [B]-row GEMMs with the identity coefficients (dY := s)
         s = _empty_rows(B, co, dev)
         ws = torch.empty(int(lib.pn2_group_colsum_workspace_bytes(P, N, co)), device=dev, dtype=torch.uint8)
         _check(lib.pn2_group_colsum(_p(dZ), dZ.shape[1], _p(y), ldy, _p(coef), P, N, co, _p(s), s.shape[1], _p(ws), st), "pn2_group_colsum")
-        ident = _ident_coef(co, dev)
-        _check(lib.pn2_conv1x1_wgrad(_p(s), s.shape[1], None, 0, None, 0, _p(s), s.shape[1], _p(ident), _p(g), cg, None, _p(dW), ct,
-                                     _p(db), B, co, cg, None, st), "pn2_conv1x1_wgrad")
+        ds = _UpGrad.linear(s, co)
+        _check(lib.pn2_conv1x1_wgrad(*ds, _p(g), cg, None, _p(dW), ct, _p(db), B, co, cg, None, st), "pn2_conv1x1_wgrad")
         dg = None
         if ctx.needs_input_grad[1]:
             dg = torch.empty(B, cg, device=dev, dtype=torch.float32)
-            _check(lib.pn2_conv1x1_dgrad(_p(s), s.shape[1], None, 0, None, 0, _p(s), s.shape[1], _p(ident), _p(wc), ct, None, 0, None,
-                                         _p(dg), cg, None, B, co, cg, None, st), "pn2_conv1x1_dgrad")
+            _check(lib.pn2_conv1x1_dgrad(*ds, _p(wc), ct, None, 0, None, _p(dg), cg, None, B, co, cg, None, st), "pn2_conv1x1_dgrad")
         return dpf, dg, None, None, None, dW.view_as(w), db, dgamma, dbeta, None, None, None
 
 
@@ -419,13 +408,9 @@ class _DenseSegHead(torch.autograd.Function):
         co, ct = ws1.shape[0], ws1.shape[1]
         cg = c5 + label.shape[1]
         srcs = (o1, o2, o3, o4)
-        zb = _zeros_small(8 * _REPL * 2 * (c5 + co) + 16 * (_r4(c5) + _r4(co)) + 4 * co, dev)
-        o = 0
-        stats5 = zb[o:o + 8 * _REPL * 2 * c5].view(torch.float64); o += 8 * _REPL * 2 * c5
-        stats1 = zb[o:o + 8 * _REPL * 2 * co].view(torch.float64); o += 8 * _REPL * 2 * co
-        aff5 = zb[o:o + 16 * _r4(c5)].view(torch.float32); o += 16 * _r4(c5)
-        aff1 = zb[o:o + 16 * _r4(co)].view(torch.float32); o += 16 * _r4(co)
-        zero_bias = zb[o:].view(torch.float32)
+        stats5, stats1, aff5, aff1, zero_bias = _carve(dev, [(torch.float64, _REPL * 2 * c5), (torch.float64, _REPL * 2 * co),
+                                                             (torch.float32, 4 * _r4(c5)), (torch.float32, 4 * _r4(co)),
+                                                             (torch.float32, co)])
         # conv5 + bn5 + max over the cloud (the pre-BN output is kept: bn5 is applied by its consumers)
         y5 = _empty_rows(P, c5, dev)
         _check(lib.pn2_conv1x1_fwd(_p(o4), o4.shape[1], None, _p(_contig_weight(w5)), ci5, _p(b5), _p(y5), y5.shape[1], P, ci5, c5,
@@ -470,18 +455,10 @@ class _DenseSegHead(torch.autograd.Function):
         g_seg = g_seg.contiguous().float()
         if g_seg.shape[1] != ld1:
             g_seg = F.pad(g_seg, (0, ld1 - g_seg.shape[1]))
-        zb = _zeros_small(8 * _REPL * 2 * (co + c5) + 16 * (_r4(co) + _r4(c5)) + 4 * (co * ct + co + c5 * ci5 + c5), dev)
-        o = 0
-        red1 = zb[o:o + 8 * _REPL * 2 * co].view(torch.float64); o += 8 * _REPL * 2 * co
-        red5 = zb[o:o + 8 * _REPL * 2 * c5].view(torch.float64); o += 8 * _REPL * 2 * c5
-        rest = zb[o:].view(torch.float32)
-        o = 0
-        coef1 = rest[o:o + 4 * _r4(co)]; o += 4 * _r4(co)
-        coef5 = rest[o:o + 4 * _r4(c5)]; o += 4 * _r4(c5)
-        dW1 = rest[o:o + co * ct].view(co, ct); o += co * ct
-        db1 = rest[o:o + co]; o += co
-        dW5 = rest[o:o + c5 * ci5].view(c5, ci5); o += c5 * ci5
-        db5 = rest[o:o + c5]
+        red1, red5, coef1, coef5, dW1, db1, dW5, db5 = _carve(dev, [
+            (torch.float64, _REPL * 2 * co), (torch.float64, _REPL * 2 * c5), (torch.float32, 4 * _r4(co)), (torch.float32, 4 * _r4(c5)),
+            (torch.float32, co * ct), (torch.float32, co), (torch.float32, c5 * ci5), (torch.float32, c5)])
+        dW1, dW5 = dW1.view(co, ct), dW5.view(c5, ci5)
         # bns1 + ReLU backward
         dZ1 = _empty_rows(P, co, dev)
         _check(lib.pn2_relu_bwd_reduce(_p(g_seg), ld1, _p(z), _p(y1), ld1, _p(aff1), P, co, _p(dZ1), dZ1.shape[1], _p(red1), st),
@@ -506,12 +483,10 @@ class _DenseSegHead(torch.autograd.Function):
         ws = torch.empty(int(lib.pn2_group_colsum_workspace_bytes(P, N, co)), device=dev, dtype=torch.uint8)
         _check(lib.pn2_group_colsum(_p(dZ1), dZ1.shape[1], _p(y1), ld1, _p(coef1), P, N, co, _p(s), s.shape[1], _p(ws), st),
                "pn2_group_colsum")
-        ident = _ident_coef(co, dev)
-        _check(lib.pn2_conv1x1_wgrad(_p(s), s.shape[1], None, 0, None, 0, _p(s), s.shape[1], _p(ident), _p(g), g.shape[1], None, _p(dW1), ct,
-                                     _p(db1), B, co, cg, None, st), "pn2_conv1x1_wgrad")
+        ds = _UpGrad.linear(s, co)
+        _check(lib.pn2_conv1x1_wgrad(*ds, _p(g), g.shape[1], None, _p(dW1), ct, _p(db1), B, co, cg, None, st), "pn2_conv1x1_wgrad")
         dg = torch.empty(B, g.shape[1], device=dev, dtype=torch.float32)
-        _check(lib.pn2_conv1x1_dgrad(_p(s), s.shape[1], None, 0, None, 0, _p(s), s.shape[1], _p(ident), _p(wc), ct, None, 0, None, _p(dg),
-                                     dg.shape[1], None, B, co, cg, None, st), "pn2_conv1x1_dgrad")
+        _check(lib.pn2_conv1x1_dgrad(*ds, _p(wc), ct, None, 0, None, _p(dg), dg.shape[1], None, B, co, cg, None, st), "pn2_conv1x1_dgrad")
         # bn5: the dense gradient from convs1 plus the pooled one (classification head + per-cloud part of convs1) at the arg-max rows
         dpool = dg[:, :c5]
         if g_max is not None:
@@ -525,11 +500,12 @@ class _DenseSegHead(torch.autograd.Function):
         dg5 = torch.empty(c5, device=dev, dtype=torch.float32)
         dbe5 = torch.empty(c5, device=dev, dtype=torch.float32)
         _check(lib.pn2_bn_bwd_coef(_p(red5), P, c5, _p(g5), _p(aff5), int(training), _p(coef5), _p(dg5), _p(dbe5), 0, st), "pn2_bn_bwd_coef")
-        _check(lib.pn2_conv1x1_wgrad(_p(d5), ld5, None, 0, None, 0, _p(y5), ld5, _p(coef5), _p(o4), o4.shape[1], None, _p(dW5), ci5,
-                                     None if training else _p(db5), P, c5, ci5, None, st), "pn2_conv1x1_wgrad")
+        dy5 = _UpGrad.dense(d5, y5, coef5)
+        _check(lib.pn2_conv1x1_wgrad(*dy5, _p(o4), o4.shape[1], None, _p(dW5), ci5, None if training else _p(db5), P, c5, ci5, None, st),
+               "pn2_conv1x1_wgrad")
         d4 = torch.empty(P, o4.shape[1], device=dev, dtype=torch.float32)
-        _check(lib.pn2_conv1x1_dgrad(_p(d5), ld5, None, 0, None, 0, _p(y5), ld5, _p(coef5), _p(_contig_weight(w5)), ci5, None, 0, None, _p(d4),
-                                     d4.shape[1], None, P, c5, ci5, None, st), "pn2_conv1x1_dgrad")
+        _check(lib.pn2_conv1x1_dgrad(*dy5, _p(_contig_weight(w5)), ci5, None, 0, None, _p(d4), d4.shape[1], None, P, c5, ci5, None, st),
+               "pn2_conv1x1_dgrad")
         d4 += dsrc[3]
         dlabel = dg[:, c5:cg] if ctx.needs_input_grad[4] else None
         return (dsrc[0], dsrc[1], dsrc[2], d4, dlabel, None, None, None, None, dW5.view_as(w5), db5, dg5, dbe5, None, None, None,

@@ -16,8 +16,10 @@ Layout notes
   * inside a module the grouped tensor is position-major ``[P, C]`` (P = B*S*K rows); the
     reference's ``[B, C, K, S]`` permute (pointnet_util.py:194) never happens.
 """
+import collections
 import contextlib
 import ctypes
+import types
 import weakref
 import os
 
@@ -686,6 +688,260 @@ def _direct_ok(params):
     return True
 
 
+def _carve(device, pieces):
+    """Zeroed views, one per (dtype, element count) of ``pieces`` (float64 first), out of ONE ``_zeros_small`` request: where the
+    arena's chunks roll over, and with it which memsets a captured graph holds, follows from the sequence of request sizes."""
+    sizes = [n * (torch.finfo(dt).bits // 8) for dt, n in pieces]
+    return [v.view(dt) for v, (dt, _) in zip(_zeros_small(sum(sizes), device).split(sizes), pieces)]
+
+
+class _UpGrad(tuple):
+    """The upstream-gradient operand of the dgrad / wgrad / bwd entry points (include/pn2.h), passed as ``*dy``: their nine leading
+    arguments ``dZ, ldz, dZp, ldo, arg, Kpool, Y, ldy, coef`` -- dZ as dense rows, or pooled as (dZp, arg) with Kpool rows per group;
+    Y and the coefficient block turn it into dY.  The only place that knows the slot order."""
+
+    @classmethod
+    def dense(cls, dZ, Y, coef):
+        return cls((_p(dZ), dZ.shape[1], None, 0, None, 0, _p(Y), Y.shape[1], _p(coef)))
+
+    @classmethod
+    def pooled(cls, dZp, ldo, arg, K, Y, coef):
+        return cls((None, 0, _p(dZp), ldo, _p(arg), K, _p(Y), Y.shape[1], _p(coef)))
+
+    @classmethod
+    def linear(cls, g, co):
+        """No BatchNorm behind the layer: dY := 1*g + 0*(g - 0) + 0, the identity block over the ``co`` real columns of ``g``."""
+        ident = _ident_coef(co, g.device)
+        dy = cls.dense(g, g, ident)
+        dy.ident = ident                 # (a block made under capture is private to the caller: it lives as long as the operand)
+        return dy
+
+
+# What grouped_mlp hands _SharedMLP for a first layer on the un-grouped source points: coordinates [B,N,3], centres [B,S,3], index
+# [B,S,K], column order, the target-sorted index (or None), and ``gather``: pn2_group_conv_fwd; otherwise the factorised first layer.
+_GroupGeom = collections.namedtuple("_GroupGeom", "xyz new_xyz idx xyz_first inv gather")
+
+
+def _fwd_gather_conv(rows, geom, w, b, y, st_l, ci, co, P):
+    """Narrow first layer: gather + conv in one launch; the grouped rows are written once, for the backward (returned)."""
+    B, N, D = rows.shape
+    gathered = _empty_rows(P, ci, rows.device)
+    _check(_lib.load().pn2_group_conv_fwd(_p(geom.xyz), _p(rows), _p(geom.new_xyz), _p(geom.idx), B, N, geom.idx.shape[1],
+                                          geom.idx.shape[2], D, int(geom.xyz_first), _p(_contig_weight(w)), ci, _p(b), _p(gathered),
+                                          gathered.shape[1], _p(y), y.shape[1], co, _p(st_l), _lib.stream()), "pn2_group_conv_fwd")
+    return gathered
+
+
+def _fwd_factorised(rows, geom, w, b, y, st_l, ci, co, w_pads):
+    """Factorised first layer: Zf = W_f f + bias once per source point, then y = Zf[idx] + W_x (xyz[idx] - centre)."""
+    lib, st = _lib.load(), _lib.stream()
+    B, N, D = rows.shape
+    S, K = geom.idx.shape[1], geom.idx.shape[2]
+    # the kernels read the xyz / feature columns straight out of the [co, 3+D] weight (pitch ci): no copies
+    w_ptr = _contig_weight(w).data_ptr()
+    wx_ptr, wf_ptr = (w_ptr, w_ptr + 12) if geom.xyz_first else (w_ptr + 4 * D, w_ptr)
+    wf_ld = ci
+    wf_pad = _padded_feature_columns(w, D, ci, geom.xyz_first)
+    if wf_pad is not None:                  # (D % 4 == 1, features first: see _padded_feature_columns)
+        w_pads["wf"] = wf_pad
+        wf_ptr, wf_ld = wf_pad.data_ptr(), wf_pad.shape[1]
+    ldd = _r4(D)
+    feat = rows.reshape(B * N, D)
+    if ldd != D:
+        feat = torch.nn.functional.pad(feat, (0, ldd - D))
+    zf = _empty_rows(B * N, co, rows.device)
+    _check(lib.pn2_conv1x1_fwd(_p(feat), ldd, None, wf_ptr, wf_ld, _p(b), _p(zf), zf.shape[1], B * N, D, co, None, None, st),
+           "pn2_conv1x1_fwd")
+    _check(lib.pn2_group_affine_fwd(_p(zf), zf.shape[1], _p(geom.xyz), _p(geom.new_xyz), _p(geom.idx), wx_ptr, ci, B, N, S, K, co,
+                                    _p(y), y.shape[1], _p(st_l), st), "pn2_group_affine_fwd")
+
+
+def _fwd_pooled_last(x, ldx, x_aff, w, b, gamma, y, st_l, ci, co, P, pool, lazy):
+    """Last layer of a pooled MLP: the weight-resident kernel also records the per-group extrema of y, so the pooled output needs no
+    second pass over Y -> (y, records).  ``y`` None: the output-free form.  Unsupported shapes: the plain launch -> (y, None)."""
+    lib, st = _lib.load(), _lib.stream()
+    pool_ws = torch.empty(2 * (P // pool) * co, device=x.device, dtype=torch.float32)
+
+    def launch(y):
+        return lib.pn2_conv1x1_fwd_pool(_p(x), ldx, _p(x_aff), _p(_contig_weight(w)), ci, _p(b), _p(y), co, P, ci, co, _p(st_l), pool,
+                                        _p(gamma), _p(pool_ws), lazy, st)
+    rc = launch(y)
+    if rc == _lib.PN2_EUNSUPPORTED and y is None:      # (no output-free form for this shape after all)
+        y = _empty_rows(P, co, x.device)
+        rc = launch(y)
+    if rc != _lib.PN2_EUNSUPPORTED:
+        _check(rc, "pn2_conv1x1_fwd_pool")
+        return y, pool_ws
+    _check(lib.pn2_conv1x1_fwd(_p(x), ldx, _p(x_aff), _p(_contig_weight(w)), ci, _p(b), _p(y), y.shape[1], P, ci, co, _p(st_l), lazy, st),
+           "pn2_conv1x1_fwd")
+    return y, None
+
+
+def _fwd_plain(x, ldx, x_aff, w, b, y, st_l, ci, co, P, lazy, w_pads, l):
+    w_rd, w_ld = _aligned_weight(w, ci, co, P)
+    if w_ld != ci:
+        w_pads[l] = w_rd                            # the data-gradient GEMM of the backward reads it too
+    _check(_lib.load().pn2_conv1x1_fwd(_p(x), ldx, _p(x_aff), _p(w_rd), w_ld, _p(b), _p(y), y.shape[1], P, ci, co, _p(st_l), lazy,
+                                       _lib.stream()), "pn2_conv1x1_fwd")
+
+
+def _bwd_route(s, a, fuse_first):
+    """The backward route of layer ``a`` (``s``: what the whole backward shares; both built in _SharedMLP.backward).  Every route
+    returns (data gradient handed to the layer below or None, the weight gradient it filled, hand-over to the next layer)."""
+    if a.l == 0 and s.ctx.geom is not None and s.ctx.gather is None:
+        return _first_layer_bwd
+    if not s.training and s.direct:
+        raise NotImplementedError("direct gradient accumulation with eval-mode BatchNorm: use autograd mode")
+    if (a.l == 1 and fuse_first and a.dZ is not None) or (a.l == 0 and a.handoff is not None):
+        return _bwd_fused_first
+    if a.y is None:
+        return _bwd_from_input
+    if (a.need_dx and s.training and
+            s.lib.pn2_bwd_res_supported(s.P, a.co, a.ci, s.K if a.pooled else 0, int(a.x_aff is not None))):
+        return _bwd_resident
+    if a.need_dx and BWD_PAIR and s.training and a.pair_key not in _PAIR_RUNS_SPLIT:
+        return _bwd_pair
+    return _bwd_streamed
+
+
+def _dy(s, a):
+    """The two forms of dZ the kernels take: dense rows, or the pooled pair (dZp, arg) with K rows per group."""
+    return _UpGrad.pooled(s.dzp, s.ldo, s.arg, s.K, a.y, a.coef) if a.pooled else _UpGrad.dense(a.dZ, a.y, a.coef)
+
+
+def _alloc_dx(s, a):
+    if a.l > 0:
+        return _empty_rows(s.P, a.ci, s.dev)
+    return torch.empty(s.P, a.ldx, device=s.dev, dtype=torch.float32)        # (d rows) pad lanes written (0) by the GEMM
+
+
+def _dgrad_operands(s, a, dx):
+    """The eight slots of a data-gradient GEMM behind dY: the [co, ci] weight as stored (read down the columns) or its 16-byte aligned,
+    zero-padded copy made by the forward; the previous layer's output and block (its ReLU mask) below the first layer; dX; reductions."""
+    w_l, w_ld = _p(_contig_weight(a.w)), a.ci
+    if a.l in s.ctx.w_pads:
+        w_l, w_ld = _p(s.ctx.w_pads[a.l]), s.ctx.w_pads[a.l].shape[1]
+    prev = (_p(a.x), a.ldx, _p(a.x_aff)) if a.l > 0 else (None, 0, None)
+    return (w_l, w_ld) + prev + (_p(dx), dx.shape[1], _p(a.prev_red))
+
+
+def _bwd_fused_first(s, a):
+    """sa1-style stacks (a first layer on the 48-byte grouped rows, nobody needs d rows): the second layer's fused backward forms
+    the first layer's sum dZ^T x from its dX tiles -- dZ1 is never written, it exists only as those sums in the scratch handed over
+    -- and the first layer's weight gradient finishes from them and the input's moments (pn2_conv1x1_wgrad_cf with dZ == NULL).
+    A shape the library refuses after all takes the layer's ordinary route."""
+    if a.l == 0:
+        _check(s.lib.pn2_conv1x1_wgrad_cf(None, 0, _p(a.coef), _p(a.x), a.ldx, _p(_contig_weight(a.w)), a.ci, _p(s.flat[7 * a.l + 1]),
+                                          _p(a.handoff), _p(a.dW), a.ci, s.P, a.co, a.ci, a.coef_lazy, s.st), "pn2_conv1x1_wgrad_cf")
+        return None, a.dW, None
+    scratch = _zeros_small(int(s.lib.pn2_conv1x1_wgrad_cf_scratch_bytes()), s.dev)
+    rc = s.lib.pn2_conv1x1_bwd_first(_p(a.dZ), a.dZ.shape[1], _p(a.y), a.y.shape[1], _p(a.coef), _p(_contig_weight(a.w)), a.ci, _p(a.x),
+                                     a.ldx, _p(a.x_aff), _p(a.prev_red), _p(a.dW), a.ci, _p(s.rows), s.rows.shape[1], s.chans[0],
+                                     _p(scratch), s.P, a.co, a.ci, a.coef_lazy, s.st)
+    if rc == _lib.PN2_EUNSUPPORTED:
+        return _bwd_route(s, a, False)(s, a)
+    _check(rc, "pn2_conv1x1_bwd_first")
+    return None, a.dW, scratch
+
+
+def _bwd_from_input(s, a):
+    """Pooled last layer that ran without its output: dX and dW from (dZp, arg) and the layer's input alone."""
+    scratch = torch.empty(int(s.lib.pn2_conv1x1_bwd_cf_scratch_bytes(a.co, a.ci)), device=s.dev, dtype=torch.uint8)
+    dx = _empty_rows(s.P, a.ci, s.dev)
+    _check(s.lib.pn2_conv1x1_bwd_cf(_p(s.dzp), s.ldo, _p(s.arg), s.K, _p(a.coef), _p(_contig_weight(a.w)), a.ci, _p(s.flat[7 * a.l + 1]),
+                                    _p(a.x), a.ldx, _p(a.x_aff), _p(dx), dx.shape[1], _p(a.prev_red), _p(a.dW), a.ci, s.P, a.co, a.ci,
+                                    a.coef_lazy, _p(scratch), s.st), "pn2_conv1x1_bwd_cf")
+    return dx, a.dW, None
+
+
+def _bwd_resident(s, a):
+    """Narrow, long layer: dgrad + wgrad in ONE pass over dZ / Y / Y_prev, weights resident in LDS (mlp_res.hip)."""
+    dx = _alloc_dx(s, a)
+    _check(s.lib.pn2_conv1x1_bwd(*_dy(s, a), _p(_contig_weight(a.w)), a.ci, _p(a.x), a.ldx, _p(a.x_aff), _p(dx), dx.shape[1],
+                                 _p(a.prev_red), _p(a.dW), a.ci, s.P, a.co, a.ci, a.coef_lazy, s.st), "pn2_conv1x1_bwd")
+    return dx, a.dW, None
+
+
+def _bwd_pair(s, a):
+    """Data gradient and weight gradient as ONE call: on the few-row / mid-size layers both kernel bodies share one launch
+    (pn2_conv1x1_bwd_pair); elsewhere the library issues the two launches itself and answers PN2_OK_SPLIT (not an error)."""
+    dx = _alloc_dx(s, a)
+    rc = s.lib.pn2_conv1x1_bwd_pair(*_dy(s, a), *_dgrad_operands(s, a, dx), _p(a.x), a.ldx, _p(a.x_aff), _p(a.dW), a.ci,
+                                    s.P, a.co, a.ci, a.coef_lazy, s.st)
+    if rc != _lib.PN2_OK_SPLIT:
+        _check(rc, "pn2_conv1x1_bwd_pair")
+    else:
+        # The library ran this shape as its own dgrad + wgrad launches.  From the next step on the shape takes _bwd_streamed, whose
+        # two calls a per-launch accounting (bench.py) sees each by itself.  That route picks its weight-gradient kernel itself:
+        # where pn2_conv1x1_wgrad_workspace_bytes is non-zero it runs pn2_conv1x1_wgrad_ws, which the pair call does not.
+        _PAIR_RUNS_SPLIT.add(a.pair_key)
+    return dx, a.dW, None
+
+
+def _bwd_streamed(s, a):
+    """pn2_conv1x1_dgrad (where a data gradient is wanted), then the weight gradient by one of three kernels."""
+    lib, st, dy, coef_lazy, dx = s.lib, s.st, _dy(s, a), a.coef_lazy, None
+    if a.need_dx:
+        dx = _alloc_dx(s, a)
+        _check(lib.pn2_conv1x1_dgrad(*dy, *_dgrad_operands(s, a, dx), s.P, a.co, a.ci, coef_lazy, st), "pn2_conv1x1_dgrad")
+        coef_lazy = None                            # filled: the weight gradient below reads it
+    if WGRAD_CF and a.l == 0 and s.training and not a.need_dx and not a.pooled and a.ci <= 15 and a.co % 16 == 0 and a.co <= 128:
+        # first layer without a data gradient: the BatchNorm-backward terms of dY in closed form from the input rows' first and
+        # second moments -- the pass reads dZ and the rows, not Y (pn2_conv1x1_wgrad_cf, include/pn2.h)
+        scratch = _zeros_small(int(lib.pn2_conv1x1_wgrad_cf_scratch_bytes()), s.dev)
+        _check(lib.pn2_conv1x1_wgrad_cf(_p(a.dZ), a.dZ.shape[1], _p(a.coef), _p(a.x), a.ldx, _p(_contig_weight(a.w)), a.ci,
+                                        _p(s.flat[7 * a.l + 1]), _p(scratch), _p(a.dW), a.ci, s.P, a.co, a.ci, coef_lazy, st),
+               "pn2_conv1x1_wgrad_cf")
+        return dx, a.dW, None
+    ws_bytes = lib.pn2_conv1x1_wgrad_workspace_bytes(s.P, a.co, a.ci, int(a.pooled)) if s.training else 0
+    if ws_bytes:                                    # two-phase dW flush of the full-tile kernel: caller scratch
+        ws = torch.empty(ws_bytes, device=s.dev, dtype=torch.uint8)
+        _check(lib.pn2_conv1x1_wgrad_ws(*dy, _p(a.x), a.ldx, _p(a.x_aff), _p(a.dW), a.ci, None, s.P, a.co, a.ci, coef_lazy, _p(ws), st),
+               "pn2_conv1x1_wgrad_ws")
+    else:
+        _check(lib.pn2_conv1x1_wgrad(*dy, _p(a.x), a.ldx, _p(a.x_aff), _p(a.dW), a.ci, None if s.training else _p(a.dbias), s.P, a.co,
+                                     a.ci, coef_lazy, st), "pn2_conv1x1_wgrad")
+    return dx, a.dW, None
+
+
+def _first_layer_bwd(s, a):
+    """Backward of the factorised first layer: scatter dY to the source points, then two small GEMMs.  The weight gradient is a
+    [co, 3+D] tensor of its own, or the parameter's ``.grad`` under direct accumulation."""
+    lib, st, geom, feats, dZ, y, co, dev = s.lib, s.st, s.ctx.geom, s.rows, a.dZ, a.y, a.co, s.dev
+    B, N, D = feats.shape
+    S, K = geom.idx.shape[1], geom.idx.shape[2]
+    ldc, ldd = _r4(co), _r4(D)
+    dW = s.flat[0].grad if s.direct else _zeros_f32((co, 3 + D), dev)
+    ldw = 3 + D
+    x_col, f_col = (0, 3) if geom.xyz_first else (D, 0)
+    G = _zeros_f32((B * N, ldc), dev)
+    if geom.inv is not None and co <= 256:           # segmented reduction over the source-sorted ball-query index
+        scratch = _zeros_small(4 * _lib.DWX_REPLICAS * 3 * ldc, dev) if DWX_REPLICAS_SCRATCH else None
+        _check(lib.pn2_group_affine_bwd_seg(_p(dZ), dZ.shape[1], _p(y), y.shape[1], _p(a.coef), _p(geom.xyz), _p(geom.new_xyz),
+                                            _p(geom.inv[0]), _p(geom.inv[1]), B, N, S, K, co, _p(G), ldc,
+                                            dW.data_ptr() + 4 * x_col, ldw, _p(scratch), a.coef_lazy, st), "pn2_group_affine_bwd_seg")
+    else:
+        _check(lib.pn2_group_affine_bwd(_p(dZ), dZ.shape[1], _p(y), y.shape[1], _p(a.coef), _p(geom.xyz), _p(geom.new_xyz),
+                                        _p(geom.idx), B, N, S, K, co, _p(G), ldc, dW.data_ptr() + 4 * x_col, ldw, st),
+               "pn2_group_affine_bwd")
+    feat = feats.reshape(B * N, D)
+    if ldd != D:
+        feat = torch.nn.functional.pad(feat, (0, ldd - D)).contiguous()
+    dy = _UpGrad.linear(G, co)
+    _check(lib.pn2_conv1x1_wgrad(*dy, _p(feat), ldd, None, dW.data_ptr() + 4 * f_col, ldw, None, B * N, co, D, None, st),
+           "pn2_conv1x1_wgrad")
+    d_feats = None
+    if s.ctx.needs_input_grad[0]:
+        wf_ptr = _contig_weight(a.w).data_ptr() + (12 if geom.xyz_first else 0)      # feature columns of the [co, 3+D] weight
+        wf_ld = 3 + D
+        if "wf" in s.ctx.w_pads:                 # their zero-padded copy made by the forward (D % 4 == 1, features first)
+            wf_ptr, wf_ld = s.ctx.w_pads["wf"].data_ptr(), s.ctx.w_pads["wf"].shape[1]
+        dF = _empty_rows(B * N, D, dev)
+        _check(lib.pn2_conv1x1_dgrad(*dy, wf_ptr, wf_ld, None, 0, None, _p(dF), ldd, None, B * N, co, D, None, st), "pn2_conv1x1_dgrad")
+        d_feats = (dF[:, :D] if ldd != D else dF).reshape(B, N, D)
+    return d_feats, dW, None
+
+
 class _SharedMLP(torch.autograd.Function):
     """L x (1x1 conv + BatchNorm + ReLU) on position-major rows, then max over ``pool`` consecutive rows.
 
@@ -698,8 +954,8 @@ class _SharedMLP(torch.autograd.Function):
     matrix (the concatenated output of the MSG scales, pointnet_util.py:260) instead of a tensor of its own that a
     ``torch.cat`` would copy; the returned tensor is that slice.
 
-    ``geom`` = None, or (xyz [B,N,3], new_xyz [B,S,3], idx [B,S,K], xyz_first) for the FACTORISED first layer:
-    ``rows`` is then the un-grouped feature tensor [B,N,D] and layer 1 is evaluated as
+    ``geom`` = None, or a ``_GroupGeom``: ``rows`` is then the un-grouped feature tensor [B,N,D].  With ``geom.gather`` the first
+    layer gathers and convolves in one launch; otherwise it is the FACTORISED first layer, evaluated as
     ``Zf[b, idx] + W_x (xyz[idx] - centre)`` with ``Zf = W_f f + bias`` computed once per source point
     (csrc/grouped.hip) -- the grouped [P, 3+D] tensor never exists and the K-fold redundant GEMM rows vanish.
     """
@@ -709,92 +965,40 @@ class _SharedMLP(torch.autograd.Function):
         lib, st = _lib.load(), _lib.stream()
         dev = rows.device
         L = len(flat) // 7
-        if geom is None:
-            P = rows.shape[0]
-        else:
-            g_xyz, g_new, g_idx, g_first, g_inv = geom[:5]
-            gB, gN, gD = rows.shape
-            gS, gK = g_idx.shape[1], g_idx.shape[2]
-            P = gB * gS * gK
+        P = rows.shape[0] if geom is None else rows.shape[0] * geom.idx.shape[1] * geom.idx.shape[2]
         chans = [c_in] + [flat[7 * l].shape[0] for l in range(L)]
-        n_stats = _REPL * 2 * sum(chans[1:]) if training else 0
-        n_aff = 4 * sum(_r4(c) for c in chans[1:])
-        zero_bytes = _zeros_small(8 * n_stats + 4 * n_aff, dev)
-        stats = zero_bytes[:8 * n_stats].view(torch.float64) if training else None
-        Ys, affs = [], []
-        aff_all = zero_bytes[8 * n_stats:8 * n_stats + 4 * n_aff].view(torch.float32)
-        aff_off = 0
-        x, ldx, x_aff, off = rows, rows.shape[-1], None, 0
-        pool_ws = None
-        gather = geom is not None and len(geom) > 5 and bool(geom[5])      # (xyz, new_xyz, idx, xyz_first, None, True)
-        gathered = None
+        # zeroed scratch: every layer's statistics (training), then every layer's affine block
+        pieces = _carve(dev, ([(torch.float64, _REPL * 2 * c) for c in chans[1:]] if training else []) +
+                        [(torch.float32, 4 * _r4(c)) for c in chans[1:]])
+        stats, affs = pieces[:-L] or [None] * L, pieces[-L:]
+        Ys = []
+        x, ldx, x_aff = rows, rows.shape[-1], None
+        pool_ws = gathered = None
         w_pads = {}
         lazy_on = training and LAZY_BN
         lazy_prev = None                   # pn2_bn_lazy of the previous layer's block: realised by the next launch that reads it
         keep = []                          # (ctypes structures must outlive the calls that take their address)
-
-        def in_lazy():
-            return None if lazy_prev is None else ctypes.byref(lazy_prev)
         for l in range(L):
             w, b, gamma, beta, rmean, rvar, nbt = flat[7 * l:7 * l + 7]
             co, ci = chans[l + 1], chans[l]
+            st_l, aff = stats[l], affs[l]
+            lazy = None if lazy_prev is None else ctypes.byref(lazy_prev)
             pooled_last = (l == L - 1 and pool and training and x_aff is not None and POOL_IN_EPILOGUE and P % 32 == 0 and
                            (pool == 16 or pool % 32 == 0) and co % 32 == 0)
             # the pooled last layer of the long sa1 stacks: its pre-BN output is never written -- the backward runs on the layer's
             # input (pn2_conv1x1_bwd_cf) -- where the library has that form (csrc/mlp_res.hip: split_bwd_cf_kernel)
             no_y = bool(pooled_last and lazy_on and lib.pn2_conv1x1_bwd_cf_supported(P, co, ci, pool))
             y = None if no_y else _empty_rows(P, co, dev)
-            st_l = stats[off:off + _REPL * 2 * co] if training else None
-            aff = aff_all[aff_off:aff_off + 4 * _r4(co)]
-            aff_off += 4 * _r4(co)
-            eps, mom = bn_cfg[l]
-            if l == 0 and gather:
-                # narrow first layer: gather + conv in one launch; the grouped rows are written once, for the backward
-                gathered = _empty_rows(P, ci, dev)
-                _check(lib.pn2_group_conv_fwd(_p(g_xyz), _p(rows), _p(g_new), _p(g_idx), gB, gN, gS, gK, gD, int(g_first),
-                                              _p(_contig_weight(w)), ci, _p(b), _p(gathered), gathered.shape[1], _p(y), y.shape[1], co,
-                                              _p(st_l), st), "pn2_group_conv_fwd")
+            if l == 0 and geom is not None and geom.gather:
+                gathered = _fwd_gather_conv(rows, geom, w, b, y, st_l, ci, co, P)
             elif l == 0 and geom is not None:
-                # the kernels read the xyz / feature columns straight out of the [co, 3+D] weight (pitch ci): no copies
-                w_ptr = _contig_weight(w).data_ptr()
-                wx_ptr, wf_ptr = (w_ptr, w_ptr + 12) if g_first else (w_ptr + 4 * gD, w_ptr)
-                wf_ld = ci
-                wf_pad = _padded_feature_columns(w, gD, ci, g_first)
-                if wf_pad is not None:                  # (D % 4 == 1, features first: see _padded_feature_columns)
-                    w_pads["wf"] = wf_pad
-                    wf_ptr, wf_ld = wf_pad.data_ptr(), wf_pad.shape[1]
-                ldd = _r4(gD)
-                feat = rows.reshape(gB * gN, gD)
-                if ldd != gD:
-                    feat = torch.nn.functional.pad(feat, (0, ldd - gD))
-                zf = _empty_rows(gB * gN, co, dev)
-                _check(lib.pn2_conv1x1_fwd(_p(feat), ldd, None, wf_ptr, wf_ld, _p(b), _p(zf), zf.shape[1], gB * gN, gD, co,
-                                           None, None, st), "pn2_conv1x1_fwd")
-                _check(lib.pn2_group_affine_fwd(_p(zf), zf.shape[1], _p(g_xyz), _p(g_new), _p(g_idx), wx_ptr, ci, gB, gN, gS,
-                                                gK, co, _p(y), y.shape[1], _p(st_l), st), "pn2_group_affine_fwd")
+                _fwd_factorised(rows, geom, w, b, y, st_l, ci, co, w_pads)
             elif pooled_last:
-                # last layer of a pooled MLP: the weight-resident kernel also records the per-group extrema of y, so the
-                # pooled output needs no second pass over Y (unsupported shapes: the plain launch + pn2_bn_relu_max below)
-                pool_ws = torch.empty(2 * (P // pool) * co, device=dev, dtype=torch.float32)
-                rc = lib.pn2_conv1x1_fwd_pool(_p(x), ldx, _p(x_aff), _p(_contig_weight(w)), ci, _p(b), _p(y), co, P, ci, co,
-                                              _p(st_l), pool, _p(gamma), _p(pool_ws), in_lazy(), st)
-                if rc == _lib.PN2_EUNSUPPORTED and y is None:      # (no output-free form for this shape after all)
-                    y = _empty_rows(P, co, dev)
-                    rc = lib.pn2_conv1x1_fwd_pool(_p(x), ldx, _p(x_aff), _p(_contig_weight(w)), ci, _p(b), _p(y), co, P, ci, co,
-                                                  _p(st_l), pool, _p(gamma), _p(pool_ws), in_lazy(), st)
-                if rc == _lib.PN2_EUNSUPPORTED:
-                    pool_ws = None
-                    _check(lib.pn2_conv1x1_fwd(_p(x), ldx, _p(x_aff), _p(_contig_weight(w)), ci, _p(b), _p(y), y.shape[1], P, ci,
-                                               co, _p(st_l), in_lazy(), st), "pn2_conv1x1_fwd")
-                else:
-                    _check(rc, "pn2_conv1x1_fwd_pool")
+                y, pool_ws = _fwd_pooled_last(x, ldx, x_aff, w, b, gamma, y, st_l, ci, co, P, pool, lazy)
             else:
-                w_rd, w_ld = _aligned_weight(w, ci, co, P)
-                if w_ld != ci:
-                    w_pads[l] = w_rd                            # the data-gradient GEMM of the backward reads it too
-                _check(lib.pn2_conv1x1_fwd(_p(x), ldx, _p(x_aff), _p(w_rd), w_ld, _p(b), _p(y), y.shape[1], P, ci,
-                                           co, _p(st_l), in_lazy(), st), "pn2_conv1x1_fwd")
+                _fwd_plain(x, ldx, x_aff, w, b, y, st_l, ci, co, P, lazy, w_pads, l)
             lazy_prev = None                                    # (whatever block the launch above read has been filled)
+            eps, mom = bn_cfg[l]
             if lazy_on:
                 # this layer's statistics become its affine block inside the next launch that reads the block
                 lazy_prev = _lib.BnLazy(_p(st_l), _p(gamma), _p(beta), eps, mom, _p(rmean), _p(rvar), _p(nbt), _p(aff), P, co)
@@ -803,9 +1007,8 @@ class _SharedMLP(torch.autograd.Function):
                 _check(lib.pn2_bn_finalize(_p(st_l), P, co, _p(gamma), _p(beta), eps, mom, int(training),
                                            _p(rmean), _p(rvar), _p(nbt), _p(aff), st), "pn2_bn_finalize")
             Ys.append(y)
-            affs.append(aff)
             x, ldx, x_aff = y, (y.shape[1] if y is not None else 0), aff
-            off += _REPL * 2 * co
+        lazy = None if lazy_prev is None else ctypes.byref(lazy_prev)
         cl = chans[-1]
         K = pool if pool else 1
         G = P // K
@@ -818,16 +1021,16 @@ class _SharedMLP(torch.autograd.Function):
         # the argmax shares the output's pitch inside the kernels (arg + g * ldo + c): its own buffer, same pitch
         arg = torch.empty(G, ldo, device=dev, dtype=torch.int32) if pool else None
         if pool_ws is not None:
-            _check(lib.pn2_bn_pool_select(_p(pool_ws), _p(affs[-1]), G, cl, _p(out), ldo, _p(arg), in_lazy(), st), "pn2_bn_pool_select")
+            _check(lib.pn2_bn_pool_select(_p(pool_ws), _p(affs[-1]), G, cl, _p(out), ldo, _p(arg), lazy, st), "pn2_bn_pool_select")
         else:
-            _check(lib.pn2_bn_relu_max(_p(Ys[-1]), Ys[-1].shape[1], _p(affs[-1]), G, K, cl, _p(out), ldo, _p(arg), in_lazy(), st),
+            _check(lib.pn2_bn_relu_max(_p(Ys[-1]), Ys[-1].shape[1], _p(affs[-1]), G, K, cl, _p(out), ldo, _p(arg), lazy, st),
                    "pn2_bn_relu_max")
         if training:
             bump_param_generation()             # running statistics were written through raw pointers
         ctx.meta = (chans, pool, bool(training), P)
-        ctx.geom = None if geom is None else (g_xyz, g_new, g_idx, bool(g_first), g_inv)   # index/coordinate tensors: no cycle
-        ctx.gather = (gB, gN, gD) if gather else None
-        if gather:
+        ctx.geom = geom                         # index/coordinate tensors: no cycle
+        ctx.gather = tuple(rows.shape) if gathered is not None else None      # (B, N, D) of the gathered source points
+        if gathered is not None:
             rows = gathered                     # what the backward reads as the first layer's input
         ctx.params = flat                       # leaf parameters / buffers (no grad_fn): no cycle either
         ctx.w_pads = w_pads                     # plain scratch tensors (no grad_fn)
@@ -845,12 +1048,12 @@ class _SharedMLP(torch.autograd.Function):
         chans, pool, training, P = ctx.meta
         saved = ctx.saved_tensors
         L = len(chans) - 1
-        rows, out, arg = saved[0], saved[1], saved[2]
-        Ys, affs = saved[3:3 + L], saved[3 + L:3 + 2 * L]
-        Ws, gammas = saved[3 + 2 * L:3 + 3 * L], saved[3 + 3 * L:3 + 4 * L]
-        dev = rows.device
+        rows, out, arg = saved[:3]
+        Ys, affs, Ws, gammas = (saved[3 + i * L:3 + (i + 1) * L] for i in range(4))
+        dev, flat = rows.device, ctx.params
         cl = chans[-1]
         ldo = out.stride(0)                    # (a column slice of a wider matrix when the forward was given a ``dest``)
+        # ---- prologue: the incoming gradient, the scratch, and the head (pooling / ReLU backward of the last layer)
         # The pooled branch reads the incoming gradient once, scalar-wise, at any pitch: a column slice of a wider matrix (a
         # branch of a concatenated MSG output) or an un-padded [G, cl] matrix is passed in place -- no copy kernel at the head
         # of the branch's backward chain.
@@ -863,238 +1066,77 @@ class _SharedMLP(torch.autograd.Function):
                 g[:, :cl] = grad_out
                 grad_out = g
             grad_out = grad_out.contiguous()
-        n_red = _REPL * 2 * sum(chans[1:])
-        direct = _direct_ok([ctx.params[7 * l + j] for l in range(L) for j in (0, 2, 3)])
-        sizes = [4 * _r4(chans[l + 1]) + (0 if direct else chans[l + 1] * chans[l] + chans[l + 1]) for l in range(L)]
-        zero_bytes = _zeros_small(8 * n_red + 4 * sum(sizes), dev)
-        red = zero_bytes[:8 * n_red].view(torch.float64)
-        offs = np.cumsum([0] + [_REPL * 2 * c for c in chans[1:]])
+        direct = _direct_ok([flat[7 * l + j] for l in range(L) for j in (0, 2, 3)])
+        # zeroed scratch: every layer's BatchNorm-backward reductions, then per layer the coefficient block (+ dW and dbias in
+        # autograd mode; under direct accumulation the kernels add into the parameters' .grad)
+        per_layer = 1 if direct else 3
+        spec = [(torch.float64, _REPL * 2 * c) for c in chans[1:]]
+        for ci, co in zip(chans[:-1], chans[1:]):
+            spec += [(torch.float32, 4 * _r4(co))] + ([] if direct else [(torch.float32, co * ci), (torch.float32, co)])
+        pieces = _carve(dev, spec)
+        reds, pieces = pieces[:L], pieces[L:]
         K = pool if pool else 1
         G = P // K
-        flat = ctx.params
-        # zeroed scratch: BN-backward coefficient blocks (+ the gradient tensors in autograd mode)
-        zbuf = zero_bytes[8 * n_red:8 * n_red + 4 * sum(sizes)].view(torch.float32)
-        zoff = np.cumsum([0] + sizes)
-        outs = []                                    # per layer: coef, dgamma, dbeta, dW, dbias
-        for l in range(L):
-            co, ci = chans[l + 1], chans[l]
-            z0 = int(zoff[l])
-            coef = zbuf[z0:z0 + 4 * _r4(co)]
-            if direct:
-                outs.append((coef, flat[7 * l + 2].grad, flat[7 * l + 3].grad, flat[7 * l].grad, None))
-            else:
-                outs.append((coef, torch.empty(co, device=dev, dtype=torch.float32),
-                             torch.empty(co, device=dev, dtype=torch.float32),
-                             zbuf[z0 + 4 * _r4(co):z0 + 4 * _r4(co) + co * ci].view(co, ci),
-                             zbuf[z0 + 4 * _r4(co) + co * ci:z0 + 4 * _r4(co) + co * ci + co]))
-        dZ = None
-        red_L = red[offs[L - 1]:offs[L]]
-        dzp = None
-        no_y = pool and Ys[-1] is None                 # the last layer ran without an output: its backward from the layer's input
-        if no_y:
-            pool_ws = saved[3 + 4 * L]
+        dZ = dzp = None
+        if pool and Ys[-1] is None:                    # the last layer ran without an output: its backward from the layer's input
             dzp = torch.empty(G, ldo, device=dev, dtype=torch.float32)
-            _check(lib.pn2_pool_bwd_reduce_rec(_p(grad_out), ld_grad, _p(out), ldo, _p(arg), _p(pool_ws), _p(affs[-1]), G, K, cl, _p(dzp),
-                                               _p(red_L), _p(_contig_weight(Ws[-1])), chans[-2], _p(flat[7 * (L - 1) + 1]), _p(Ys[-2]),
-                                               Ys[-2].shape[1], _p(affs[-2]), chans[-2], st), "pn2_pool_bwd_reduce_rec")
+            _check(lib.pn2_pool_bwd_reduce_rec(_p(grad_out), ld_grad, _p(out), ldo, _p(arg), _p(saved[3 + 4 * L]), _p(affs[-1]), G, K, cl,
+                                               _p(dzp), _p(reds[-1]), _p(_contig_weight(Ws[-1])), chans[-2], _p(flat[7 * (L - 1) + 1]),
+                                               _p(Ys[-2]), Ys[-2].shape[1], _p(affs[-2]), chans[-2], st), "pn2_pool_bwd_reduce_rec")
         elif pool:
             dzp = torch.empty(G, ldo, device=dev, dtype=torch.float32)    # dOut masked by out > 0: the pooled form of dZ_L the GEMM loaders read (pitch ldo, as arg)
             _check(lib.pn2_pool_bwd_reduce_ld(_p(grad_out), ld_grad, _p(out), ldo, _p(arg), _p(Ys[-1]), Ys[-1].shape[1], _p(affs[-1]),
-                                              G, K, cl, _p(dzp), _p(red_L), st), "pn2_pool_bwd_reduce_ld")
+                                              G, K, cl, _p(dzp), _p(reds[-1]), st), "pn2_pool_bwd_reduce_ld")
         else:
             dZ = _empty_rows(P, cl, dev)
             _check(lib.pn2_relu_bwd_reduce(_p(grad_out), ldo, _p(out), _p(Ys[-1]), Ys[-1].shape[1], _p(affs[-1]), P, cl,
-                                           _p(dZ), dZ.shape[1], _p(red_L), st), "pn2_relu_bwd_reduce")
-        grads = [None] * (7 * L)
-        d_rows = None
-        # sa1-style stacks (a first layer on the 48-byte grouped rows, nobody needs d rows): the second layer's fused backward forms
-        # the first layer's sum dZ^T x from its dX tiles (pn2_conv1x1_bwd_first) -- dZ1 is never written -- and the first layer's
-        # weight gradient finishes from the input's moments (pn2_conv1x1_wgrad_cf with dZ == NULL)
+                                           _p(dZ), dZ.shape[1], _p(reds[-1]), st), "pn2_relu_bwd_reduce")
+        # the fused-first route's preconditions (see _bwd_fused_first)
         fuse_first = bool(L >= 3 and ctx.gather is not None and not ctx.needs_input_grad[0] and training and WGRAD_CF and LAZY_BN and
                           chans[0] <= 12 and chans[1] % 16 == 0 and chans[1] <= 128 and rows.shape[1] % 4 == 0 and
                           rows.shape[1] >= 12 and Ys[1] is not None and
                           lib.pn2_conv1x1_bwd_first_supported(P, chans[2], chans[1], chans[0]))
-        first_scratch = None
+        s = types.SimpleNamespace(lib=lib, st=st, ctx=ctx, dev=dev, P=P, K=K, training=training, direct=direct, chans=chans, rows=rows, flat=flat,
+                                  dzp=dzp, arg=arg, ldo=ldo)
+        # ---- loop: per layer the BatchNorm coefficients, one route, the gradient bookkeeping
+        grads = [None] * (7 * L)
+        handoff = None                                 # what the fused-first route hands from layer 1 to layer 0
         for l in range(L - 1, -1, -1):
             co, ci = chans[l + 1], chans[l]
-            y, aff = Ys[l], affs[l]
-            ldy = y.shape[1] if y is not None else 0
-            coef, dgamma, dbeta, dW, dbias = outs[l]
-            w_p = flat[7 * l]
-            # consumer-side BatchNorm backward: the first launch below that reads `coef` fills it from the reductions
+            y, aff, coef = Ys[l], affs[l], pieces[per_layer * l]
+            if direct:
+                dgamma, dbeta, dW, dbias = flat[7 * l + 2].grad, flat[7 * l + 3].grad, flat[7 * l].grad, None
+            else:
+                dgamma, dbeta = (torch.empty(co, device=dev, dtype=torch.float32) for _ in range(2))
+                dW, dbias = pieces[3 * l + 1].view(co, ci), pieces[3 * l + 2]
+            # consumer-side BatchNorm backward: the first launch of the route that reads `coef` fills it from the reductions
+            # (of the factorised first layer's kernels the segmented scatter is such a consumer; the atomics form is not)
+            factorised = l == 0 and ctx.geom is not None and ctx.gather is None
             coef_lazy = None
-            first_layer_special = l == 0 and ctx.geom is not None and ctx.gather is None
-            # (the factorised first layer: its segmented scatter kernel is the consumer; the atomics form is not)
-            seg_ok = not first_layer_special or (ctx.geom[4] is not None and co <= 256)
-            if training and LAZY_BN and seg_ok:
-                cl_struct = _lib.BnCoefLazy(_p(red[offs[l]:offs[l + 1]]), _p(gammas[l]), _p(aff), _p(coef), _p(dgamma), _p(dbeta),
-                                            int(direct), P, co)
+            if training and LAZY_BN and (not factorised or (ctx.geom.inv is not None and co <= 256)):
+                cl_struct = _lib.BnCoefLazy(_p(reds[l]), _p(gammas[l]), _p(aff), _p(coef), _p(dgamma), _p(dbeta), int(direct), P, co)
                 coef_lazy = ctypes.byref(cl_struct)
             else:
-                _check(lib.pn2_bn_bwd_coef(_p(red[offs[l]:offs[l + 1]]), P, co, _p(gammas[l]), _p(aff), int(training),
+                _check(lib.pn2_bn_bwd_coef(_p(reds[l]), P, co, _p(gammas[l]), _p(aff), int(training),
                                            _p(coef), _p(dgamma), _p(dbeta), int(direct), st), "pn2_bn_bwd_coef")
-            if not direct:
-                grads[7 * l + 1], grads[7 * l + 2], grads[7 * l + 3] = dbias, dgamma, dbeta
-            if l == 0 and ctx.geom is not None and ctx.gather is None:
-                d_rows, dW0 = _SharedMLP._first_layer_bwd(ctx, rows, Ws[0], dZ, y, coef, co, ctx.needs_input_grad[0],
-                                                          w_p.grad if direct else None, coef_lazy)
-                grads[0] = dW0
-                continue
             x = rows if l == 0 else Ys[l - 1]
-            x_aff = None if l == 0 else affs[l - 1]
-            ldx = x.shape[1]
-            pooled = dZ is None
-            if not training and direct:
-                raise NotImplementedError("direct gradient accumulation with eval-mode BatchNorm: use autograd mode")
-            need_dx = l > 0 or ctx.needs_input_grad[0]
-            if l == 1 and fuse_first and dZ is not None:
-                first_scratch = _zeros_small(int(lib.pn2_conv1x1_wgrad_cf_scratch_bytes()), dev)
-                rc = lib.pn2_conv1x1_bwd_first(_p(dZ), dZ.shape[1], _p(y), ldy, _p(coef), _p(_contig_weight(Ws[l])), ci, _p(x), ldx, _p(x_aff),
-                                               _p(red[offs[0]:offs[1]]), _p(dW), ci, _p(rows), rows.shape[1], chans[0], _p(first_scratch),
-                                               P, co, ci, coef_lazy, st)
-                if rc != _lib.PN2_EUNSUPPORTED:
-                    _check(rc, "pn2_conv1x1_bwd_first")
-                    if not direct:
-                        grads[7 * l] = dW.view_as(Ws[l])
-                    dZ = None                                       # (the first layer's dZ exists only as the sums above)
-                    continue
-                first_scratch = None
-            if l == 0 and first_scratch is not None:
-                _check(lib.pn2_conv1x1_wgrad_cf(None, 0, _p(coef), _p(x), ldx, _p(_contig_weight(Ws[l])), ci, _p(flat[7 * l + 1]),
-                                                _p(first_scratch), _p(dW), ci, P, co, ci, coef_lazy, st), "pn2_conv1x1_wgrad_cf")
-                if not direct:
-                    grads[7 * l] = dW.view_as(Ws[l])
-                continue
-            if y is None:
-                # pooled last layer without its output: dX and dW from (dZp, arg) and the layer's input alone
-                scratch = torch.empty(int(lib.pn2_conv1x1_bwd_cf_scratch_bytes(co, ci)), device=dev, dtype=torch.uint8)
-                dx = _empty_rows(P, ci, dev)
-                _check(lib.pn2_conv1x1_bwd_cf(_p(dzp), ldo, _p(arg), K, _p(coef), _p(_contig_weight(Ws[l])), ci, _p(flat[7 * l + 1]), _p(x), ldx,
-                                              _p(x_aff), _p(dx), dx.shape[1], _p(red[offs[l - 1]:offs[l]]), _p(dW), ci, P, co, ci, coef_lazy,
-                                              _p(scratch), st), "pn2_conv1x1_bwd_cf")
-                if not direct:
-                    grads[7 * l] = dW.view_as(Ws[l])
-                dZ = dx
-                continue
-            # the two forms of dZ the kernels take: dense rows, or the pooled pair (dZp, arg) with K rows per group
-            c_dz = (None, 0) if pooled else (_p(dZ), dZ.shape[1])
-            c_pool = (_p(dzp), ldo, _p(arg), K) if pooled else (None, 0, None, 0)
-            if (need_dx and training and
-                    lib.pn2_bwd_res_supported(P, co, ci, K if pooled else 0, int(x_aff is not None))):
-                # narrow, long layer: dgrad + wgrad in ONE pass over dZ / Y / Y_prev, weights resident in LDS (mlp_res.hip)
-                dx = _empty_rows(P, ci, dev) if l > 0 else torch.empty(P, ldx, device=dev, dtype=torch.float32)
-                if l == 0:
-                    d_rows = dx
-                _check(lib.pn2_conv1x1_bwd(*c_dz, *c_pool, _p(y), ldy, _p(coef), _p(_contig_weight(Ws[l])), ci, _p(x), ldx,
-                                           _p(x_aff), _p(dx), dx.shape[1], _p(red[offs[l - 1]:offs[l]]) if l > 0 else None,
-                                           _p(dW), ci, P, co, ci, coef_lazy, st), "pn2_conv1x1_bwd")
-                if not direct:
-                    grads[7 * l] = dW.view_as(Ws[l])
-                if l > 0:
-                    dZ = dx
-                continue
-            dx = None
-            if need_dx:
-                w_l = _p(_contig_weight(Ws[l]))             # [co, ci] as stored: the dgrad kernel reads it down the columns
-                w_ld = ci
-                if l in ctx.w_pads:                         # its 16-byte aligned, zero-padded copy made by the forward
-                    w_l, w_ld = _p(ctx.w_pads[l]), ctx.w_pads[l].shape[1]
-                if l > 0:
-                    dx = _empty_rows(P, ci, dev)
-                else:
-                    dx = d_rows = torch.empty(P, ldx, device=dev, dtype=torch.float32)   # pad lanes written (0) by the GEMM
-            pair_key = (P, co, ci, pooled, l > 0)
-            if need_dx and BWD_PAIR and training and pair_key not in _PAIR_RUNS_SPLIT:
-                # data gradient and weight gradient of this layer as ONE call: on the few-row / mid-size layers both kernel
-                # bodies share one launch (pn2_conv1x1_bwd_pair); elsewhere the library issues the two launches itself
-                prev = (_p(x), ldx, _p(x_aff), _p(dx), dx.shape[1], _p(red[offs[l - 1]:offs[l]])) if l > 0 else \
-                    (None, 0, None, _p(dx), ldx, None)
-                rc = lib.pn2_conv1x1_bwd_pair(*c_dz, *c_pool, _p(y), ldy, _p(coef), w_l, w_ld, *prev, _p(x), ldx, _p(x_aff), _p(dW), ci,
-                                              P, co, ci, coef_lazy, st)
-                if rc != _lib.PN2_OK_SPLIT:                 # (1: done as two launches -- not an error)
-                    _check(rc, "pn2_conv1x1_bwd_pair")
-                else:
-                    # the library ran this shape as pn2_conv1x1_dgrad + pn2_conv1x1_wgrad: from now on those two calls are made
-                    # here (same launches, same results) -- a per-launch accounting (bench.py) then sees each kernel by itself
-                    _PAIR_RUNS_SPLIT.add(pair_key)
-            else:
-                if need_dx:
-                    if l > 0:
-                        _check(lib.pn2_conv1x1_dgrad(*c_dz, *c_pool, _p(y), ldy, _p(coef), w_l, w_ld, _p(x), ldx, _p(x_aff), _p(dx),
-                                                     dx.shape[1], _p(red[offs[l - 1]:offs[l]]), P, co, ci, coef_lazy, st), "pn2_conv1x1_dgrad")
-                    else:
-                        _check(lib.pn2_conv1x1_dgrad(*c_dz, *c_pool, _p(y), ldy, _p(coef), w_l, w_ld, None, 0, None, _p(dx),
-                                                     ldx, None, P, co, ci, coef_lazy, st), "pn2_conv1x1_dgrad")
-                    coef_lazy = None                            # filled: the weight gradient below reads it
-                if WGRAD_CF and l == 0 and training and not need_dx and not pooled and ci <= 15 and co % 16 == 0 and co <= 128:
-                    # first layer without a data gradient: the BatchNorm-backward terms of dY in closed form from the input rows'
-                    # first and second moments -- the pass reads dZ and the rows, not Y (pn2_conv1x1_wgrad_cf, include/pn2.h)
-                    scratch = _zeros_small(int(lib.pn2_conv1x1_wgrad_cf_scratch_bytes()), dev)
-                    _check(lib.pn2_conv1x1_wgrad_cf(*c_dz, _p(coef), _p(x), ldx, _p(_contig_weight(Ws[l])), ci,
-                                                    _p(flat[7 * l + 1]), _p(scratch), _p(dW), ci, P, co, ci, coef_lazy, st),
-                           "pn2_conv1x1_wgrad_cf")
-                else:
-                    ws_bytes = lib.pn2_conv1x1_wgrad_workspace_bytes(P, co, ci, int(pooled)) if training else 0
-                    if ws_bytes:                                # two-phase dW flush of the full-tile kernel: caller scratch
-                        ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
-                        _check(lib.pn2_conv1x1_wgrad_ws(*c_dz, *c_pool, _p(y), ldy, _p(coef), _p(x), ldx, _p(x_aff), _p(dW), ci, None, P, co, ci,
-                                                        coef_lazy, _p(ws), st), "pn2_conv1x1_wgrad_ws")
-                    else:
-                        _check(lib.pn2_conv1x1_wgrad(*c_dz, *c_pool, _p(y), ldy, _p(coef), _p(x), ldx, _p(x_aff), _p(dW), ci,
-                                                     None if training else _p(dbias), P, co, ci, coef_lazy, st), "pn2_conv1x1_wgrad")
+            a = types.SimpleNamespace(l=l, co=co, ci=ci, w=Ws[l], y=y, coef=coef, coef_lazy=coef_lazy, dZ=dZ, pooled=dZ is None,
+                                      x=x, ldx=x.shape[1], x_aff=None if l == 0 else affs[l - 1], prev_red=reds[l - 1] if l > 0 else None,
+                                      need_dx=l > 0 or ctx.needs_input_grad[0], dW=dW, dbias=dbias, handoff=handoff,
+                                      pair_key=(P, co, ci, dZ is None, l > 0))
+            dZ, dW, handoff = _bwd_route(s, a, fuse_first)(s, a)
             if not direct:
-                grads[7 * l] = dW.view_as(Ws[l])
-            if l > 0:
-                dZ = dx
-        if ctx.gather is not None and d_rows is not None:          # gradient of the grouped rows -> the gathered source points
+                grads[7 * l:7 * l + 4] = dW.view_as(Ws[l]), dbias, dgamma, dbeta
+        d_rows = dZ                                    # (of the first layer's input; None where nobody asked for it)
+        # ---- epilogue: gradient of the grouped rows -> the gathered source points
+        if ctx.gather is not None and d_rows is not None:
             gB, gN, gD = ctx.gather
-            g_idx = ctx.geom[2]
+            g_idx = ctx.geom.idx
             gp = _zeros_f32((gB, gN, gD), dev)
-            _check(lib.pn2_group_bwd(_p(d_rows), _p(g_idx), gB, gN, g_idx.shape[1], g_idx.shape[2], gD, int(ctx.geom[3]),
+            _check(lib.pn2_group_bwd(_p(d_rows), _p(g_idx), gB, gN, g_idx.shape[1], g_idx.shape[2], gD, int(ctx.geom.xyz_first),
                                      d_rows.shape[1], _p(gp), st), "pn2_group_bwd")
             d_rows = gp
         return (d_rows, None, None, None, None, None, None) + tuple(grads)
-
-    @staticmethod
-    def _first_layer_bwd(ctx, feats, w, dZ, y, coef, co, need_dfeat, w_grad, coef_lazy=None):
-        """Backward of the factorised first layer: scatter dY to the source points, then two small GEMMs.
-        ``w_grad``: None (return dW) or the [co, 3+D] gradient tensor to accumulate into (returns None)."""
-        lib, st = _lib.load(), _lib.stream()
-        g_xyz, g_new, g_idx, g_first, g_inv = ctx.geom
-        B, N, D = feats.shape
-        S, K = g_idx.shape[1], g_idx.shape[2]
-        dev = feats.device
-        ldc, ldd = _r4(co), _r4(D)
-        ident = _ident_coef(co, dev)                  # dY := 1*G + 0*(y-0) + 0
-        dW = _zeros_small(4 * co * (3 + D), dev).view(torch.float32).view(co, 3 + D) if w_grad is None else w_grad
-        ldw = 3 + D
-        x_col, f_col = (0, 3) if g_first else (D, 0)
-        G = _zeros_f32((B * N, ldc), dev)
-        if g_inv is not None and co <= 256:           # segmented reduction over the source-sorted ball-query index
-            scratch = _zeros_small(4 * _lib.DWX_REPLICAS * 3 * ldc, dev) if DWX_REPLICAS_SCRATCH else None
-            _check(lib.pn2_group_affine_bwd_seg(_p(dZ), dZ.shape[1], _p(y), y.shape[1], _p(coef), _p(g_xyz), _p(g_new),
-                                                _p(g_inv[0]), _p(g_inv[1]), B, N, S, K, co, _p(G), ldc,
-                                                dW.data_ptr() + 4 * x_col, ldw, _p(scratch), coef_lazy, st), "pn2_group_affine_bwd_seg")
-        else:
-            _check(lib.pn2_group_affine_bwd(_p(dZ), dZ.shape[1], _p(y), y.shape[1], _p(coef), _p(g_xyz), _p(g_new),
-                                            _p(g_idx), B, N, S, K, co, _p(G), ldc, dW.data_ptr() + 4 * x_col, ldw, st),
-                   "pn2_group_affine_bwd")
-        feat = feats.reshape(B * N, D)
-        if ldd != D:
-            feat = torch.nn.functional.pad(feat, (0, ldd - D)).contiguous()
-        _check(lib.pn2_conv1x1_wgrad(_p(G), ldc, None, 0, None, 0, _p(G), ldc, _p(ident), _p(feat), ldd, None,
-                                     dW.data_ptr() + 4 * f_col, ldw, None, B * N, co, D, None, st), "pn2_conv1x1_wgrad")
-        d_feats = None
-        if need_dfeat:
-            wf_ptr = _contig_weight(w).data_ptr() + (12 if g_first else 0)      # feature columns of the [co, 3+D] weight
-            wf_ld = 3 + D
-            if "wf" in ctx.w_pads:                   # their zero-padded copy made by the forward (D % 4 == 1, features first)
-                wf_ptr, wf_ld = ctx.w_pads["wf"].data_ptr(), ctx.w_pads["wf"].shape[1]
-            dF = _empty_rows(B * N, D, dev)
-            _check(lib.pn2_conv1x1_dgrad(_p(G), ldc, None, 0, None, 0, _p(G), ldc, _p(ident), wf_ptr, wf_ld, None, 0, None,
-                                         _p(dF), ldd, None, B * N, co, D, None, st), "pn2_conv1x1_dgrad")
-            d_feats = (dF[:, :D] if ldd != D else dF).reshape(B, N, D)
-        return d_feats, (dW.view_as(w) if w_grad is None else None)
 
 
 class _Conv1x1(torch.autograd.Function):
@@ -1132,22 +1174,19 @@ class _Conv1x1(torch.autograd.Function):
             g[:, :co] = grad
         else:
             g = grad.contiguous()
-        ident = _ident_coef(co, dev)                       # dY := 1*g + 0*(y - 0) + 0
+        dy = _UpGrad.linear(g, co)
         direct = _direct_ok(ctx.params)                    # the kernel's atomics add straight into .grad (see set_direct_grad_accumulation)
         if direct:
             dW, db = ctx.params[0].grad.view(co, ci), ctx.params[1].grad
         else:
-            zb = _zeros_small(4 * (co * ci + co), dev).view(torch.float32)
-            dW = zb[:co * ci].view(co, ci)
-            db = zb[co * ci:]
-        _check(lib.pn2_conv1x1_wgrad(_p(g), ldy, None, 0, None, 0, _p(g), ldy, _p(ident), _p(rows), ldx, None, _p(dW), ci,
-                                     _p(db), P, co, ci, None, st), "pn2_conv1x1_wgrad")
+            dW, db = _carve(dev, [(torch.float32, co * ci), (torch.float32, co)])
+            dW = dW.view(co, ci)
+        _check(lib.pn2_conv1x1_wgrad(*dy, _p(rows), ldx, None, _p(dW), ci, _p(db), P, co, ci, None, st), "pn2_conv1x1_wgrad")
         d_rows = None
         if ctx.needs_input_grad[0]:
             d_rows = torch.empty(P, ldx, device=dev, dtype=torch.float32)     # pad lanes written (0) by the GEMM
-            _check(lib.pn2_conv1x1_dgrad(_p(g), ldy, None, 0, None, 0, _p(g), ldy, _p(ident), _p(_contig_weight(weight)), ci,
-                                         None, 0, None,
-                                         _p(d_rows), ldx, None, P, co, ci, None, st), "pn2_conv1x1_dgrad")
+            _check(lib.pn2_conv1x1_dgrad(*dy, _p(_contig_weight(weight)), ci, None, 0, None, _p(d_rows), ldx, None, P, co, ci, None, st),
+                   "pn2_conv1x1_dgrad")
         if direct:
             return d_rows, None, None, None
         return d_rows, dW.view_as(weight), db, None
@@ -1347,12 +1386,13 @@ def grouped_mlp(xyz, points, new_xyz, idx, xyz_first, convs, bns, training, inv=
         return fused_eval_grouped(xyz, points, new_xyz, idx.contiguous(), S, K, xyz_first, convs, bns)
     if _factorised(D, len(convs), training):
         flat, cfg = _flat_params(convs, bns)
-        return _SharedMLP.apply(points, 3 + D, K, training, cfg, (xyz, new_xyz, idx, xyz_first, inv), dest, *flat)
+        return _SharedMLP.apply(points, 3 + D, K, training, cfg, _GroupGeom(xyz, new_xyz, idx, bool(xyz_first), inv, False), dest, *flat)
     if (GATHER_CONV and 1 <= D <= 9 and convs[0].out_channels in (32, 64) and (B * S * K) % 64 == 0 and new_xyz is not None and
             idx is not None):
         # narrow first layer (the sa1 stacks): pn2_group and the first conv are one launch (pn2_group_conv_fwd)
         flat, cfg = _flat_params(convs, bns)
-        return _SharedMLP.apply(points, 3 + D, K, training, cfg, (xyz, new_xyz, idx.contiguous(), xyz_first, None, True), dest, *flat)
+        return _SharedMLP.apply(points, 3 + D, K, training, cfg, _GroupGeom(xyz, new_xyz, idx.contiguous(), bool(xyz_first), None, True),
+                                dest, *flat)
     rows = _Group.apply(xyz, points, new_xyz, idx, S, K, xyz_first)
     return shared_mlp(rows, 3 + D, convs, bns, K, training, dest)
 
