@@ -606,14 +606,16 @@ int pn2_point_transform(const float *X, int ldx, const float *T, int B, int N, i
 /* Its backward: dX = dOut * T_b^T (dX != NULL, pitch lddx, pad columns written as zeros) and dT_b = sum_n X_n^T dOut_n
  * (dT != NULL: [B, k, k], STORED; X required).  dT is summed per 256-row slab into `workspace`
  * (pn2_point_transform_workspace_bytes(B, N, k) bytes, 4-byte aligned, contents irrelevant) and the slabs are added in a fixed
- * order by a second launch: run-to-run identical, no atomics.  dOut pitch ldd (multiple of 4, >= round4(k), pad columns zero). */
+ * order by a second launch: run-to-run identical, no atomics.  dOut pitch ldd (multiple of 4, >= round4(k), pad columns zero).
+ * Every argument is checked before the first launch: a refused call (PN2_EINVAL) has written neither dX nor dT. */
 int64_t pn2_point_transform_workspace_bytes(int B, int N, int k);
 int pn2_point_transform_bwd(const float *dOut, int ldd, const float *X, int ldx, const float *T, int B, int N, int k, float *dX, int lddx,
                             float *dT, void *workspace, pn2_stream_t stream);
 /* pn2_bn_relu_max WITHOUT the ReLU (the encoder's bn3(conv3(x)) then torch.max over all points): out[g,c] = max_k bn(Y[g*K+k, c]),
  * bn(y) = fma(y - mean, scale, beta) from the affine block; arg[g,c] = the first k attaining it (a negative gamma selects the
  * smallest y; a zero gamma gives beta everywhere and names row 0).  Pitches as pn2_bn_relu_max; pad columns are written (0).
- * Any K. */
+ * Any K.  Finite inputs only are tested: the comparison is a strict `>`, so a NaN is skipped, not propagated as torch.max does
+ * (a group whose every bn(y) is NaN, or -inf, gives out = -inf and arg = 0). */
 int pn2_bn_max(const float *Y, int ldy, const float *affine, int64_t G, int K, int C, float *out, int ldo, int32_t *arg,
                pn2_stream_t stream);
 /* Its backward: dZp[g,c] = dOut[g,c] (pitch ldo like arg, pad lanes zero; dOut at any pitch ld_dout >= C), red (replicated,

@@ -323,15 +323,15 @@ int pn2_point_transform_bwd(const float *dOut, int ldd, const float *X, int ldx,
     PN2_CHECK_ARG(dOut && T && B > 0 && B <= 65535 && N > 0 && k > 0 && k <= kTfMaxK && (dX || dT));
     const int kp = (k + 3) & ~3;
     PN2_CHECK_ARG(ldd % 4 == 0 && ldd >= kp);
+    PN2_CHECK_ARG(dX == nullptr || (lddx % 4 == 0 && lddx >= kp));              // (every refusal before the first launch)
+    PN2_CHECK_ARG(dT == nullptr || (X && workspace && ldx % 4 == 0 && ldx >= kp));
     if (dX) {
-        PN2_CHECK_ARG(lddx % 4 == 0 && lddx >= kp);
         hipLaunchKernelGGL(point_transform_kernel<true>, dim3((unsigned)pn2_cdiv(N, kTfRows), (unsigned)B), dim3(256),
                            (size_t)kp * kp * sizeof(float), pn2_s(stream), dOut, ldd, T, N, k, dX, lddx);
         const int rc = pn2_launch_status();
         if (rc != PN2_OK) return rc;
     }
     if (dT) {
-        PN2_CHECK_ARG(X && workspace && ldx % 4 == 0 && ldx >= kp);
         const int nch = (int)pn2_cdiv(N, kTfRows);
         float *part = static_cast<float *>(workspace);
         hipLaunchKernelGGL(point_transform_dt_part_kernel, dim3((unsigned)nch, (unsigned)B), dim3(256), 0, pn2_s(stream), X, ldx, dOut, ldd,

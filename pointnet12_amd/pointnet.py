@@ -116,8 +116,8 @@ class _ConvBnMax(torch.autograd.Function):
         N, training, P, G, co, ci = ctx.meta
         dev = x.device
         ldo = arg.shape[1]
-        if grad.stride(-1) != 1 or grad.dtype != torch.float32:
-            grad = grad.contiguous().float()
+        if grad.stride(-1) != 1 or grad.stride(0) < co or grad.dtype != torch.float32:     # (a row-broadcast gradient, as .sum(0)
+            grad = grad.contiguous().float()                                                # hands back, has pitch 0)
         red, coef, dW, db = _carve(dev, [(torch.float64, _REPL * 2 * co), (torch.float32, 4 * _r4(co)), (torch.float32, co * ci),
                                          (torch.float32, co)])
         dW = dW.view(co, ci)
