@@ -999,6 +999,67 @@ int pn2_voxel_components(const float *pts, int ld, const int64_t *row_begin, con
                          int32_t *comp_points, int32_t *comp_voxels, int32_t *comp_label, int64_t *comp_count, int *err, void *workspace,
                          pn2_stream_t stream);
 
+/* ---- camera colour lookup for points (csrc/image.hip), added within ABI 15 (purely additive: no version change) -------------------
+ * pn2_sample_image writes the colour of the pixel under each projected point: the per-point loop of
+ * data_utils/ColorGenerator_Loader.py:63-65 (`pts_color[i] = frame_HSV[row, col]` inside the frame) and the divisions of :68-69, for
+ * a batch of B clouds whose rows lie back to back in device memory.  One plain launch; no host synchronisation, no allocation.
+ *   pix        int32 [rows, 2] (8-byte aligned), exactly what pn2_project_points writes: x = column, y = row, INT32_MIN in both
+ *              for an unprojectable point.
+ *   image      uint8 [B, H, W, 3], contiguous, device memory; cloud b reads image b only.  H * W * 3 < 2^31 per image.
+ *   channel_order  PN2_CHANNELS_RGB: the bytes of a pixel are R, G, B; PN2_CHANNELS_BGR: B, G, R (a cv2.imread frame, read in place).
+ *   mode / normalize   PN2_IMAGE_RGB or PN2_IMAGE_HSV; 0 or 1.
+ *   row_begin, row_count   int64[B], DEVICE memory, with the host bound max_rows (0 <= max_rows < 2^31): pn2_scan_filter's
+ *              conventions.  Cloud b is rows [row_begin[b], row_begin[b] + min(max(row_count[b], 0), max_rows)) of pix, out and
+ *              valid.  Rows at or beyond the device-side count are NOT TOUCHED, so a captured launch stays valid when the count
+ *              changes; a negative count is 0.  Both NULL (B must be 1): rows [0, max_rows).
+ *   rows       host: how many rows pix, out and valid hold (rows >= max_rows).  A cloud whose rows would leave [0, rows) -- a stale
+ *              or corrupt row_begin[b] / row_count[b] -- is skipped WHOLE: nothing of it is read or written, and *err (device int,
+ *              caller zeroes, may be NULL) receives PN2_IMAGE_ERR_ROWS.
+ *   out        float32 rows of pitch ldo >= 3 floats; EXACTLY three columns per row are written.  The caller may pass a pointer into
+ *              a wider row: with out = rows + 4, ldo = 7 the rows x, y, z, i, c0, c1, c2 are painted in place.
+ *   valid      uint8 [rows] (1: the point is in the image), may be NULL.
+ * THE RULE, per point (x, y):
+ *   in the image iff 0 <= y && y < H && 0 <= x && x < W -- the reference's test (:64, whose names x / y are swapped).  It works on
+ *   TRUNCATED coordinates: a projected coordinate in (-1, 0) has become 0 and counts as inside.  That quirk is kept.
+ *   outside the image, or INT32_MIN: three +0.0 and valid = 0.
+ *   NO DEPTH TEST: as in the reference, a point BEHIND the camera that projects into the frame takes that pixel.  The caller
+ *   filters first (pn2_scan_filter with the `inview` angles keeps only what the camera sees).
+ *   mode RGB: (float)R, (float)G, (float)B; normalised: each divided by 255.0f, one IEEE float32 division.
+ *   mode HSV: OpenCV's 8-bit COLOR_BGR2HSV integers as floats, by this rule on the integers r, g, b:
+ *     v = max(r, g, b);  d = v - min(r, g, b);  s = (d * sdiv[v] + 2048) >> 12;
+ *     h0 = (v == r) ? g - b : (v == g) ? b - r + 2 d : r - g + 4 d   (tested in that order);
+ *     h = (h0 * hdiv[d] + 2048) >> 12 (an arithmetic shift), plus 180 if negative;
+ *     sdiv[i] = rint(255 * 4096 / i), hdiv[i] = rint(180 * 4096 / (6 i)), round-half-even in fp64, both 0 at i = 0.
+ *     The output is (h, s, v): h in 0 .. 179, s and v in 0 .. 255.
+ *   HSV normalised: h / 180.0f, s / 255.0f, v / 255.0f as float32 divisions (:68-69, numpy's in-place float32 `/=`): true
+ *   divisions, not reciprocal multiplies.
+ *   THE HSV RULE IS WRITTEN FROM MEMORY OF OPENCV'S SCALAR CODE AND IS UNVERIFIED AGAINST OPENCV, which was not available where this
+ *   was written.  It was checked against the real-valued definition over all 2^24 colours: the hue stays within 0.640 of
+ *   30 * sector (circular distance), the saturation within 0.522 of 255 d / v (tests/test_image_sample_cpu.py).
+ * PN2_EINVAL without a launch for a null pix / image / out, B < 1 or B > 65535, H or W < 1, H * W * 3 >= 2^31, ldo < 3, an
+ * unknown channel_order / mode / normalize, max_rows < 0 or >= 2^31, exactly one of row_begin / row_count NULL, both NULL with
+ * B != 1, a pix that is not 8-byte aligned, rows < max_rows.  max_rows == 0 launches nothing. */
+#define PN2_CHANNELS_RGB 0
+#define PN2_CHANNELS_BGR 1
+#define PN2_IMAGE_RGB 0
+#define PN2_IMAGE_HSV 1
+#define PN2_IMAGE_ERR_ROWS 1
+int pn2_sample_image(const int32_t *pix, const uint8_t *image, int B, int H, int W, int channel_order, int mode, int normalize,
+                     const int64_t *row_begin, const int64_t *row_count, int64_t max_rows, int64_t rows, float *out, int ldo,
+                     uint8_t *valid, int *err, pn2_stream_t stream);
+/* pn2_hsv_to_rgb is the way back, for looking at a prediction (the step the reference has commented out at :66-67).  hsv: N float32
+ * rows of pitch ld >= 3, three normalised columns (h in units of 180, s and v in units of 255: what pn2_sample_image writes in mode
+ * HSV, normalised); out uint8 [N, 3] in the given channel order.  THIS IS THIS PACKAGE'S OWN DEFINITION: OpenCV's HSV2RGB is
+ * float-based and is not claimed bit for bit.  In fp64 on the float32 inputs, every operation rounded separately (no fused
+ * multiply-add):
+ *   s, v clamped to [0, 1];  h6 = (h - floor(h)) * 6;  k = min((int)h6, 5);  f = h6 - k;
+ *   p = v * (1 - s),  q = v * (1 - s * f),  t = v * (1 - s * (1 - f));
+ *   (r, g, b) = (v, t, p), (q, v, p), (p, v, t), (p, q, v), (t, p, v), (v, p, q) for k = 0 .. 5;
+ *   each channel is rint(255 * c), round-half-even.
+ * A NaN input (or an infinite h, whose fraction is NaN) gives a black pixel.  PN2_EINVAL for ld < 3, N < 0, an unknown
+ * channel_order, a null pointer with N > 0. */
+int pn2_hsv_to_rgb(const float *hsv, int ld, int64_t N, int channel_order, uint8_t *out, pn2_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

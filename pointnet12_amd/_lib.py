@@ -108,6 +108,8 @@ SIGNATURES = {
     "pn2_splat_resolve": (_i, [_vp, _i, _i, _vp, _i64, _vp, _i, _vp, _vp, _vp, _vp]),
     "pn2_depth_splat": (_i, [_vp, _i, _i64, _vp, _vp, _d, _d, _i, _i, _i, _vp, _vp]),
     "pn2_depth_resolve": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "pn2_sample_image": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i64, _i64, _vp, _i, _vp, _vp, _vp]),
+    "pn2_hsv_to_rgb": (_i, [_vp, _i, _i64, _i, _vp, _vp]),
     "pn2_scan_filter_workspace_bytes": (_i64, [_i, _i64]),
     "pn2_scan_filter": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pn2_knn": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
@@ -130,6 +132,9 @@ PN2_OK_SPLIT = 1                 # pn2_conv1x1_bwd_pair: done as two launches
 DWX_REPLICAS = 32        # PN2_DWX_REPLICAS of include/pn2.h
 SCAN_TILE = 1024         # PN2_SCAN_TILE of include/pn2.h: rows per workgroup of pn2_scan_filter
 SCAN_ERR_CLASS, SCAN_ERR_ROWS = 1, 2     # PN2_SCAN_ERR_* of include/pn2.h
+CHANNELS_RGB, CHANNELS_BGR = 0, 1         # PN2_CHANNELS_* of include/pn2.h: pn2_sample_image / pn2_hsv_to_rgb
+IMAGE_RGB, IMAGE_HSV = 0, 1               # PN2_IMAGE_* of include/pn2.h: pn2_sample_image's mode
+IMAGE_ERR_ROWS = 1                        # PN2_IMAGE_ERR_ROWS: a cloud's rows left the buffers and were skipped
 KNN_MAX_K = 32           # pn2_knn / pn2_knn_vote: larger K is PN2_EUNSUPPORTED
 KNN_ERR_LABEL, KNN_ERR_DST = 1, 2        # the err bits of pn2_knn_vote
 VOXEL_TILE = 1024        # PN2_VOXEL_TILE of include/pn2.h: rows per workgroup of pn2_voxel_grid's compaction passes

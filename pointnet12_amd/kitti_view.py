@@ -13,6 +13,9 @@ one ``cv2.circle`` at a time (``draw_2d_points``, data_utils/kitti_utils.py:368-
     pinhole camera of ``config/ego_view.json`` (``PinholeCamera.from_json``), square points of ``config/render_option.json``'s
     size (``RenderOption.from_json``), nearest point per pixel -- ``pn2_depth_splat`` + ``pn2_depth_resolve`` +
     ``pn2_splat_resolve``; also the depth image and the index image (which point is visible where) of a cloud;
+  * ``sample_image`` / ``paint_points`` / ``hsv_to_rgb``   the image -> points direction, on ``csrc/image.hip``: the colour of the pixel
+    under each projected point (the per-point loop of data_utils/ColorGenerator_Loader.py:59-69), RGB or OpenCV-style 8-bit HSV,
+    and the way back for looking at a prediction -- ``pn2_sample_image`` / ``pn2_hsv_to_rgb``;
   * ``FrameSegmenter``                the frame loop's body, device tensors in and out, nothing read back.
 
 Nothing here copies the reference's tables: class names and colours come from the dataset's own ``semantic-kitti.yaml``
@@ -41,6 +44,14 @@ Differences from the reference, all deliberate:
     hold the kernel to an fp64 restatement of that rule, not to open3d; a pixel here and there may differ from open3d's window.
   * THE EGO VIEW'S NEAR / FAR PLANES ARE THIS PACKAGE'S CHOICE (0.1 and 1000 in the cloud's units), also unverified: open3d
     derives its clipping planes from the scene's bounding box.  Lighting, normals and the coordinate frame are not drawn.
+  * THE HSV RULE IS UNVERIFIED AGAINST OPENCV.  ``sample_image(mode="hsv")`` states OpenCV's 8-bit ``COLOR_BGR2HSV`` as an integer
+    rule written from memory of OpenCV's scalar code (include/pn2.h, ``pn2_sample_image``); OpenCV was not available where this
+    was written.  The rule was checked against the real-valued definition over all 2^24 colours (hue within 0.640 of
+    ``30 * sector``, saturation within 0.522 of ``255 d / v``); the tests hold the kernel to the rule, not to OpenCV.
+    ``hsv_to_rgb`` is this package's own fp64 definition; OpenCV's float-based ``HSV2RGB`` is not claimed bit for bit.
+  * ``sample_image`` has NO DEPTH TEST, as the reference has none: a point behind the camera that projects into the frame takes
+    that pixel.  Filter first (``kitti.ScanFilter`` with the ``inview`` subset).  Its in-image test works on TRUNCATED pixel
+    coordinates, as the reference's does: a projected coordinate in (-1, 0) has become 0 and counts as inside.
   * float32 log-probabilities on the GPU only: a CPU tensor raises ``Pn2Error``; there is no fallback path.
 """
 import ctypes
@@ -338,13 +349,18 @@ def draw_2d_points(pts_2d, labels, colors, image=None, size=(375, 1242), radius=
     A label outside ``[0, C)`` paints nothing and sets ``err`` (a zeroed device int32 tensor).  Without ``err`` the flag is
     read back and raises ``IndexError`` (skipped under stream capture).  ``out`` / ``owner``: the image and a uint32-sized
     (int32) ``[H * W]`` scratch to write into; with both and ``err`` given the call allocates nothing."""
-    if not isinstance(pts_2d, torch.Tensor) or not pts_2d.is_cuda or not isinstance(labels, torch.Tensor) or not labels.is_cuda:
+    if not isinstance(pts_2d, torch.Tensor) or not pts_2d.is_cuda or \
+            (labels is not None and (not isinstance(labels, torch.Tensor) or not labels.is_cuda)):
         raise _lib.Pn2Error("draw_2d_points: points and labels must live on the GPU: this package has no CPU path")
     radius, hw = _half_widths(radius, half_widths)
     dev = pts_2d.device
     if pts_2d.dim() != 2 or pts_2d.shape[1] != 2:
         raise AssertionError(tuple(pts_2d.shape))
     N = int(pts_2d.shape[0])
+    if labels is None:                                               # per-point colours: point i paints colors[i]
+        if tuple(np.shape(colors)) != (N, 3):
+            raise ValueError("draw_2d_points: without labels, colors must be uint8 [%d, 3], one row per point" % N)
+        labels = torch.arange(N, device=dev, dtype=torch.int64)
     if labels.numel() != N or labels.dtype != torch.int64:
         raise ValueError("draw_2d_points: labels must be int64 [%d]" % N)
     pix = pts_2d.contiguous() if pts_2d.dtype == torch.int32 else to_pixels(pts_2d.detach())
@@ -380,6 +396,153 @@ def draw_2d_top_view(pcd_3d, labels, colors, out=None, owner=None, err=None):
     """The 600 x 800 top view of ``draw_2d_top_view`` (kitti_utils.py:381-392) of NORMALISED points ``[N, >= 3]``: discs of radius
     3 at ``(Y, X)``, on black."""
     return draw_2d_points(top_view_pixels(pcd_3d), labels, colors, None, (600, 800), 3, None, out, owner, err)
+
+
+# ------------------------------------------------------------------------------------------------------------ image -> points
+_MODES = {"rgb": _lib.IMAGE_RGB, "hsv": _lib.IMAGE_HSV}
+_ORDERS = {"rgb": _lib.CHANNELS_RGB, "bgr": _lib.CHANNELS_BGR}
+
+
+def _code(table, key, what):
+    if key not in table:
+        raise ValueError("%s must be one of %s (got %r)" % (what, sorted(table), key))
+    return table[key]
+
+
+def _color_rows(out, M, dev, what, zero):
+    """The ``out`` of ``sample_image``: float32 ``[M, 3]`` whose rows may be a column slice of wider rows -> (tensor, pitch)."""
+    if out is None:
+        out = (torch.zeros if zero else torch.empty)(M, 3, device=dev, dtype=torch.float32)
+    elif not isinstance(out, torch.Tensor) or out.shape != (M, 3) or out.dtype != torch.float32 or out.device != dev or \
+            (M > 0 and out.stride(1) != 1) or (M > 1 and not 3 <= out.stride(0) < 2 ** 31):
+        raise ValueError("%s: out must be float32 [%d, 3] on %s with adjacent columns (a column slice of wider rows is fine)"
+                         % (what, M, dev))
+    return out, int(out.stride(0)) if M > 1 else 3
+
+
+def sample_image(pts_2d_or_pix, image, mode="rgb", normalize=True, channel_order="rgb", out=None, valid=None, row_begin=None,
+                 row_count=None, max_rows=None, err=None):
+    """``(colors float32 [M, 3], valid bool [M])``: the colour of the pixel under each point -- the loop of
+    data_utils/ColorGenerator_Loader.py:63-65 and the divisions of :68-69, one ``pn2_sample_image`` launch.  ``pts_2d_or_pix``: int32
+    ``[M, 2]`` pixels ``(x = column, y = row)`` as ``project_3d_to_2d(..., return_pixels=True)`` gives them, or float ``[M, 2]``
+    (cast as ``to_pixels`` does).  ``image``: uint8 ``[H, W, 3]`` or ``[B, H, W, 3]`` on the device, its bytes in ``channel_order``
+    (``"bgr"``: a ``cv2.imread`` frame, read in place).  ``mode="rgb"``: R, G, B; ``"hsv"``: OpenCV's 8-bit H (0 .. 179), S, V
+    by the integer rule of include/pn2.h (UNVERIFIED against OpenCV, see the module docstring).  ``normalize``: divided by 255
+    (the hue by 180) in float32, as the reference stores them.  A point outside the image (or unprojectable) gets three zeros and
+    ``valid = False``; there is no depth test.
+
+    ``out``: float32 ``[M, 3]`` to write into; a column slice of wider rows (``rows[:, 4:7]``) is painted in place.  ``valid``: a
+    uint8 or bool ``[M]`` buffer.  ``row_begin`` / ``row_count`` (int64 ``[B]`` on the device) and ``max_rows`` (host bound of every
+    count; default ``M``): cloud ``b`` is rows ``[row_begin[b], row_begin[b] + row_count[b])`` and reads ``image[b]``; rows beyond a
+    count, or beyond ``max_rows``, are not touched (zeros where this call allocated them).  A cloud whose rows would leave
+    ``[0, M)`` -- a stale count or begin -- is skipped whole, nothing of it read or written, and ``err`` (a zeroed device int32
+    tensor of one element, optional) receives ``_lib.IMAGE_ERR_ROWS``.
+    Nothing is read back: with ``out`` and ``valid`` given (and int32 pixels) the call allocates nothing and can be captured."""
+    if not isinstance(pts_2d_or_pix, torch.Tensor) or not pts_2d_or_pix.is_cuda or not isinstance(image, torch.Tensor) or not image.is_cuda:
+        raise _lib.Pn2Error("sample_image: points and image must live on the GPU: this package has no CPU path")
+    if pts_2d_or_pix.dim() != 2 or pts_2d_or_pix.shape[1] != 2:
+        raise AssertionError(tuple(pts_2d_or_pix.shape))
+    dev = pts_2d_or_pix.device
+    pix = pts_2d_or_pix.contiguous() if pts_2d_or_pix.dtype == torch.int32 else to_pixels(pts_2d_or_pix.detach())
+    M = int(pix.shape[0])
+    if image.dtype != torch.uint8 or image.dim() not in (3, 4) or image.shape[-1] != 3 or image.device != dev:
+        raise ValueError("sample_image: image must be uint8 [H, W, 3] or [B, H, W, 3] on %s" % dev)
+    image = image.contiguous()
+    B = int(image.shape[0]) if image.dim() == 4 else 1
+    H, W = int(image.shape[-3]), int(image.shape[-2])
+    if H < 1 or W < 1 or H * W * 3 >= 2 ** 31:
+        raise ValueError("sample_image: an image must hold 1 <= H * W * 3 < 2^31 bytes")
+    if (row_begin is None) != (row_count is None) or (row_count is None and B != 1):
+        raise ValueError("sample_image: row_begin and row_count come together, and a batch of images needs them")
+    for t in (row_begin, row_count):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.device != dev or t.numel() != B
+                              or not t.is_contiguous()):
+            raise ValueError("sample_image: row_begin / row_count must be contiguous int64 [%d] tensors on %s" % (B, dev))
+    max_rows = M if max_rows is None else int(max_rows)
+    if not 0 <= max_rows <= M:
+        raise ValueError("sample_image: max_rows must lie in [0, %d]" % M)
+    partial = row_count is not None or max_rows < M                  # rows may stay untouched: what is allocated here is zeroed
+    out, ldo = _color_rows(out, M, dev, "sample_image", partial)
+    if err is not None and (not isinstance(err, torch.Tensor) or err.dtype != torch.int32 or err.numel() != 1 or err.device != dev):
+        raise ValueError("sample_image: err must be an int32 tensor of one element on %s" % dev)
+    order, what = _code(_ORDERS, channel_order, "channel_order"), _code(_MODES, mode, "mode")
+    if valid is None:
+        valid = (torch.zeros if partial else torch.empty)(M, device=dev, dtype=torch.uint8)
+    elif not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.uint8, torch.bool) or valid.shape != (M,) or \
+            not valid.is_contiguous() or valid.device != dev:
+        raise ValueError("sample_image: valid must be a contiguous uint8 or bool [%d] tensor on %s" % (M, dev))
+    if max_rows > 0:
+        _check(_lib.load().pn2_sample_image(_p(pix), _p(image), B, H, W, order, what, int(bool(normalize)), _p(row_begin),
+                                            _p(row_count), max_rows, M, _p(out), ldo, _p(valid), _p(err), _lib.stream()),
+               "pn2_sample_image")
+    return out, valid.view(torch.bool)
+
+
+def paint_points(points, calib, image, mode="rgb", normalize=True, channel_order="rgb", out=None, pix=None, valid=None,
+                 row_begin=None, row_count=None, max_rows=None, return_valid=False, err=None):
+    """``[M, C + 3]`` float32 rows: ``points`` (float32 ``[M, C >= 3]``, velodyne x, y, z first) with the camera colour of each point
+    appended -- ``project_3d_to_2d`` then ``sample_image`` (two launches of the library, nothing read back), the first step of the
+    colour-generation task (ColorGenerator_Loader.py:58-71: ``[M, 7]`` rows x, y, z, i, c0, c1, c2).  ``image`` and the colour
+    arguments are ``sample_image``'s; for a batch (``image`` ``[B, H, W, 3]`` with ``row_begin`` / ``row_count``) one calibration
+    serves all clouds.  ``out``: contiguous float32 ``[M, C + 3]`` to write into (``out[:, :C]`` may BE ``points``: nothing is
+    copied then); ``pix``: int32 ``[M, 2]``, ``valid``: uint8 / bool ``[M]`` buffers.  With all three given the call allocates
+    nothing and can be captured.  ``return_valid``: return ``(rows, valid bool [M])``.  Rows outside every count (or beyond
+    ``max_rows``) keep their points and get NO colour: zeros where this call allocated ``out``, whatever a given ``out`` held.
+    ``err``: ``sample_image``'s."""
+    pts, M, _ = _xyz_rows(points, "paint_points")
+    C, dev = int(points.shape[1]), pts.device
+    if out is None:
+        partial = row_count is not None or (max_rows is not None and int(max_rows) < M)
+        out = (torch.zeros if partial else torch.empty)(M, C + 3, device=dev, dtype=torch.float32)
+    elif not isinstance(out, torch.Tensor) or out.shape != (M, C + 3) or out.dtype != torch.float32 or not out.is_contiguous() or \
+            out.device != dev:
+        raise ValueError("paint_points: out must be a contiguous float32 [%d, %d] tensor on %s" % (M, C + 3, dev))
+    if M > 0 and not (points.data_ptr() == out.data_ptr() and tuple(points.stride()) == (C + 3, 1)):
+        out[:, :C].copy_(points.detach())
+    if pix is None:
+        pix = torch.empty(M, 2, device=dev, dtype=torch.int32)
+    _project_pixels(out, M, C + 3, calib, pix)
+    _, valid = sample_image(pix, image, mode, normalize, channel_order, out[:, C:], valid, row_begin, row_count, max_rows, err)
+    return (out, valid) if return_valid else out
+
+
+def _project_pixels(rows, M, ld, calib, pix):
+    """The pixels alone (``pn2_project_points`` with a NULL ``pts_2d``) of the first three columns of contiguous rows."""
+    if pix.shape != (M, 2) or pix.dtype != torch.int32 or not pix.is_contiguous() or pix.device != rows.device:
+        raise ValueError("paint_points: pix must be a contiguous int32 [%d, 2] tensor on %s" % (M, rows.device))
+    if M > 0:
+        _check(_lib.load().pn2_project_points(_p(rows), ld, M, calib.RT.ctypes.data_as(ctypes.c_void_p),
+                                              calib.P.ctypes.data_as(ctypes.c_void_p), None, _p(pix), _lib.stream()),
+               "pn2_project_points")
+
+
+def hsv_to_rgb(colors, channel_order="rgb", out=None):
+    """uint8 ``[..., 3]`` pixels of normalised HSV rows float32 ``[..., 3]`` (h in units of 180, s and v in units of 255: what
+    ``sample_image(mode="hsv")`` writes and ``PointNetColorGen`` predicts) -- for LOOKING at a prediction, the step the reference
+    has commented out (ColorGenerator_Loader.py:66-67).  This package's own fp64 definition (include/pn2.h, ``pn2_hsv_to_rgb``:
+    s and v clamped to [0, 1], the hue wrapped, round-half-even), not OpenCV's float-based ``HSV2RGB`` bit for bit.  A NaN gives a
+    black pixel.  A column slice of wider rows is read in place.  ``out``: a contiguous uint8 tensor of as many elements."""
+    if not isinstance(colors, torch.Tensor) or not colors.is_cuda:
+        raise _lib.Pn2Error("hsv_to_rgb: colors must live on the GPU: this package has no CPU path")
+    if colors.dtype != torch.float32:
+        raise RuntimeError("hsv_to_rgb: colors must be float32 (got %s)" % colors.dtype)
+    if colors.dim() < 1 or colors.shape[-1] != 3:
+        raise AssertionError(tuple(colors.shape))
+    shape = tuple(colors.shape)
+    rows = colors.detach()
+    if rows.dim() != 2 or (rows.shape[0] > 0 and rows.stride(1) != 1) or (rows.shape[0] > 1 and not 3 <= rows.stride(0) < 2 ** 31):
+        rows = rows.reshape(-1, 3).contiguous()
+    N = int(rows.shape[0])
+    if out is None:
+        out = torch.empty(shape, device=rows.device, dtype=torch.uint8)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.numel() != 3 * N or not out.is_contiguous() or \
+            out.device != rows.device:
+        raise ValueError("hsv_to_rgb: out must be a contiguous uint8 tensor of %d elements on %s" % (3 * N, rows.device))
+    order = _code(_ORDERS, channel_order, "channel_order")
+    if N > 0:
+        _check(_lib.load().pn2_hsv_to_rgb(_p(rows), int(rows.stride(0)) if N > 1 else 3, N, order, _p(out), _lib.stream()),
+               "pn2_hsv_to_rgb")
+    return out
 
 
 # ----------------------------------------------------------------------------------------------------------------- ego view
@@ -558,10 +721,15 @@ class FrameSegmenter:
 
     ``camera`` (a ``PinholeCamera``): ``render`` then also draws the 3-D ego view of the un-normalised points (pcdvis.py:143,
     ``render_points`` with ``point_size`` on ``ego_background``, a colour triple) into ``ego_view`` uint8
-    ``[camera.height, camera.width, 3]``, and ``frame`` returns it under ``"ego_view"``.  Without a camera there is no such key, buffer or launch."""
+    ``[camera.height, camera.width, 3]``, and ``frame`` returns it under ``"ego_view"``.  Without a camera there is no such key, buffer or launch.
+
+    ``frame`` / ``frame_raw`` / ``label_scan(..., image=)``: the camera frame (uint8 ``[H, W, 3]``, bytes in ``channel_order``).  The
+    result then gains ``"point_colors"`` float32 ``[N, 3]`` and ``"point_valid"`` bool ``[N]``: the colour of the pixel under each DRAWN
+    row (``sample_image`` on ``pix`` with ``color_mode`` / ``color_normalize``), e.g. the colour-generation task's target for this
+    frame.  ``image=None`` leaves all three calls exactly as they are: no key, buffer or launch."""
 
     def __init__(self, model, calib, colors, npoints=25000, image_size=(375, 1242), groups=None, radius=2, device="cuda", camera=None,
-                 point_size=2, ego_background=(0, 0, 0)):
+                 point_size=2, ego_background=(0, 0, 0), color_mode="rgb", color_normalize=True, channel_order="rgb"):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.Pn2Error("FrameSegmenter: the HIP device is the only implementation")
@@ -588,6 +756,10 @@ class FrameSegmenter:
             self._ego_background = bg if bg == (0, 0, 0) else \
                 torch.tensor(bg, device=dev, dtype=torch.uint8).expand(camera.height, camera.width, 3).contiguous()
         self.error_flag = torch.zeros(1, device=dev, dtype=torch.int32)
+        _code(_MODES, color_mode, "color_mode")
+        _code(_ORDERS, channel_order, "channel_order")
+        self.color_mode, self.color_normalize, self.channel_order = color_mode, bool(color_normalize), channel_order
+        self.point_colors = self._point_valid = None                 # made by the first frame that comes with an image
 
     def choice(self, length, rng="numpy"):
         """``np.random.choice(length, npoints, replace=True)`` (pcdvis.py:121: a seeded numpy run draws what the reference
@@ -625,7 +797,7 @@ class FrameSegmenter:
             render_points(raw_rows, self.pred, self.colors, self.camera, self.point_size, self._ego_background, out=self.ego_view,
                           zkey=self._zkey, owner=self._owner[:self.camera.height * self.camera.width], err=self.error_flag)
 
-    def frame(self, points, background=None, choice=None, rng="numpy"):
+    def frame(self, points, background=None, choice=None, rng="numpy", image=None):
         lib = _lib.load()
         self.error_flag.zero_()                                      # per frame; an async fill, nothing is read back
         if isinstance(points, np.ndarray):
@@ -651,9 +823,9 @@ class FrameSegmenter:
         # the resampled raw rows (pcdvis.py:122, :125) through the library's row gather: [1, M, 4] -> [1, n, 4]
         _check(lib.pn2_gather_rows(_p(raw), _p(choice), 1, M, 4, n, _p(self.raw_rows), _p(self.error_flag), _lib.stream()),
                "pn2_gather_rows")
-        return self._finish(normed, background)
+        return self._finish(normed, background, image)
 
-    def _finish(self, normed, background):
+    def _finish(self, normed, background, image=None):
         """The network and the post-network stages on the normalised rows ``[1, n, 4]`` (``self.raw_rows`` holds the raw ones)."""
         was_training = self.model.training
         self.model.eval()
@@ -672,6 +844,15 @@ class FrameSegmenter:
                "pts_2d": self.pts_2d, "pix": self.pix, "image": self.image, "top_view": self.top_view}
         if self.camera is not None:
             out["ego_view"] = self.ego_view
+        if image is not None:
+            # the camera colour under every drawn row (sample_image on the pixels just projected): buffers made on first use
+            if self.point_colors is None:
+                self.point_colors = torch.empty(self.npoints, 3, device=self.device, dtype=torch.float32)
+                self._point_valid = torch.empty(self.npoints, device=self.device, dtype=torch.uint8)
+            image = _dev_u8(image, self.device, "image")
+            _, valid = sample_image(self.pix, image, self.color_mode, self.color_normalize, self.channel_order, self.point_colors,
+                                    self._point_valid)
+            out["point_colors"], out["point_valid"] = self.point_colors, valid
         return out
 
     def _raw_buffers(self, scan_filter, rows):
@@ -687,7 +868,7 @@ class FrameSegmenter:
         return held
 
     def frame_raw(self, raw_scan, raw_label=None, scan_filter=None, rng="numpy", background=None, choice=None, max_rows=None,
-                  voxel=None):
+                  voxel=None, image=None):
         """``frame`` for a RAW scan: ``raw_scan`` float32 ``[M, 4]`` (the ``.bin`` rows) and, if there is one, ``raw_label`` ``[M]``
         (the ``.label`` words, uint32 / int32; None: a live feed), as numpy arrays or tensors on either side.  ``scan_filter``: a
         ``kitti.ScanFilter`` (its class map, subset and ranges).  The stages are: upload into a static buffer of ``max_rows`` rows
@@ -764,7 +945,7 @@ class FrameSegmenter:
                                       _p(self.error_flag), _lib.stream()), "pn2_prepare_clouds")
         _check(lib.pn2_gather_rows(_p(src), _p(choice), 1, held["rows"], 4, n, _p(self.raw_rows), _p(self.error_flag), _lib.stream()),
                "pn2_gather_rows")
-        out = self._finish(normed, background)
+        out = self._finish(normed, background, image)
         out.update({"count": count, "labels": labels, "index": index})
         if voxel is not None:
             # (entries beyond the voxel count are whatever the buffer held: clamped, so that the gather stays inside `index`)
@@ -773,7 +954,7 @@ class FrameSegmenter:
         return out
 
     def label_scan(self, raw_scan, raw_label=None, scan_filter=None, rng="numpy", k=5, max_dist=1.0, lut=None, background=None,
-                   choice=None, max_rows=None, voxel=None, instances=None):
+                   choice=None, max_rows=None, voxel=None, instances=None, image=None):
         """``frame_raw``, then a label for EVERY row of the raw scan.  The network labels ``npoints`` rows drawn with
         replacement (about ``exp(-npoints / count)`` of the kept rows are never drawn); here each kept row takes the majority
         label of its ``k`` nearest drawn rows (``pointnet_util.propagate_labels``: queries = the kept rows' xyz with the
@@ -800,7 +981,7 @@ class FrameSegmenter:
         each instance's lowest kept row.  With a device generator nothing is read back.  ``kitti.write_labels(fn, scan_labels,
         scan_instances)`` writes both halves of the ``.label`` words.  ``instances=None`` leaves this call exactly as it was."""
         from . import pointnet_util as U
-        out = self.frame_raw(raw_scan, raw_label, scan_filter, rng, background, choice, max_rows, voxel)
+        out = self.frame_raw(raw_scan, raw_label, scan_filter, rng, background, choice, max_rows, voxel, image)
         held = self._raw_state
         rows, n, M = held["rows"], self.npoints, int(raw_scan.shape[0])
         k = int(k)

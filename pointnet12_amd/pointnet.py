@@ -386,6 +386,20 @@ class PointNetSeg(nn.Module):
         return log_softmax_rows(logits, self.k).view(B, N, self.k), trans_feat
 
 
+class PointNetColorGen(PointNetSeg):
+    """data_utils/ColorGenerator_Loader.py:1-24 PointNetColorGen (the colour-generation task: a colour per point): ``PointNetSeg``
+    without the log-softmax, returns ``(x [B, N, k], trans_feat)``.  Its ``state_dict`` keys are ``PointNetSeg``'s, so
+    ``pointnet2.load_reference_state`` loads a reference checkpoint.  The ``k`` columns are a slice of the padded rows the last GEMM
+    wrote (pitch ``round4(k)``): no copy is made, and the tensor is not contiguous unless ``k`` is a multiple of 4."""
+
+    def forward(self, x):
+        B, _, N = x.shape
+        g, pointfeat, trans, trans_feat = self.feat.features(x)
+        h = global_concat_conv(pointfeat, g, self.conv1, self.bn1, N, self.training)
+        h = shared_mlp(h, 512, [self.conv2, self.conv3], [self.bn2, self.bn3], 0, self.training)
+        return conv1x1(h, self.conv4, padded=True)[:, :self.k].view(B, N, self.k), trans_feat
+
+
 class _DenseSegHead(torch.autograd.Function):
     """PointNetDenseCls from out4 on: conv5 + bn5 (no ReLU) + max over the cloud -> out_max, and
     relu(bns1(convs1(cat([cat([out_max, label]).repeat(N), out1, out2, out3, out4, out5])))) as rows.

@@ -55,3 +55,22 @@ def uniform_batch(seed, batch, n_points, channels=9):
     pts = rng.uniform(-1.0, 1.0, size=(batch, channels, n_points)).astype(np.float32)
     labels = rng.integers(0, 13, size=(batch, n_points)).astype(np.int64)
     return pts, labels
+
+
+def kitti_scan(seed, n_points):
+    """``kitti_cloud`` un-normalised back to metres: float32 [n_points, 4] (x, y, z, intensity), the .bin row format."""
+    n = kitti_cloud(seed, n_points, n_points, 1)[:, :4]
+    return np.stack([n[:, 0] * 70, n[:, 1] * 70, n[:, 2] * 3, n[:, 3] / 2 + 0.5], 1).astype(np.float32)
+
+
+def camera_image(seed, height=375, width=1242):
+    """A camera frame for the colour lookup: uint8 [height, width, 3] (R, G, B), a sky-to-road gradient with coloured blocks and
+    a little noise, so that a point's colour says where it landed."""
+    rng = np.random.default_rng(seed)
+    y, x = np.mgrid[0:height, 0:width]
+    v, u = y / max(height - 1, 1), x / max(width - 1, 1)
+    img = np.stack([60 + 150 * v, 110 + 60 * np.sin(6.0 * u), 230 - 170 * v], -1)
+    for _ in range(12):                                              # "cars" and "signs"
+        h0, w0 = int(rng.integers(0, height)), int(rng.integers(0, width))
+        img[h0:h0 + int(rng.integers(8, 60)), w0:w0 + int(rng.integers(8, 120))] = rng.integers(0, 256, 3)
+    return np.clip(img + rng.normal(0.0, 4.0, img.shape), 0, 255).astype(np.uint8)

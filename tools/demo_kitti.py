@@ -2,7 +2,7 @@
 """One frame of the reference's KITTI demo (``python pcdvis.py``) on the HIP library: scan -> labels -> pixels -> two images,
 three with ``--ego``.
 
-    python tools/demo_kitti.py [--out DIR] [--npoints 25000] [--seed 0] [--merge] [--time] [--raw [--labels-out FILE [--instances SIZE]]] [--ego CAMERA.json [--render-option FILE.json]]
+    python tools/demo_kitti.py [--out DIR] [--npoints 25000] [--seed 0] [--merge] [--time] [--raw [--labels-out FILE [--instances SIZE]]] [--ego CAMERA.json [--render-option FILE.json]] [--image FILE]
     python tools/demo_kitti.py --root $KITTI_ROOT --part 01 --index 0 --calib DIR --config semantic-kitti.yaml [--checkpoint CKPT]
 
 Without ``--root`` the scan is synthetic (``synthetic.kitti_cloud``, un-normalised back to metres), the calibration is the one
@@ -15,6 +15,12 @@ written as PNG through PIL (``semantic.png``: the camera view, ``top_view.png``)
 ``--ego CAMERA.json`` (an open3d ``PinholeCameraParameters`` file, the reference's ``config/ego_view.json``) adds the demo's 3-D ego
 view (``Window_Manager.update``, pcdvis.py:31-51) as ``ego_view.png``; ``--render-option FILE.json`` (an open3d ``RenderOption``
 file, the reference's ``config/render_option.json``) sets its point size and background colour (defaults: 2, black).  The picture follows the rule stated in include/pn2.h, which is unverified against open3d.
+
+``--image FILE`` (any picture PIL reads; ``synthetic``: ``synthetic.camera_image``) is the camera frame for the image -> points
+direction: every drawn row takes the colour of the pixel under it (``FrameSegmenter.frame(image=)``, ``pn2_sample_image``; no depth
+test, as in the reference) and ``painted.png`` shows those rows drawn with THEIR OWN camera colour on black
+(``draw_2d_points(labels=None, colors=[N, 3])``): the coloured cloud as the camera sees it.  With ``--root`` the frame read from the
+dataset stays the background of ``semantic.png``; FILE must have its size.
 
 ``--raw`` feeds the RAW scan through ``FrameSegmenter.frame_raw``: the class map, the class drop, the view filter and the
 compaction run on the device (``kitti.ScanFilter``, ``pn2_scan_filter``) and the kept count never leaves it; the synthetic scan has
@@ -215,6 +221,7 @@ def main():
                     help="with --voxel: a cell's label is its first row's or the majority of its rows'")
     ap.add_argument("--ego", metavar="CAMERA.json", help="also draw the 3-D ego view through this open3d PinholeCameraParameters file")
     ap.add_argument("--render-option", metavar="FILE.json", help="open3d RenderOption file: the ego view's point size and background colour")
+    ap.add_argument("--image", metavar="FILE", help="camera frame to colour the drawn rows from ('synthetic': a generated one); writes painted.png")
     ap.add_argument("--root")
     ap.add_argument("--part", default="01")
     ap.add_argument("--index", type=int, default=0)
@@ -240,6 +247,15 @@ def main():
     model = model.cuda().eval()
     groups = V.merge_groups(names, MERGE, colors) if args.merge else None
     size = (375, 1242) if frame is None else frame.shape[:2]
+    camera_image = None
+    if args.image:
+        camera_image = syn.camera_image(args.seed, *size) if args.image == "synthetic" else \
+            np.ascontiguousarray(np.asarray(Image.open(args.image).convert("RGB")))
+        if frame is None:
+            size = camera_image.shape[:2]
+        elif camera_image.shape[:2] != tuple(size):
+            ap.error("--image must have the dataset frame's size, %d x %d" % tuple(size))
+        camera_image = torch.from_numpy(camera_image).cuda()
     if args.render_option and not args.ego:
         ap.error("--render-option needs --ego")
     if args.labels_out and (not args.raw or args.merge):
@@ -253,7 +269,8 @@ def main():
     camera = V.PinholeCamera.from_json(args.ego) if args.ego else None
     option = V.RenderOption.from_json(args.render_option) if args.render_option else V.RenderOption()
     seg = V.FrameSegmenter(model, calib, colors if groups is None else groups.colors, npoints=args.npoints, image_size=size, groups=groups,
-                           camera=camera, point_size=option.point_size, ego_background=option.background_color)
+                           camera=camera, point_size=option.point_size, ego_background=option.background_color, color_mode="rgb",
+                           color_normalize=False)
     if args.raw:
         from pointnet12_amd import kitti
         scan_filter = kitti.ScanFilter(cfg["learning_map"] if words is not None else None, "inview")
@@ -265,7 +282,7 @@ def main():
             grid = voxel.VoxelGrid(args.voxel, reduce=args.voxel_reduce, label_reduce=args.voxel_labels)
         if args.labels_out:
             out = seg.label_scan(scan, words, scan_filter=scan_filter, rng=gen, lut=kitti.inverse_label_lut(cfg["learning_map_inv"]),
-                                 background=frame, voxel=grid,
+                                 background=frame, voxel=grid, image=camera_image,
                                  instances=None if args.instances is None else V.InstanceSpec(args.instances, range(8)))
             kitti.write_labels(args.labels_out, out["scan_labels"], out.get("scan_instances"))
             print("labelled %d of %d rows; wrote %s" % (int((out["scan_labels"] != 0).sum()), len(scan), args.labels_out))
@@ -273,13 +290,13 @@ def main():
                 print("%d instances of the thing classes on %d rows (cells of %g m)"
                       % (int(out["instance_count"].item()), int((out["scan_instances"] != 0).sum()), args.instances))
         else:
-            out = seg.frame_raw(scan, words, scan_filter=scan_filter, rng=gen, background=frame, voxel=grid)
+            out = seg.frame_raw(scan, words, scan_filter=scan_filter, rng=gen, background=frame, voxel=grid, image=camera_image)
         print("raw scan of %d rows, %d kept by the device filter; filter error flag %d"
               % (len(scan), int(out["count"].item()), int(scan_filter.error_flag.item())))
         if grid is not None:
             print("%d voxels of %g m; grid error flag %d" % (int(out["voxel_count"].item()), args.voxel, int(grid.error_flag.item())))
     else:
-        out = seg.frame(scan, background=frame)
+        out = seg.frame(scan, background=frame, image=camera_image)
     os.makedirs(args.out, exist_ok=True)
     Image.fromarray(out["image"].cpu().numpy()).save(os.path.join(args.out, "semantic.png"))
     Image.fromarray(out["top_view"].cpu().numpy()).save(os.path.join(args.out, "top_view.png"))
@@ -287,6 +304,12 @@ def main():
         Image.fromarray(out["ego_view"].cpu().numpy()).save(os.path.join(args.out, "ego_view.png"))
         print("ego view %d x %d, point size %d, background %s; wrote %s/ego_view.png"
               % (camera.height, camera.width, option.point_size, option.background_color, args.out))
+    if camera_image is not None:
+        valid = out["point_valid"]
+        pix = torch.where(valid[:, None], out["pix"], torch.full_like(out["pix"], V.INT32_MIN))      # rows outside the frame are not drawn
+        painted = V.draw_2d_points(pix, None, out["point_colors"].to(torch.uint8), None, size)
+        Image.fromarray(painted.cpu().numpy()).save(os.path.join(args.out, "painted.png"))
+        print("%d of %d drawn rows inside the camera frame; wrote %s/painted.png" % (int(valid.sum()), args.npoints, args.out))
     counts = torch.bincount(out["pred"], minlength=len(colors)).cpu().tolist()
     drawn = int((out["pix"][:, 0] != V.INT32_MIN).sum())
     print("scan of %d points resampled to %d; %d with a pixel, %d classes predicted; error flag %d; wrote %s/semantic.png and top_view.png"
