@@ -5,7 +5,13 @@
 //
 // Activations are position-major: row p = one grouped position, channels contiguous.
 // Replaces model/pointnet_util.py:194-199, :251-256, :309-312 and their autograd.
-#include "mlp_loaders.h"
+#include "mlp_host.h"
+
+struct PairJob {            // see "dgrad + wgrad of one layer in ONE launch" below
+    bool active, taken;
+    const float *X; int ldx; const float *x_aff;
+    float *dW; int lddw; int M, N;
+};
 
 namespace {
 
@@ -190,8 +196,7 @@ struct BMat { const float *p; int ld; int K; int vec; const float *zp; };
 // (ld >= round4(len)): the caller then guarantees ZERO pad entries (include/pn2.h) -- the host side makes such a padded copy of
 // the 137- / 323- / 515-column weights once per step (pointnet_util._aligned_weight).
 inline BMat make_bmat(const float *p, int ld, int K, int contiguous_len) {
-    const bool vec = (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(p) & 15) == 0 &&
-                     ((contiguous_len & 3) == 0 || ld >= ((contiguous_len + 3) & ~3));
+    const bool vec = (ld & 3) == 0 && aligned16(p) && ((contiguous_len & 3) == 0 || ld >= round4(contiguous_len));
     return BMat{p, ld, K, vec ? 1 : 0, zero_page_dev()};
 }
 
@@ -520,18 +525,10 @@ __global__ __launch_bounds__(NTHREADS, MINB) void gemm_nt_kernel(ALoad aload, BM
 // the first blocks of a one-dimensional grid run the NT body (dX), the rest the TN body (dW) -- no fork, no join, one launch
 // less on the chain, and the chip is filled by both.  pn2_conv1x1_bwd_pair posts the weight-gradient half as a pending job;
 // the dgrad dispatch picks it up in the one leaf that has a pair instantiation (64 x 128 x 16 tiles) and reports back.
-struct PairJob {
-    bool active, taken;
-    const float *X; int ldx; const float *x_aff;
-    float *dW; int lddw; int M, N;
-};
 // (passed down the dispatch explicitly: round 4 posted it in thread-local storage, hidden state behind a C ABI that promises none)
 
 template <int BM, int BN, int BK, int WR, int WC, bool VEC, class ALoad, class Epi>
 bool launch_bwd_pair(const PairJob &j, ALoad aload, BMat bm, int64_t P, int K4, int N, Epi epi, hipStream_t s, unsigned nt_gx, unsigned nt_gy, int *rc);
-
-template <class A, class B> struct pn2_same { static constexpr bool v = false; };
-template <class A> struct pn2_same<A, A> { static constexpr bool v = true; };
 
 template <int BM, int BN, int BK, int WR, int WC, int MINB, int DEPTH, bool BNN, bool VEC, int ACCS = 1, bool ROT = false, class ALoad, class Epi>
 int launch_nt(ALoad aload, BMat bm, int64_t P, int K4, int N, Epi epi, hipStream_t s, int n_lo = 0, int n_hi = 0, PairJob *job = nullptr) {
@@ -541,8 +538,8 @@ int launch_nt(ALoad aload, BMat bm, int64_t P, int K4, int N, Epi epi, hipStream
     if (cap < 1) cap = 1;
     unsigned gx = (unsigned)(tiles_m < cap ? tiles_m : cap);
     if constexpr (BNN && VEC && BM == 64 && BN == 128 && BK == 16 && WR == 2 && WC == 2 && DEPTH == 1 && ACCS == 1 && !ROT &&
-                  (pn2_same<ALoad, LoadDyDense>::v || pn2_same<ALoad, LoadDyPooled>::v) &&
-                  (pn2_same<Epi, EpiDgradMask>::v || pn2_same<Epi, EpiStore>::v)) {
+                  (same<ALoad, LoadDyDense>::v || same<ALoad, LoadDyPooled>::v) &&
+                  (same<Epi, EpiDgradMask>::v || same<Epi, EpiStore>::v)) {
         if (job != nullptr && job->active && !job->taken && n_lo == 0 && n_hi == 0) {
             int rc = PN2_OK;
             // both halves must be RESIDENT together (two workgroups of 70 KB fit a CU): one per CU for each body -- with the
@@ -580,9 +577,6 @@ int launch_nt(ALoad aload, BMat bm, int64_t P, int K4, int N, Epi epi, hipStream
 //    (every few-row layer of the four networks except the 515- and 137-column ones, which stay on the core above);
 //  * the four partial tiles are summed in LDS in a fixed order (deterministic) and leave through the same epilogue
 //    functors as the core (bias / ReLU mask, per-channel reductions).
-template <class T, class U> struct fr_same { static constexpr bool v = false; };
-template <class T> struct fr_same<T, T> { static constexpr bool v = true; };
-
 // KS: waves sharing one 32 x 64 tile (they split K); a workgroup owns 4 / KS consecutive tiles of the (row tile, column tile) grid,
 // column tiles fastest -- its waves then read the same activation rows.  The host picks KS so that about four waves per CU
 // have 4+ stages each.
@@ -590,8 +584,8 @@ template <class T> struct fr_same<T, T> { static constexpr bool v = true; };
 // data gradient that it does not need when left alone -- the instantiations use 116 .. 246 registers, so two still fit)
 template <int KS, bool BNN, class ALoad, class Epi>
 __global__ __launch_bounds__(NTHREADS, 1) void fewrow_nt_kernel(ALoad aload, BMat bm, int K4, int N, Epi epi) {
-    constexpr bool kPlain = fr_same<ALoad, LoadPlain>::v, kBn = fr_same<ALoad, LoadBnRelu>::v;
-    constexpr bool kDense = fr_same<ALoad, LoadDyDense>::v, kPooled = fr_same<ALoad, LoadDyPooled>::v;
+    constexpr bool kPlain = same<ALoad, LoadPlain>::v, kBn = same<ALoad, LoadBnRelu>::v;
+    constexpr bool kDense = same<ALoad, LoadDyDense>::v, kPooled = same<ALoad, LoadDyPooled>::v;
     static_assert(kPlain || kBn || kDense || kPooled, "unknown operand loader");
     static_assert(KS == 1 || KS == 2 || KS == 4, "waves per tile");
     constexpr int kTabRows = kPlain ? 0 : kBn ? 3 : 4;
@@ -806,7 +800,7 @@ bool launch_fewrow(ALoad aload, BMat bm, int64_t P, int K4, int N, Epi epi, hipS
     if (!bm.vec || (P & 31) || (N & 63) || (K4 & 31) || bm.K != K4 || K4 < 128) return false;
     const int64_t tiles = (P / 32) * (N / 64);
     if (tiles > max_tiles || (tiles & 3)) return false;
-    constexpr int tab_rows = fr_same<ALoad, LoadPlain>::v ? 0 : fr_same<ALoad, LoadBnRelu>::v ? 3 : 4;
+    constexpr int tab_rows = same<ALoad, LoadPlain>::v ? 0 : same<ALoad, LoadBnRelu>::v ? 3 : 4;
     const size_t dyn = (size_t)tab_rows * K4 * sizeof(float);
     if (dyn + 4 * 32 * 72 * sizeof(float) > 64 * 1024) return false;
     // about four waves per CU with as many stages each as that allows
@@ -1165,8 +1159,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_skinny_kernel(const float *__res
 }
 
 template <int NQ>
-int launch_skinny(const float *dZ, int ldz, const float *Y, int ldy, const float *coef, int ldc, const float *X, int ldx,
-                  int64_t P, int M, int N, float *dW, int lddw, float *dbias, hipStream_t s, LazyCoef lc) {
+int launch_skinny(const UpGrad &up, int ldc, const float *X, int ldx, int64_t P, int M, int N, float *dW, int lddw, float *dbias, hipStream_t s) {
     int cg_log2 = 3;                                          // 8 column groups = 32 channels at least
     while ((4 << cg_log2) < M && cg_log2 < 6) ++cg_log2;      // up to 64 groups = 256 channels per grid.y slab
     const int CG = 1 << cg_log2, RS = 256 >> cg_log2;
@@ -1176,8 +1169,8 @@ int launch_skinny(const float *dZ, int ldz, const float *Y, int ldy, const float
     if (gx > cap) gx = cap;
     if (gx < 1) gx = 1;
     PN2_NOTE_KERNEL(wgrad_skinny_kernel<NQ>);
-    hipLaunchKernelGGL((wgrad_skinny_kernel<NQ>), dim3((unsigned)gx, gy), dim3(256), 0, s, dZ, ldz, Y, ldy, coef, ldc, X, ldx, P, M, N,
-                       cg_log2, dW, lddw, dbias, lc);
+    hipLaunchKernelGGL((wgrad_skinny_kernel<NQ>), dim3((unsigned)gx, gy), dim3(256), 0, s, up.dZ, up.ldz, up.Y, up.ldy, up.coef, ldc, X, ldx,
+                       P, M, N, cg_log2, dW, lddw, dbias, up.lc);
     return pn2_launch_status();
 }
 
@@ -1217,7 +1210,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void bwd_pair_kernel(ALoad aload, BMat
 
 template <int BM, int BN, int BK, int WR, int WC, bool VEC, class ALoad, class Epi>
 bool launch_bwd_pair(const PairJob &j, ALoad aload, BMat bm, int64_t P, int K4, int N, Epi epi, hipStream_t s, unsigned nt_gx, unsigned nt_gy, int *rc) {
-    constexpr bool masked = pn2_same<Epi, EpiDgradMask>::v;
+    constexpr bool masked = same<Epi, EpiDgradMask>::v;
     if (masked != (j.x_aff != nullptr)) return false;      // the weight gradient's X loader follows the data gradient's epilogue
     // the split over P of launch_tn<64, 64, 32, 2, 2, 2, 1, 2, 4> (the few-row weight-gradient configuration)
     constexpr int WG_BP = 32;
@@ -1233,17 +1226,13 @@ bool launch_bwd_pair(const PairJob &j, ALoad aload, BMat bm, int64_t P, int K4, 
     split = pn2_cdiv(P, chunk);
     const unsigned total = nt_gx * nt_gy + tm * tn * (unsigned)split;
     const size_t dyn = (size_t)ALoad::kTab * K4 * sizeof(float);
-    if constexpr (masked) {
-        const LoadBnReluFixed xl{j.X, j.ldx, j.x_aff, zero_page_dev()};
-        PN2_NOTE_KERNEL(bwd_pair_kernel<BM, BN, BK, WR, WC, VEC, ALoad, Epi, LoadBnReluFixed>);
-        hipLaunchKernelGGL((bwd_pair_kernel<BM, BN, BK, WR, WC, VEC, ALoad, Epi, LoadBnReluFixed>), dim3(total), dim3(NTHREADS), dyn, s, aload, bm, P,
+    const auto launch = [&](auto xl) {
+        PN2_NOTE_KERNEL(bwd_pair_kernel<BM, BN, BK, WR, WC, VEC, ALoad, Epi, decltype(xl)>);
+        hipLaunchKernelGGL((bwd_pair_kernel<BM, BN, BK, WR, WC, VEC, ALoad, Epi, decltype(xl)>), dim3(total), dim3(NTHREADS), dyn, s, aload, bm, P,
                            K4, N, epi, (int)nt_gx, (int)nt_gy, xl, chunk, j.M, j.N, j.dW, j.lddw, (int)tm, (int)tn, (int)split);
-    } else {
-        const LoadPlain xl{j.X, j.ldx, zero_page_dev()};
-        PN2_NOTE_KERNEL(bwd_pair_kernel<BM, BN, BK, WR, WC, VEC, ALoad, Epi, LoadPlain>);
-        hipLaunchKernelGGL((bwd_pair_kernel<BM, BN, BK, WR, WC, VEC, ALoad, Epi, LoadPlain>), dim3(total), dim3(NTHREADS), dyn, s, aload, bm, P, K4,
-                           N, epi, (int)nt_gx, (int)nt_gy, xl, chunk, j.M, j.N, j.dW, j.lddw, (int)tm, (int)tn, (int)split);
-    }
+    };
+    if constexpr (masked) launch(LoadBnReluFixed{j.X, j.ldx, j.x_aff, zero_page_dev()});
+    else launch(LoadPlain{j.X, j.ldx, zero_page_dev()});
     *rc = pn2_launch_status();
     return true;
 }
@@ -1612,8 +1601,6 @@ __global__ void bn_bwd_coef_kernel(const double *__restrict__ red, double inv_p,
     bn_coef_channel(r0, r1, c, ld, inv_p, gamma, aff, use_batch, coef, dgamma, dbeta, accumulate);
 }
 
-inline int round4(int x) { return (x + 3) & ~3; }
-
 }  // namespace
 
 #ifdef PN2_STAMP
@@ -1622,20 +1609,6 @@ extern "C" int pn2_debug_stamps(unsigned long long *host_out, int n) {
     return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(pn2_stamp_buf), sizeof(unsigned long long) * (size_t)n) == hipSuccess ? 0 : -2;
 }
 #endif
-
-int pn2_fwd_res(const float *X, int ldx, const float *in_affine, const float *W, int ldw, const float *bias, float *Y, int ldy,
-                int64_t P, int K, int N, double *stats, LazyBn lz, hipStream_t s);      // mlp_res.hip
-// mlp_wide.hip: register-stationary kernels for the wide layers; *rows_done = the leading rows they covered (whole tiles)
-int pn2_wide_fwd(const float *X, int ldx, const float *in_affine, const float *W, int ldw, const float *bias, float *Y, int ldy,
-                 int64_t P, int K, int N, double *stats, LazyBn lz, hipStream_t s, int64_t *rows_done, int Kpool = 0,
-                 const float *pool_gamma = nullptr, float *pool_ws = nullptr);
-int pn2_wide_dgrad(const float *dZ, int ldz, const float *dZp, int ldo, const int32_t *arg, int Kpool, const float *Y, int ldy,
-                   const float *coef, const float *W, int ldw, const float *prev_Y, int ld_prev, const float *prev_affine,
-                   float *dXout, int ldxo, double *prev_red, int64_t P, int K, int N, LazyCoef lc, hipStream_t s, int64_t *rows_done);
-int pn2_wide_wgrad(const float *dZ, int ldz, const float *dZp, int ldo, const int32_t *arg, int Kpool, const float *Y, int ldy,
-                   const float *coef, const float *X, int ldx, const float *x_affine, float *dW, int lddw, float *dbias,
-                   int64_t P, int M, int N, LazyCoef lc, hipStream_t s, float *workspace = nullptr);
-int64_t pn2_wide_wgrad_workspace_bytes(int64_t P, int M, int N, int pooled);
 
 namespace {
 
@@ -1799,6 +1772,56 @@ int dispatch_multi_nt(const LoadMulti<UNI> &ld, BMat bm, int64_t P, int K4, int 
 
 }  // namespace
 
+// `job`: the weight-gradient half pn2_conv1x1_bwd_pair wants to ride in this launch (null for the plain entry point)
+int pn2_dgrad_up(UpGrad up, const float *W, int ldw, const float *prev_Y, int ld_prev, const float *prev_affine, float *dXout, int ldxo,
+                 double *prev_red, int64_t P, int K, int N, hipStream_t s, PairJob *job) {
+    PN2_CHECK_ARG(W && dXout && P > 0 && P < (1LL << 31) && K > 0 && N > 0 && ldw >= N && ldxo % 4 == 0 && ldxo >= round4(N));
+    // (the dZ pitch is checked below, for the rows the wide kernels leave: they take any)
+    PN2_CHECK_ARG(up.valid(K, false) && (prev_Y == nullptr || prev_affine != nullptr));
+    const BMat bm = make_bmat(W, ldw, K, N);
+    const int K4 = round4(K);
+    if (prev_Y != nullptr) {                                            // wide layer: W stays in registers (mlp_wide.hip)
+        int64_t done = 0;
+        const int rc = pn2_wide_dgrad(up, W, ldw, prev_Y, ld_prev, prev_affine, dXout, ldxo, prev_red, P, K, N, s, &done);
+        if (rc != PN2_EUNSUPPORTED) {
+            if (rc != PN2_OK || done == P) return rc;
+            up = up.advanced(done);                                     // ragged tail
+            prev_Y += done * ld_prev; dXout += done * ldxo; P -= done;
+        }
+    }
+    PN2_CHECK_ARG(up.valid(K));
+    return with_dy(up, K4, [&](auto dy) {
+        if (prev_Y)
+            return dispatch_nt<true>(dy, bm, P, K4, N,
+                                     EpiDgradMask{dXout, ldxo, prev_Y, ld_prev, prev_affine, round4(N), prev_red, zero_page_dev()}, s, job);
+        return dispatch_nt<true>(dy, bm, P, K4, N, EpiStore{dXout, ldxo}, s, job);
+    });
+}
+
+int pn2_wgrad_up(const UpGrad &up, const float *X, int ldx, const float *x_affine, float *dW, int lddw, float *dbias, int64_t P, int M,
+                 int N, float *workspace, hipStream_t s) {
+    PN2_CHECK_ARG(X && dW && P > 0 && P < (1LL << 31) && M > 0 && N > 0 && up.valid(M) && ldx % 4 == 0 && ldx >= round4(N) && lddw >= N);
+    const int ldc = round4(M);
+    {                                                                   // wide layer: all of dW resident in one workgroup (mlp_wide.hip)
+        // (the workspace is used only if it is as large as the query said it must be: the caller passes what it was told)
+        const int rc = pn2_wide_wgrad(up, X, ldx, x_affine, dW, lddw, dbias, P, M, N, s,
+                                      pn2_wide_wgrad_workspace_bytes(P, M, N, !up.dense()) > 0 ? workspace : nullptr);
+        if (rc != PN2_EUNSUPPORTED) return rc;
+    }
+    if (up.dense() && pn2_opt(PN2_OPT_WGRAD_SKINNY) && x_affine == nullptr && N <= 16 && P >= 4096) {   // first layers: stream dZ / Y once, no MFMA
+        switch ((N + 3) / 4) {
+            case 1: return launch_skinny<1>(up, ldc, X, ldx, P, M, N, dW, lddw, dbias, s);
+            case 2: return launch_skinny<2>(up, ldc, X, ldx, P, M, N, dW, lddw, dbias, s);
+            case 3: return launch_skinny<3>(up, ldc, X, ldx, P, M, N, dW, lddw, dbias, s);
+            default: return launch_skinny<4>(up, ldc, X, ldx, P, M, N, dW, lddw, dbias, s);
+        }
+    }
+    return with_dy(up, ldc, [&](auto dy) {
+        if (x_affine) return dispatch_tn(dy, LoadBnReluFixed{X, ldx, x_affine, zero_page_dev()}, P, M, N, dW, lddw, dbias, s);
+        return dispatch_tn(dy, LoadPlain{X, ldx, zero_page_dev()}, P, M, N, dW, lddw, dbias, s);
+    });
+}
+
 extern "C" {
 
 int pn2_conv1x1_fwd_multi(const pn2_src *src, int nsrc, const float *W, int ldw, const float *bias, const float *gbias, int ldg,
@@ -1808,7 +1831,7 @@ int pn2_conv1x1_fwd_multi(const pn2_src *src, int nsrc, const float *W, int ldw,
     PN2_CHECK_ARG(make_multi(src, nsrc, lv, &K, &align));
     PN2_CHECK_ARG(W && bias && Y && P > 0 && P < (1LL << 31) && N > 0 && ldw >= K && ldy % 4 == 0 && ldy >= round4(N));
     PN2_CHECK_ARG(gbias == nullptr || (rows_per_group > 0 && P % rows_per_group == 0 && ldg % 4 == 0 && ldg >= round4(N) &&
-                                       (reinterpret_cast<uintptr_t>(gbias) & 15) == 0));
+                                       aligned16(gbias)));
     const int rpg = gbias ? (int)rows_per_group : 1;                  // <= P < 2^31
     const EpiFwdG epi{Y, ldy, bias, gbias, ldg, rpg, pow2_shift(rpg), stats, zero_page_dev()};
     const BMat bm = make_bmat(W, ldw, K, K);
@@ -1886,7 +1909,7 @@ int pn2_bn_finalize(const double *stats, int64_t P, int C, const float *gamma, c
 int pn2_bn_relu_max(const float *Y, int ldy, const float *affine, int64_t G, int K, int C, float *out, int ldo,
                     int32_t *arg, const pn2_bn_lazy *lazy, pn2_stream_t stream) {
     PN2_CHECK_ARG(Y && affine && out && G > 0 && K > 0 && C > 0 && lazy_bn_ok(lazy, affine, C));
-    const int ld = (C + 3) & ~3;
+    const int ld = round4(C);
     PN2_CHECK_ARG(ldy % 4 == 0 && ldo % 4 == 0 && ldy >= ld && ldo >= ld);      // float4 rows; pad columns are written (0)
     const LazyBn lz = make_lazy_bn(lazy);
     const int cg = ld / 4;
@@ -1917,11 +1940,11 @@ int pn2_bn_relu_max(const float *Y, int ldy, const float *affine, int64_t G, int
 
 int pn2_pool_bwd_reduce_ld(const float *dOut, int ld_dout, const float *out, int ldo, const int32_t *arg, const float *Y, int ldy,
                            const float *affine, int64_t G, int K, int C, float *dZp, double *red, pn2_stream_t stream) {
-    PN2_CHECK_ARG(dOut && out && arg && Y && affine && dZp && red && G > 0 && K > 0 && C > 0 && ldo >= ((C + 3) & ~3) && ld_dout >= C);
+    PN2_CHECK_ARG(dOut && out && arg && Y && affine && dZp && red && G > 0 && K > 0 && C > 0 && ldo >= round4(C) && ld_dout >= C);
     int64_t gy = pn2_cdiv(G, 4 * 4);                    // one trip of four groups per thread where the grid allows
     if (gy > 1024) gy = 1024;                           // (x 8 reduction replicas: same-address queues of <= 128)
-    hipLaunchKernelGGL(pool_bwd_reduce_kernel, dim3((unsigned)pn2_cdiv((C + 3) & ~3, 64), (unsigned)gy), dim3(256), 0, pn2_s(stream), dOut,
-                       ld_dout, ldo, out, arg, Y, ldy, affine, (C + 3) & ~3, G, K, C, dZp, red);
+    hipLaunchKernelGGL(pool_bwd_reduce_kernel, dim3((unsigned)pn2_cdiv(round4(C), 64), (unsigned)gy), dim3(256), 0, pn2_s(stream), dOut,
+                       ld_dout, ldo, out, arg, Y, ldy, affine, round4(C), G, K, C, dZp, red);
     return pn2_launch_status();
 }
 
@@ -1929,11 +1952,11 @@ int pn2_pool_bwd_reduce_rec(const float *dOut, int ld_dout, const float *out, in
                             const float *affine, int64_t G, int K, int C, float *dZp, double *red, const float *W, int ldw, const float *bias,
                             const float *prev_Y, int ld_prev, const float *prev_affine, int C_in, pn2_stream_t stream) {
     PN2_CHECK_ARG(dOut && out && arg && pool_ws && affine && dZp && red && W && bias && prev_Y && prev_affine && G > 0 && K > 0 && C > 0 &&
-                  C_in > 0 && ldo >= ((C + 3) & ~3) && ld_dout >= C && ldw >= C_in && ld_prev >= C_in);
+                  C_in > 0 && ldo >= round4(C) && ld_dout >= C && ldw >= C_in && ld_prev >= C_in);
     int64_t gy = pn2_cdiv(G, 4 * 4);
     if (gy > 1024) gy = 1024;
-    hipLaunchKernelGGL(pool_bwd_reduce_rec_kernel, dim3((unsigned)pn2_cdiv((C + 3) & ~3, 64), (unsigned)gy), dim3(256), 0, pn2_s(stream), dOut,
-                       ld_dout, ldo, out, arg, reinterpret_cast<const float2 *>(pool_ws), C, affine, (C + 3) & ~3, G, K, C, dZp, red, W, ldw, bias,
+    hipLaunchKernelGGL(pool_bwd_reduce_rec_kernel, dim3((unsigned)pn2_cdiv(round4(C), 64), (unsigned)gy), dim3(256), 0, pn2_s(stream), dOut,
+                       ld_dout, ldo, out, arg, reinterpret_cast<const float2 *>(pool_ws), C, affine, round4(C), G, K, C, dZp, red, W, ldw, bias,
                        prev_Y, ld_prev, prev_affine, C_in);
     return pn2_launch_status();
 }
@@ -1949,7 +1972,7 @@ int pn2_relu_bwd_reduce(const float *dOut, int ldo, const float *out, const floa
     int64_t gy = pn2_cdiv(P, 4 * 16);
     if (gy > 512) gy = 512;
     hipLaunchKernelGGL(relu_bwd_reduce_kernel, dim3((unsigned)pn2_cdiv(C, 64), (unsigned)gy), dim3(256), 0, pn2_s(stream), dOut,
-                       ldo, out, Y, ldy, affine, (C + 3) & ~3, P, C, dZ, ldz, red);
+                       ldo, out, Y, ldy, affine, round4(C), P, C, dZ, ldz, red);
     return pn2_launch_status();
 }
 
@@ -1957,56 +1980,16 @@ int pn2_bn_bwd_coef(const double *red, int64_t P, int C, const float *gamma, con
                     float *coef, float *dgamma, float *dbeta, int accumulate, pn2_stream_t stream) {
     PN2_CHECK_ARG(red && gamma && affine && coef && P > 0 && C > 0);
     hipLaunchKernelGGL(bn_bwd_coef_kernel, dim3((unsigned)pn2_cdiv(C, 128)), dim3(128), 0, pn2_s(stream), red, 1.0 / (double)P,
-                       C, (C + 3) & ~3, gamma, affine, use_batch_stats, coef, dgamma, dbeta, accumulate);
+                       C, round4(C), gamma, affine, use_batch_stats, coef, dgamma, dbeta, accumulate);
     return pn2_launch_status();
-}
-
-// `job`: the weight-gradient half pn2_conv1x1_bwd_pair wants to ride in this launch (null for the plain entry point)
-static int conv1x1_dgrad_impl(const float *dZ, int ldz, const float *dZp, int ldo, const int32_t *arg, int Kpool, const float *Y, int ldy, const float *coef, const float *W, int ldw,
-                              const float *prev_Y, int ld_prev, const float *prev_affine, float *dXout, int ldxo,
-                              double *prev_red, int64_t P, int K, int N, const pn2_bn_coef_lazy *coef_lazy, pn2_stream_t stream, PairJob *job) {
-    PN2_CHECK_ARG(Y && coef && W && dXout && P > 0 && P < (1LL << 31) && K > 0 && N > 0 && lazy_coef_ok(coef_lazy, coef, K));
-    LazyCoef lc = make_lazy_coef(coef_lazy);                            // realised by the FIRST launch below
-    PN2_CHECK_ARG(dZ != nullptr || (dZp && arg && Kpool > 0 && P < (1LL << 31)));
-    PN2_CHECK_ARG(ldw >= N && ldy % 4 == 0 && ldy >= round4(K) && ldxo % 4 == 0 && ldxo >= round4(N));
-    const BMat bm = make_bmat(W, ldw, K, N);
-    PN2_CHECK_ARG(prev_Y == nullptr || prev_affine != nullptr);
-    const int K4 = round4(K), ldc = round4(K);
-    hipStream_t s = pn2_s(stream);
-    if (prev_Y != nullptr) {                                            // wide layer: W stays in registers (mlp_wide.hip)
-        int64_t done = 0;
-        const int rc = pn2_wide_dgrad(dZ, ldz, dZp, ldo, arg, Kpool, Y, ldy, coef, W, ldw, prev_Y, ld_prev, prev_affine, dXout, ldxo,
-                                      prev_red, P, K, N, lc, s, &done);
-        if (rc != PN2_EUNSUPPORTED) {
-            if (rc != PN2_OK || done == P) return rc;
-            lc = LazyCoef{};
-            // ragged tail (whole pooling groups: the tile height divides Kpool or is a multiple of it)
-            if (dZ) dZ += done * ldz;
-            else { dZp += (done / Kpool) * ldo; arg += (done / Kpool) * ldo; }
-            Y += done * ldy; prev_Y += done * ld_prev; dXout += done * ldxo; P -= done;
-        }
-    }
-    if (dZ) {
-        PN2_CHECK_ARG(ldz % 4 == 0 && ldz >= K4);
-        LoadDyDense ld{dZ, ldz, Y, ldy, coef, ldc, zero_page_dev(), lc};
-        if (prev_Y)
-            return dispatch_nt<true>(ld, bm, P, K4, N,
-                                     EpiDgradMask{dXout, ldxo, prev_Y, ld_prev, prev_affine, round4(N), prev_red, zero_page_dev()}, s, job);
-        return dispatch_nt<true>(ld, bm, P, K4, N, EpiStore{dXout, ldxo}, s, job);
-    }
-    PN2_CHECK_ARG(ldo % 4 == 0 && ldo >= K4);
-    LoadDyPooled ld{dZp, ldo, arg, Kpool, Y, ldy, coef, ldc, zero_page_dev(), pow2_shift(Kpool), lc};
-    if (prev_Y)
-        return dispatch_nt<true>(ld, bm, P, K4, N,
-                                 EpiDgradMask{dXout, ldxo, prev_Y, ld_prev, prev_affine, round4(N), prev_red, zero_page_dev()}, s, job);
-    return dispatch_nt<true>(ld, bm, P, K4, N, EpiStore{dXout, ldxo}, s, job);
 }
 
 int pn2_conv1x1_dgrad(const float *dZ, int ldz, const float *dZp, int ldo, const int32_t *arg, int Kpool, const float *Y, int ldy, const float *coef, const float *W, int ldw,
                       const float *prev_Y, int ld_prev, const float *prev_affine, float *dXout, int ldxo,
                       double *prev_red, int64_t P, int K, int N, const pn2_bn_coef_lazy *coef_lazy, pn2_stream_t stream) {
-    return conv1x1_dgrad_impl(dZ, ldz, dZp, ldo, arg, Kpool, Y, ldy, coef, W, ldw, prev_Y, ld_prev, prev_affine, dXout, ldxo, prev_red, P, K, N,
-                              coef_lazy, stream, nullptr);
+    PN2_CHECK_ARG(lazy_coef_ok(coef_lazy, coef, K));
+    const UpGrad up{dZ, ldz, dZp, ldo, arg, Kpool, Y, ldy, coef, make_lazy_coef(coef_lazy)};     // realised by the FIRST launch
+    return pn2_dgrad_up(up, W, ldw, prev_Y, ld_prev, prev_affine, dXout, ldxo, prev_red, P, K, N, pn2_s(stream));
 }
 
 int64_t pn2_conv1x1_wgrad_workspace_bytes(int64_t P, int M, int N, int pooled) { return pn2_wide_wgrad_workspace_bytes(P, M, N, pooled); }
@@ -2018,8 +2001,7 @@ int pn2_conv1x1_wgrad_cf(const float *dZ, int ldz, const float *coef, const floa
                          pn2_stream_t stream) {
     PN2_CHECK_ARG(coef && X && W && bias && scratch && dW && P > 0 && P < (1LL << 31) && M > 0 && N > 0 && lazy_coef_ok(coef_lazy, coef, M));
     if (M % 16 != 0 || M > 128 || N > 15) return PN2_EUNSUPPORTED;
-    PN2_CHECK_ARG((dZ == nullptr || (ldz >= M && ldz % 4 == 0 && (reinterpret_cast<uintptr_t>(dZ) & 15) == 0)) && ldx >= N && lddw >= N && ldw >= N &&
-                  (reinterpret_cast<uintptr_t>(scratch) & 15) == 0);
+    PN2_CHECK_ARG((dZ == nullptr || (ldz >= M && ldz % 4 == 0 && aligned16(dZ))) && ldx >= N && lddw >= N && ldw >= N && aligned16(scratch));
     const LazyCoef lc = make_lazy_coef(coef_lazy);
     double *mom = reinterpret_cast<double *>(scratch);                              // [CF_REPL][16][16]
     float *part = reinterpret_cast<float *>(mom + CF_REPL * 256);                   // [CF_REPL][M][16]
@@ -2043,48 +2025,16 @@ int pn2_conv1x1_wgrad_cf(const float *dZ, int ldz, const float *coef, const floa
 
 int pn2_conv1x1_wgrad_ws(const float *dZ, int ldz, const float *dZp, int ldo, const int32_t *arg, int Kpool, const float *Y, int ldy, const float *coef, const float *X, int ldx,
                          const float *x_affine, float *dW, int lddw, float *dbias, int64_t P, int M, int N,
-                         const pn2_bn_coef_lazy *coef_lazy, float *workspace, pn2_stream_t stream);
+                         const pn2_bn_coef_lazy *coef_lazy, float *workspace, pn2_stream_t stream) {
+    PN2_CHECK_ARG(lazy_coef_ok(coef_lazy, coef, M));
+    const UpGrad up{dZ, ldz, dZp, ldo, arg, Kpool, Y, ldy, coef, make_lazy_coef(coef_lazy)};
+    return pn2_wgrad_up(up, X, ldx, x_affine, dW, lddw, dbias, P, M, N, workspace, pn2_s(stream));
+}
 
 int pn2_conv1x1_wgrad(const float *dZ, int ldz, const float *dZp, int ldo, const int32_t *arg, int Kpool, const float *Y, int ldy, const float *coef, const float *X, int ldx,
                       const float *x_affine, float *dW, int lddw, float *dbias, int64_t P, int M, int N,
                       const pn2_bn_coef_lazy *coef_lazy, pn2_stream_t stream) {
     return pn2_conv1x1_wgrad_ws(dZ, ldz, dZp, ldo, arg, Kpool, Y, ldy, coef, X, ldx, x_affine, dW, lddw, dbias, P, M, N, coef_lazy, nullptr, stream);
-}
-
-int pn2_conv1x1_wgrad_ws(const float *dZ, int ldz, const float *dZp, int ldo, const int32_t *arg, int Kpool, const float *Y, int ldy, const float *coef, const float *X, int ldx,
-                         const float *x_affine, float *dW, int lddw, float *dbias, int64_t P, int M, int N,
-                         const pn2_bn_coef_lazy *coef_lazy, float *workspace, pn2_stream_t stream) {
-    PN2_CHECK_ARG(Y && coef && X && dW && P > 0 && P < (1LL << 31) && M > 0 && N > 0 && lazy_coef_ok(coef_lazy, coef, M));
-    const LazyCoef lc = make_lazy_coef(coef_lazy);
-    PN2_CHECK_ARG(dZ != nullptr || (dZp && arg && Kpool > 0 && P < (1LL << 31)));
-    PN2_CHECK_ARG(ldy % 4 == 0 && ldy >= round4(M) && ldx % 4 == 0 && ldx >= round4(N) && lddw >= N);
-    const int ldc = round4(M);
-    hipStream_t s = pn2_s(stream);
-    PN2_CHECK_ARG(dZ ? (ldz % 4 == 0 && ldz >= round4(M)) : (ldo % 4 == 0 && ldo >= round4(M)));
-    {                                                                   // wide layer: all of dW resident in one workgroup (mlp_wide.hip)
-        // (the workspace is used only if it is as large as the query said it must be: the caller passes what it was told)
-        const int rc = pn2_wide_wgrad(dZ, ldz, dZp, ldo, arg, Kpool, Y, ldy, coef, X, ldx, x_affine, dW, lddw, dbias, P, M, N, lc, s,
-                                      pn2_wide_wgrad_workspace_bytes(P, M, N, dZ == nullptr) > 0 ? workspace : nullptr);
-        if (rc != PN2_EUNSUPPORTED) return rc;
-    }
-    if (dZ) {
-        const int skinny = pn2_opt(PN2_OPT_WGRAD_SKINNY);
-        if (skinny && x_affine == nullptr && N <= 16 && P >= 4096) {     // first layers: stream dZ / Y once, no MFMA
-            switch ((N + 3) / 4) {
-                case 1: return launch_skinny<1>(dZ, ldz, Y, ldy, coef, ldc, X, ldx, P, M, N, dW, lddw, dbias, s, lc);
-                case 2: return launch_skinny<2>(dZ, ldz, Y, ldy, coef, ldc, X, ldx, P, M, N, dW, lddw, dbias, s, lc);
-                case 3: return launch_skinny<3>(dZ, ldz, Y, ldy, coef, ldc, X, ldx, P, M, N, dW, lddw, dbias, s, lc);
-                default: return launch_skinny<4>(dZ, ldz, Y, ldy, coef, ldc, X, ldx, P, M, N, dW, lddw, dbias, s, lc);
-            }
-        }
-        LoadDyDense dy{dZ, ldz, Y, ldy, coef, ldc, zero_page_dev(), lc};
-        if (x_affine) return dispatch_tn(dy, LoadBnReluFixed{X, ldx, x_affine, zero_page_dev()}, P, M, N, dW, lddw, dbias, s);
-        return dispatch_tn(dy, LoadPlain{X, ldx, zero_page_dev()}, P, M, N, dW, lddw, dbias, s);
-    }
-    PN2_CHECK_ARG(ldo % 4 == 0 && ldo >= round4(M));
-    LoadDyPooled dy{dZp, ldo, arg, Kpool, Y, ldy, coef, ldc, zero_page_dev(), pow2_shift(Kpool), lc};
-    if (x_affine) return dispatch_tn(dy, LoadBnReluFixed{X, ldx, x_affine, zero_page_dev()}, P, M, N, dW, lddw, dbias, s);
-    return dispatch_tn(dy, LoadPlain{X, ldx, zero_page_dev()}, P, M, N, dW, lddw, dbias, s);
 }
 
 int pn2_conv1x1_bwd_pair(const float *dZ, int ldz, const float *dZp, int ldo, const int32_t *arg, int Kpool, const float *Y, int ldy,
@@ -2098,13 +2048,12 @@ int pn2_conv1x1_bwd_pair(const float *dZ, int ldz, const float *dZp, int ldo, co
     // the weight-gradient half rides in the data gradient's launch only where dispatch_tn would take its few-row configuration
     const bool tn_small = N > 32 && M > 32 && !(M <= 64 && N <= 64) && tn_cfg == 0 && tdepth == 2 &&
                           (P <= small_p || (P <= 2 * (int64_t)small_p && (int64_t)M * N <= 16384));
+    PN2_CHECK_ARG(lazy_coef_ok(coef_lazy, coef, C_out));
+    const UpGrad up{dZ, ldz, dZp, ldo, arg, Kpool, Y, ldy, coef, make_lazy_coef(coef_lazy)};
     PairJob job{on && tn_small, false, X, ldx, x_affine, dW, lddw, M, N};
-    const int rc = conv1x1_dgrad_impl(dZ, ldz, dZp, ldo, arg, Kpool, Y, ldy, coef, W, ldw, prev_Y, ld_prev, prev_affine, dXout, ldxo, prev_red, P,
-                                      C_out, C_in, coef_lazy, stream, &job);
-    const bool taken = job.taken;
-    if (rc != PN2_OK || taken) return rc;
-    const int rc2 = pn2_conv1x1_wgrad(dZ, ldz, dZp, ldo, arg, Kpool, Y, ldy, coef, X, ldx, x_affine, dW, lddw, nullptr, P, C_out, C_in, nullptr,
-                                      stream);
+    const int rc = pn2_dgrad_up(up, W, ldw, prev_Y, ld_prev, prev_affine, dXout, ldxo, prev_red, P, C_out, C_in, pn2_s(stream), &job);
+    if (rc != PN2_OK || job.taken) return rc;
+    const int rc2 = pn2_wgrad_up(up.without_lazy(), X, ldx, x_affine, dW, lddw, nullptr, P, C_out, C_in, nullptr, pn2_s(stream));
     return rc2 == PN2_OK ? PN2_OK_SPLIT : rc2;             // done, as two launches (callers that account per launch can tell)
 }
 

@@ -17,14 +17,8 @@
 //     work -- dX tiles (contraction over C_out) and dW tiles (contraction over the 64 rows; divisible by row halves
 //     because dW is accumulated with atomics anyway) -- is dealt to the waves by a host-side LPT plan so every wave
 //     issues the same number of MFMAs.  dW accumulators stay in registers across all tiles of the workgroup.
-#include "mlp_loaders.h"
+#include "mlp_host.h"
 #include "split_bf16.h"
-#include <algorithm>
-
-// mlp_wide.hip: the register-stationary forward (with the pooling extrema in its epilogue when Kpool > 0)
-int pn2_wide_fwd(const float *X, int ldx, const float *in_affine, const float *W, int ldw, const float *bias, float *Y, int ldy,
-                 int64_t P, int K, int N, double *stats, LazyBn lz, hipStream_t s, int64_t *rows_done, int Kpool,
-                 const float *pool_gamma, float *pool_ws);
 
 namespace {
 
@@ -477,7 +471,19 @@ inline size_t bwd_res_lds_bytes(int Co, int Ci, bool dbuf) {
 
 template <int CO_T, int CI_T, int POOL, bool MASKED, int DEPTH, bool DBUF, int NTHR = 512>
 int launch_bwd_res_impl(ResDy dy, const float *Yp, int ldp, const float *aff_p, const float *W, int ldw, int64_t tiles, float *dX, int ldxo,
-                        double *red_p, float *dW, int lddw, hipStream_t s);
+                        double *red_p, float *dW, int lddw, hipStream_t s) {
+    ResPlan plan;
+    if (!(NTHR == 256 ? make_res_plan4(CI_T, &plan) : make_res_plan(CI_T, &plan))) return PN2_EINVAL;
+    const size_t lds = bwd_res_lds_bytes(32 * CO_T, 32 * CI_T, DBUF);
+    static Pn2PerDevice raised;
+    if (pn2_raise_dynamic_lds(reinterpret_cast<const void *>(&bwd_res_kernel<CO_T, CI_T, POOL, MASKED, DEPTH, DBUF, NTHR>), raised) != PN2_OK)
+        return PN2_ELAUNCH;
+    const int64_t cap = (int64_t)pn2_num_cus() * (512 / NTHR);     // one 8-wave workgroup per CU, or two of four waves
+    PN2_NOTE_KERNEL(bwd_res_kernel<CO_T, CI_T, POOL, MASKED, DEPTH, DBUF, NTHR>);
+    hipLaunchKernelGGL((bwd_res_kernel<CO_T, CI_T, POOL, MASKED, DEPTH, DBUF, NTHR>), dim3((unsigned)(tiles < cap ? tiles : cap)), dim3(NTHR), lds, s, dy, Yp,
+                       ldp, aff_p, W, ldw, tiles, dX, ldxo, red_p, dW, lddw, plan);
+    return pn2_launch_status();
+}
 
 template <int CO_T, int CI_T, int POOL, bool MASKED>
 int launch_bwd_res(ResDy dy, const float *Yp, int ldp, const float *aff_p, const float *W, int ldw, int64_t tiles, float *dX, int ldxo,
@@ -500,22 +506,6 @@ int launch_bwd_res(ResDy dy, const float *Yp, int ldp, const float *aff_p, const
             return launch_bwd_res_impl<CO_T, CI_T, POOL, MASKED, 1, false, 256>(dy, Yp, ldp, aff_p, W, ldw, tiles, dX, ldxo, red_p, dW, lddw, s);
     }
     return launch_bwd_res_impl<CO_T, CI_T, POOL, MASKED, DEPTH, false>(dy, Yp, ldp, aff_p, W, ldw, tiles, dX, ldxo, red_p, dW, lddw, s);
-}
-
-template <int CO_T, int CI_T, int POOL, bool MASKED, int DEPTH, bool DBUF, int NTHR>
-int launch_bwd_res_impl(ResDy dy, const float *Yp, int ldp, const float *aff_p, const float *W, int ldw, int64_t tiles, float *dX, int ldxo,
-                        double *red_p, float *dW, int lddw, hipStream_t s) {
-    ResPlan plan;
-    if (!(NTHR == 256 ? make_res_plan4(CI_T, &plan) : make_res_plan(CI_T, &plan))) return PN2_EINVAL;
-    const size_t lds = bwd_res_lds_bytes(32 * CO_T, 32 * CI_T, DBUF);
-    static Pn2PerDevice raised;
-    if (pn2_raise_dynamic_lds(reinterpret_cast<const void *>(&bwd_res_kernel<CO_T, CI_T, POOL, MASKED, DEPTH, DBUF, NTHR>), raised) != PN2_OK)
-        return PN2_ELAUNCH;
-    const int64_t cap = (int64_t)pn2_num_cus() * (512 / NTHR);     // one 8-wave workgroup per CU, or two of four waves
-    PN2_NOTE_KERNEL(bwd_res_kernel<CO_T, CI_T, POOL, MASKED, DEPTH, DBUF, NTHR>);
-    hipLaunchKernelGGL((bwd_res_kernel<CO_T, CI_T, POOL, MASKED, DEPTH, DBUF, NTHR>), dim3((unsigned)(tiles < cap ? tiles : cap)), dim3(NTHR), lds, s, dy, Yp,
-                       ldp, aff_p, W, ldw, tiles, dX, ldxo, red_p, dW, lddw, plan);
-    return pn2_launch_status();
 }
 
 #ifndef PN2_SPLIT_RES_DXFREE
@@ -932,7 +922,7 @@ int launch_split_bwd_res(ResDy dy, const float *Yp, int ldp, const float *aff_p,
     constexpr size_t lds = 2 * 6 * (size_t)(32 * 256) + sizeof(float) * (2 * 32 * (Ci + 4) + 8 * Co + 6 * Ci + (FUSE0 ? 2 * 32 * 12 : 0)) +
                            (CO_T == 4 && CI_T < 4 ? (size_t)CI_T * (Co / 16) * 1024 : 0);      // (the kernel's WL_LDS region)
     static_assert(lds <= 160 * 1024, "LDS");
-    if ((reinterpret_cast<uintptr_t>(dy.Y) & 15) != 0 || (reinterpret_cast<uintptr_t>(Yp) & 15) != 0) return PN2_EUNSUPPORTED;
+    if (!aligned16(dy.Y) || !aligned16(Yp)) return PN2_EUNSUPPORTED;
     auto kern = split_bwd_res_kernel<CO_T, CI_T, POOLED, MASKED, FUSE0>;
     static Pn2PerDevice raised;
     if (pn2_raise_dynamic_lds(reinterpret_cast<const void *>(kern), raised) != PN2_OK) return PN2_ELAUNCH;
@@ -1396,10 +1386,10 @@ int launch_split_bwd_cf(const float *dZp, const int32_t *arg, int ldo, int kshif
     float *W2 = scratch, *slab = scratch + (((Co + Ci + 1) * Ci + 63) & ~63);
     const int64_t chunks = P / 32, cap = pn2_num_cus() < 256 ? pn2_num_cus() : 256;
     const int grid = (int)(chunks < cap ? chunks : cap);
-    hipLaunchKernelGGL(cf_prep_kernel, dim3(Co + Ci + 1), dim3(128), 0, s, lc, coef, (Co + 3) & ~3, W, ldw, bias, Co, Ci, W2);
+    hipLaunchKernelGGL(cf_prep_kernel, dim3(Co + Ci + 1), dim3(128), 0, s, lc, coef, round4(Co), W, ldw, bias, Co, Ci, W2);
     PN2_NOTE_KERNEL(kern);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, s, dZp, arg, ldo, kshift, W2, Yp, ldp, aff_p, chunks, dX, ldxo, red_p, slab);
-    hipLaunchKernelGGL(cf_finish_kernel, dim3(Ci), dim3(256), sizeof(double) * 4 * LDT, s, slab, grid, Co, Ci, coef, (Co + 3) & ~3, W, ldw, bias,
+    hipLaunchKernelGGL(cf_finish_kernel, dim3(Ci), dim3(256), sizeof(double) * 4 * LDT, s, slab, grid, Co, Ci, coef, round4(Co), W, ldw, bias,
                        dW, lddw);
     return pn2_launch_status();
 }
@@ -1784,7 +1774,7 @@ extern "C" int pn2_res_supported(int64_t P, int C_out, int C_in) {
 // it to the streamed dgrad + wgrad pair.  Kpool = 0: dense dZ; masked: the layer has a BatchNorm + ReLU input (prev_affine).
 extern "C" int pn2_bwd_res_supported(int64_t P, int C_out, int C_in, int Kpool, int masked) {
     if (!pn2_res_supported(P, C_out, C_in)) return 0;
-    if (P * (int64_t)std::max(C_out, C_in) >= (1LL << 32)) return 0;     // 32-bit element offsets inside the fused kernel
+    if (!fits_u32_offsets(P, C_out, C_in)) return 0;                     // 32-bit element offsets inside the fused kernel
     const int64_t tiles = P / RES_BM;
     const auto is = [&](int co, int ci) { return C_out == co && C_in == ci; };
     const int64_t min128 = (pn2_opt(PN2_OPT_SPLIT) && pn2_opt(PN2_OPT_SPLIT_RES)) ? std::min<int64_t>(4096, pn2_opt(PN2_OPT_SPLIT_RES_MIN_TILES_128)) : 4096;
@@ -1843,7 +1833,7 @@ extern "C" int pn2_conv1x1_fwd_pool(const float *X, int ldx, const float *in_aff
     PN2_CHECK_ARG(X && in_affine && W && bias && stats && gamma && pool_ws && P > 0 && P < (1LL << 31) && K > 0 && N > 0 && Kpool > 0);
     PN2_CHECK_ARG(lazy_bn_ok(in_lazy, in_affine, K));
     PN2_CHECK_ARG(ldx % 4 == 0 && ldx >= K && ldw >= K && ldy % 4 == 0 && ldy >= N);
-    PN2_CHECK_ARG((reinterpret_cast<uintptr_t>(pool_ws) & 15) == 0);
+    PN2_CHECK_ARG(aligned16(pool_ws));
     if (P % Kpool == 0 && ldy == N && N % 32 == 0) {                 // wide last layers (128 / 196 -> 256): the register-stationary forward
         int64_t done = 0;
         const int rc = pn2_wide_fwd(X, ldx, in_affine, W, ldw, bias, Y, ldy, P, K, N, stats, make_lazy_bn(in_lazy), pn2_s(stream), &done,
@@ -1866,7 +1856,7 @@ extern "C" int pn2_bn_pool_select(const float *pool_ws, const float *affine, int
     PN2_CHECK_ARG(lazy_bn_ok(lazy, affine, C));
     // ldo: pitch of out AND of arg (out may be a column slice of a wider matrix: the concatenated MSG output)
     PN2_CHECK_ARG(pool_ws && affine && out && arg && G > 0 && C > 0 && C % 32 == 0 && ldo >= C && ldo % 4 == 0 &&
-                  (reinterpret_cast<uintptr_t>(pool_ws) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0);
+                  aligned16(pool_ws) && aligned16(out));
     const int64_t n = G * (C >> 2);
     int64_t blocks = pn2_cdiv(n, 256);
     const int64_t cap = (int64_t)pn2_num_cus() * 8;                 // bounded grid (see the kernel)
@@ -1882,38 +1872,32 @@ extern "C" int pn2_conv1x1_bwd(const float *dZ, int ldz, const float *dZp, int l
                                int64_t P, int C_out, int C_in, const pn2_bn_coef_lazy *coef_lazy, pn2_stream_t stream) {
     PN2_CHECK_ARG(Y && coef && W && prev_Y && dXout && dW && P > 0 && P < (1LL << 31) && res_shape_ok(C_out, C_in));
     PN2_CHECK_ARG(lazy_coef_ok(coef_lazy, coef, C_out));
-    PN2_CHECK_ARG(dZ != nullptr || (dZp && arg && Kpool > 0));
-    PN2_CHECK_ARG(ldw >= C_in && lddw >= C_in && ldy % 4 == 0 && ldy >= C_out && ld_prev % 4 == 0 && ld_prev >= C_in && ldxo >= C_in);
+    const UpGrad up{dZ, ldz, dZp, ldo, arg, Kpool, Y, ldy, coef, make_lazy_coef(coef_lazy)};
+    PN2_CHECK_ARG(up.valid(C_out) && ldw >= C_in && lddw >= C_in && ld_prev % 4 == 0 && ld_prev >= C_in && ldxo >= C_in);
     PN2_CHECK_ARG(prev_affine != nullptr || prev_red == nullptr);
     hipStream_t s = pn2_s(stream);
-    const int kshift = dZ ? 0 : pow2_shift(Kpool);
-    PN2_CHECK_ARG(dZ ? (ldz == ldy) : (kshift >= 0 && ldo % 4 == 0 && ldo >= C_out && prev_affine != nullptr && P % Kpool == 0));
+    // what the fused kernel asks beyond that: one pitch for Y and a dense dZ; whole power-of-two groups under a masked input
+    PN2_CHECK_ARG(dZ ? (ldz == ldy) : (pow2_shift(Kpool) >= 0 && prev_affine != nullptr && P % Kpool == 0));
     int64_t tiles = P / RES_BM, P_full = tiles * RES_BM;
     int rc = PN2_OK;
     // the fused kernel addresses with 32-bit element offsets (tile base + lane term): past 2^32 elements of any of its
     // matrices (16 GiB: the K = 128 branch of the dense scans at B = 16) the streamed pair below takes all rows
-    const int64_t ld_max = std::max(std::max((int64_t)ldy, (int64_t)ld_prev), std::max((int64_t)ldxo, dZ ? (int64_t)ldz : (int64_t)ldo));
-    if (P * ld_max >= (1LL << 32)) { tiles = 0; P_full = 0; }
+    if (!fits_u32_offsets(P, ldy, ld_prev, ldxo, dZ ? ldz : ldo)) { tiles = 0; P_full = 0; }
+    UpGrad rest = up;                                                              // what the streamed kernels below have to do
     if (tiles > 0) {
-        ResDy dy{dZ, dZp, arg, ldo, kshift, Y, ldy, coef, make_lazy_coef(coef_lazy)};
-        rc = dispatch_bwd_res(dZ ? 0 : Kpool, prev_affine != nullptr, C_out, C_in, dy, prev_Y, ld_prev, prev_affine, W, ldw, tiles, dXout, ldxo,
-                              prev_red, dW, lddw, s);
+        rc = dispatch_bwd_res(dZ ? 0 : Kpool, prev_affine != nullptr, C_out, C_in, res_dy<ResDy>(up), prev_Y, ld_prev, prev_affine, W, ldw, tiles,
+                              dXout, ldxo, prev_red, dW, lddw, s);
         if (rc == PN2_EUNSUPPORTED) { rc = PN2_OK; tiles = 0; P_full = 0; }    // no weight-resident kernel for this pair: all rows below
-        else coef_lazy = nullptr;                                              // the block is filled: the tail launches read it
+        else rest = up.advanced(P_full);                                       // the block is filled: the tail launches read it
     }
     if (rc != PN2_OK || P_full == P) return rc;
-    // ragged tail (< 64 rows), or a pair without a resident kernel: the streamed kernels, on offset pointers; everything
-    // they produce is accumulated
+    // ragged tail (< 64 rows; P_full is a multiple of Kpool: Kpool | 64), or a pair without a resident kernel: the streamed
+    // kernels, on offset pointers; everything they produce is accumulated
     const int64_t tail = P - P_full;
-    const int64_t g_off = dZ ? 0 : (P_full / Kpool) * ldo;                     // P_full is a multiple of Kpool here (Kpool | 64)
-    const float *dZt = dZ ? dZ + P_full * ldz : nullptr;
-    const float *dZpt = dZ ? nullptr : dZp + g_off;
-    const int32_t *argt = dZ ? nullptr : arg + g_off;
-    rc = pn2_conv1x1_dgrad(dZt, ldz, dZpt, ldo, argt, Kpool, Y + P_full * ldy, ldy, coef, W, ldw, prev_affine ? prev_Y + P_full * ld_prev : nullptr,
-                           ld_prev, prev_affine, dXout + P_full * ldxo, ldxo, prev_red, tail, C_out, C_in, coef_lazy, stream);
+    rc = pn2_dgrad_up(rest, W, ldw, prev_affine ? prev_Y + P_full * ld_prev : nullptr, ld_prev, prev_affine, dXout + P_full * ldxo, ldxo, prev_red,
+                      tail, C_out, C_in, s);
     if (rc != PN2_OK) return rc;
-    return pn2_conv1x1_wgrad(dZt, ldz, dZpt, ldo, argt, Kpool, Y + P_full * ldy, ldy, coef, prev_Y + P_full * ld_prev, ld_prev, prev_affine,
-                             dW, lddw, nullptr, tail, C_out, C_in, nullptr, stream);
+    return pn2_wgrad_up(rest.without_lazy(), prev_Y + P_full * ld_prev, ld_prev, prev_affine, dW, lddw, nullptr, tail, C_out, C_in, nullptr, s);
 }
 
 // ----------------------------------------------------------------------------------------------- pooled last layer from its input: entry points
@@ -1926,7 +1910,7 @@ extern "C" int pn2_conv1x1_bwd_cf_supported(int64_t P, int C_out, int C_in, int 
     // one (159 vs 158 us at 524 288 rows, + 18 us of prep / finish); in the step the forward runs 125 -> 99 us and cfg5 MSG gains 0.3 ms
     if (C_in == 64 && pn2_opt(PN2_OPT_POOL_CF) < 2) return 0;
     if (Kpool < 32 || (Kpool & (Kpool - 1)) != 0 || P % Kpool != 0) return 0;
-    if (P * (int64_t)std::max(C_out, C_in) >= (1LL << 32)) return 0;           // 32-bit element offsets inside the kernel
+    if (!fits_u32_offsets(P, C_out, C_in)) return 0;                           // 32-bit element offsets inside the kernel
     return 1;
 }
 
@@ -1943,11 +1927,9 @@ extern "C" int pn2_conv1x1_bwd_cf(const float *dZp, int ldo, const int32_t *arg,
     PN2_CHECK_ARG(dZp && arg && coef && W && bias && prev_Y && prev_affine && dXout && dW && scratch && P > 0 && P < (1LL << 31));
     PN2_CHECK_ARG(lazy_coef_ok(coef_lazy, coef, C_out));
     PN2_CHECK_ARG(ldw >= C_in && lddw >= C_in && ld_prev % 4 == 0 && ld_prev >= C_in && ldxo >= C_in && ldo % 4 == 0 && ldo >= C_out);
-    PN2_CHECK_ARG((reinterpret_cast<uintptr_t>(scratch) & 255) == 0 && (reinterpret_cast<uintptr_t>(prev_Y) & 15) == 0 &&
-                  (reinterpret_cast<uintptr_t>(dZp) & 15) == 0 && (reinterpret_cast<uintptr_t>(arg) & 15) == 0);
+    PN2_CHECK_ARG((reinterpret_cast<uintptr_t>(scratch) & 255) == 0 && aligned16(prev_Y) && aligned16(dZp) && aligned16(arg));
     if (!pn2_conv1x1_bwd_cf_supported(P, C_out, C_in, Kpool)) return PN2_EUNSUPPORTED;
-    const int64_t ld_max = std::max(std::max((int64_t)ld_prev, (int64_t)ldxo), (int64_t)ldo);
-    if (P * ld_max >= (1LL << 32)) return PN2_EUNSUPPORTED;
+    if (!fits_u32_offsets(P, ld_prev, ldxo, ldo)) return PN2_EUNSUPPORTED;
     const int kshift = pow2_shift(Kpool);
     const LazyCoef lc = make_lazy_coef(coef_lazy);
     hipStream_t s = pn2_s(stream);
@@ -1959,7 +1941,7 @@ extern "C" int pn2_conv1x1_bwd_cf(const float *dZp, int ldo, const int32_t *arg,
 extern "C" int pn2_conv1x1_bwd_first_supported(int64_t P, int C_out, int C_in, int N0) {
     if (!(pn2_opt(PN2_OPT_SPLIT) && pn2_opt(PN2_OPT_SPLIT_RES) && pn2_opt(PN2_OPT_FUSE_FIRST))) return 0;
     if (!pn2_res_supported(P, C_out, C_in) || P % 64 != 0 || N0 < 1 || N0 > 12) return 0;
-    if (P * (int64_t)std::max(C_out, C_in) >= (1LL << 32)) return 0;
+    if (!fits_u32_offsets(P, C_out, C_in)) return 0;
     return (C_out == 96 && C_in == 64) || (C_out == 64 && C_in == 64);
 }
 
@@ -1970,12 +1952,12 @@ extern "C" int pn2_conv1x1_bwd_first(const float *dZ, int ldz, const float *Y, i
     PN2_CHECK_ARG(dZ && Y && coef && W && prev_Y && prev_affine && prev_red && dW && X0 && cf_scratch && P > 0 && P < (1LL << 31));
     PN2_CHECK_ARG(lazy_coef_ok(coef_lazy, coef, C_out));
     PN2_CHECK_ARG(ldz == ldy && ldw >= C_in && lddw >= C_in && ldy % 4 == 0 && ldy >= C_out && ld_prev % 4 == 0 && ld_prev >= C_in);
-    PN2_CHECK_ARG(ld0 % 4 == 0 && ld0 >= 12 && (reinterpret_cast<uintptr_t>(X0) & 15) == 0 && (reinterpret_cast<uintptr_t>(cf_scratch) & 15) == 0);
+    PN2_CHECK_ARG(ld0 % 4 == 0 && ld0 >= 12 && aligned16(X0) && aligned16(cf_scratch));
     if (!pn2_conv1x1_bwd_first_supported(P, C_out, C_in, N0)) return PN2_EUNSUPPORTED;
-    if (P * (int64_t)std::max((int64_t)ldy, std::max((int64_t)ld_prev, (int64_t)ld0)) >= (1LL << 32)) return PN2_EUNSUPPORTED;
+    if (!fits_u32_offsets(P, ldy, ld_prev, ld0)) return PN2_EUNSUPPORTED;
     // pn2_conv1x1_wgrad_cf's scratch: moments [PN2_CF_REPL][16][16] doubles, then part [PN2_CF_REPL][128][16] floats (here: [..][C_in][16])
     float *part0 = reinterpret_cast<float *>(reinterpret_cast<double *>(cf_scratch) + PN2_CF_REPL * 256);
-    ResDy dy{dZ, nullptr, nullptr, 0, 0, Y, ldy, coef, make_lazy_coef(coef_lazy)};
+    const ResDy dy = res_dy<ResDy>(UpGrad{dZ, ldz, nullptr, 0, nullptr, 0, Y, ldy, coef, make_lazy_coef(coef_lazy)});
     const int64_t tiles = P / RES_BM;
     hipStream_t s = pn2_s(stream);
     if (C_out == 96) return launch_split_bwd_res<3, 2, false, true, true>(dy, prev_Y, ld_prev, prev_affine, W, ldw, tiles, nullptr, 0, prev_red, dW, lddw, s, X0, ld0, part0);

@@ -19,7 +19,7 @@
 // hold is a property of their own mix of LDS, memory and matrix work, not a ceiling.)
 //
 // Whole BM-row tiles only; the entry points of mlp.hip hand a ragged tail to the streamed kernels.
-#include "mlp_loaders.h"
+#include "mlp_host.h"
 #include "split_bf16.h"
 
 namespace {
@@ -1432,17 +1432,17 @@ int pn2_wide_fwd(const float *X, int ldx, const float *in_affine, const float *W
                  const float *pool_gamma, float *pool_ws) {
     const int on = pn2_opt(PN2_OPT_WIDE), min_rows = pn2_opt(PN2_OPT_WIDE_MIN_ROWS);
     *rows_done = 0;
-    if (!on || P < min_rows || ldx != ((K + 3) & ~3)) return PN2_EUNSUPPORTED;
+    if (!on || P < min_rows || ldx != round4(K)) return PN2_EUNSUPPORTED;
     // the LDS-DMA ring form (16-byte aligned rows; PN2_RING=0: the register-staged kernel, A/B runs)
     const int ring_on = pn2_opt(PN2_OPT_RING);
-    const bool ring = ring_on && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
+    const bool ring = ring_on && aligned16(X);
     RegwArgs g{};
     g.lz = lz;
     g.A = X; g.lda = ldx; g.tab = in_affine; g.W = W; g.ldw = ldw; g.bias = bias; g.Out = Y; g.ldout = ldy; g.red = stats;
     g.K = K; g.N = N;
     g.pool_rec = reinterpret_cast<float2 *>(pool_ws); g.pool_gamma = pool_gamma; g.pool_ld = N;
     // fp32 products on the bf16 pipe (split_nt_kernel; option PN2_SPLIT): 64-row tiles (128 where the waves split the rows)
-    if (pn2_opt(PN2_OPT_SPLIT) && (reinterpret_cast<uintptr_t>(X) & 15) == 0 && (reinterpret_cast<uintptr_t>(W) & 15) == 0 && (ldw & 3) == 0) {
+    if (pn2_opt(PN2_OPT_SPLIT) && aligned16(X) && aligned16(W) && (ldw & 3) == 0) {
         const bool pool_ok = Kpool == 0 || (in_affine && pool_gamma && pool_ws && pn2_opt(PN2_OPT_WIDE_POOL) && P % 128 == 0);
 #define SPLIT_FWD(KK, NN, NCB, RS, TM, PKP)                                                                              \
         if (K == KK && N == NN && Kpool == PKP && pool_ok && (Y != nullptr || PKP > 0)) {                                \
@@ -1514,19 +1514,18 @@ int pn2_wide_fwd(const float *X, int ldx, const float *in_affine, const float *W
     return PN2_EUNSUPPORTED;
 }
 
-int pn2_wide_dgrad(const float *dZ, int ldz, const float *dZp, int ldo, const int32_t *arg, int Kpool, const float *Y, int ldy,
-                   const float *coef, const float *W, int ldw, const float *prev_Y, int ld_prev, const float *prev_affine,
-                   float *dXout, int ldxo, double *prev_red, int64_t P, int K, int N, LazyCoef lc, hipStream_t s, int64_t *rows_done) {
+int pn2_wide_dgrad(const UpGrad &up, const float *W, int ldw, const float *prev_Y, int ld_prev, const float *prev_affine, float *dXout,
+                   int ldxo, double *prev_red, int64_t P, int K, int N, hipStream_t s, int64_t *rows_done) {
     const int on = pn2_opt(PN2_OPT_WIDE), min_rows = pn2_opt(PN2_OPT_WIDE_MIN_ROWS);
+    const float *const dZ = up.dZ, *const Y = up.Y; const int Kpool = up.Kpool, ldo = up.ldo;     // (the names the tables below use)
     *rows_done = 0;
-    if (!on || P < min_rows || ldy != ((K + 3) & ~3) || prev_Y == nullptr) return PN2_EUNSUPPORTED;
+    if (!on || P < min_rows || up.ldy != round4(K) || prev_Y == nullptr) return PN2_EUNSUPPORTED;
     if (!dZ && (Kpool <= 0 || P % Kpool != 0)) return PN2_EUNSUPPORTED;
     RegwArgs g{};
-    g.lc = lc;
-    g.A = Y; g.lda = ldy; g.dZ = dZ; g.ldz = ldz; g.dZp = dZp; g.arg = arg; g.ldo = ldo; g.kshift = 0; g.tab = coef;
+    fill_dz(g, up); g.lc = up.lc; g.A = Y; g.lda = up.ldy; g.tab = up.coef;      // (kshift stays 0: the group size is a template parameter)
     g.W = W; g.ldw = ldw; g.Out = dXout; g.ldout = ldxo; g.prevY = prev_Y; g.ldp = ld_prev; g.prev_aff = prev_affine; g.red = prev_red;
     g.K = K; g.N = N;
-    if (pn2_opt(PN2_OPT_SPLIT) && pn2_opt(PN2_OPT_SPLIT_K256) && dZ == nullptr && (reinterpret_cast<uintptr_t>(Y) & 15) == 0 && ldo % 4 == 0) {
+    if (pn2_opt(PN2_OPT_SPLIT) && pn2_opt(PN2_OPT_SPLIT_K256) && dZ == nullptr && aligned16(Y) && ldo % 4 == 0) {
         // K = 256 (the pooled last layers of sa2): the contraction split over wave pairs, N = 196 as two column groups
 #define SPLIT_DGRAD_P(KK, NN, NCB, NG, PKP)                                                                              \
         if (K == KK && N == NN && Kpool == PKP && P % 64 == 0) {                                                         \
@@ -1540,7 +1539,7 @@ int pn2_wide_dgrad(const float *dZ, int ldz, const float *dZp, int ldo, const in
         SPLIT_DGRAD_P(256, 196, 4, 2, 64)
 #undef SPLIT_DGRAD_P
     }
-    if (pn2_opt(PN2_OPT_SPLIT) && dZ != nullptr && (reinterpret_cast<uintptr_t>(Y) & 15) == 0 && (reinterpret_cast<uintptr_t>(dZ) & 15) == 0) {
+    if (pn2_opt(PN2_OPT_SPLIT) && dZ != nullptr && aligned16(Y) && aligned16(dZ)) {
         // fp32 products on the bf16 pipe, contraction lengths that fit the register-held W slice (K <= 208): the dense data gradients
 #define SPLIT_DGRAD(KK, NN, NCB, RS, TM, MINROWS)                                                                        \
         if (K == KK && N == NN && P >= MINROWS) {                                                                        \
@@ -2067,44 +2066,10 @@ __global__ __launch_bounds__(64 * ((MM + 31) / 32) * (((NN + 31) / 32) / TNW)) v
     }
 }
 
-template <int MM, int NN, int TNW, int DYM, int PKP, int BP>
-int launch_split_tn(WgradArgs g, hipStream_t s) {
-    constexpr int MB = (MM + 31) / 32, NB = (NN + 31) / 32, NW = MB * (NB / TNW);
-    constexpr int PA = (MB * 32 + 127) / 128, PB = (NB * 32 + 127) / 128, BUF = 3 * (PA + PB) * BP * 256;
-    constexpr size_t lds = 2 * (size_t)BUF + sizeof(float) * (4 * MB * 32 + 3 * NB * 32);
-    static_assert(lds <= 160 * 1024, "LDS");
-    if (g.dbias != nullptr || g.P % BP != 0) return PN2_EUNSUPPORTED;
-    auto kern = split_tn_kernel<MM, NN, TNW, DYM, PKP, BP>;
-    static Pn2PerDevice raised;
-    if (pn2_raise_dynamic_lds(reinterpret_cast<const void *>(kern), raised) != PN2_OK) return PN2_ELAUNCH;
-    int64_t wgs = pn2_num_cus();
-    int64_t rows = pn2_cdiv(pn2_cdiv(g.P, wgs), BP) * BP;
-    if (PKP > 0 && rows % PKP != 0 && PKP % rows != 0) rows = pn2_cdiv(rows, PKP) * PKP;   // chunks never straddle a group: BP | PKP
-    g.rows_per_wg = rows;
-    wgs = pn2_cdiv(g.P, rows);
-    PN2_NOTE_KERNEL(kern);
-    hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(64 * NW), lds, s, g);
-    if (g.ws != nullptr) {                                          // (second phase as launch_wgrad_full's)
-        const int rows_pad = MB * 32, ldn = NB * 32;
-        const unsigned gx = (unsigned)pn2_cdiv((int64_t)rows_pad * (ldn / 4), 256);
-        unsigned gy = (unsigned)(4 * pn2_num_cus() / gx);
-        if (gy < 1) gy = 1;
-        if (gy > (unsigned)wgs) gy = (unsigned)wgs;
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(gx, gy), dim3(256), 0, s, g.ws, (int)wgs, rows_pad, ldn, g.M, g.N, g.dW, g.lddw);
-    }
-    return pn2_launch_status();
-}
-
-template <int MM, int NN, int TNW, int DYM, bool XACT, int PKP, int BP>
-int launch_wgrad_full(WgradArgs g, hipStream_t s) {
-    constexpr int MB = (MM + 31) / 32, NB = (NN + 31) / 32;
-    constexpr int NW = MB * (NB / TNW), LDA = MB * 32 + 4, LDB = NB * 32 + 4;
-    constexpr size_t lds = sizeof(float) * (2 * BP * LDA + 2 * BP * LDB + 4 * MB * 32 + 3 * NB * 32 + 4 * 64 * NW);
-    static_assert(lds <= 160 * 1024, "LDS");
-    auto kern = wgrad_full_kernel<MM, NN, TNW, DYM, XACT, PKP, BP, false>;
-    if (g.dbias != nullptr) return PN2_EUNSUPPORTED;              // (eval-mode bias gradients: the streamed kernel)
-    static Pn2PerDevice raised;
-    if (pn2_raise_dynamic_lds(reinterpret_cast<const void *>(kern), raised) != PN2_OK) return PN2_ELAUNCH;
+// The launch the two full-product weight gradients share: one workgroup per CU, each with an equal share of the rows in whole
+// BP-row chunks; with caller scratch, the second phase of the two-phase flush behind it.
+template <class Kern>
+int launch_wgrad_wgs(Kern kern, WgradArgs g, int PKP, int BP, int MB, int NB, int NW, size_t lds, hipStream_t s) {
     int64_t wgs = pn2_num_cus();
     int64_t rows = pn2_cdiv(pn2_cdiv(g.P, wgs), BP) * BP;
     if (PKP > 0 && rows % PKP != 0 && PKP % rows != 0) rows = pn2_cdiv(rows, PKP) * PKP;   // chunks never straddle a group: BP | PKP
@@ -2123,21 +2088,47 @@ int launch_wgrad_full(WgradArgs g, hipStream_t s) {
     return pn2_launch_status();
 }
 
+template <int MM, int NN, int TNW, int DYM, int PKP, int BP>
+int launch_split_tn(WgradArgs g, hipStream_t s) {
+    constexpr int MB = (MM + 31) / 32, NB = (NN + 31) / 32, NW = MB * (NB / TNW);
+    constexpr int PA = (MB * 32 + 127) / 128, PB = (NB * 32 + 127) / 128, BUF = 3 * (PA + PB) * BP * 256;
+    constexpr size_t lds = 2 * (size_t)BUF + sizeof(float) * (4 * MB * 32 + 3 * NB * 32);
+    static_assert(lds <= 160 * 1024, "LDS");
+    if (g.dbias != nullptr || g.P % BP != 0) return PN2_EUNSUPPORTED;
+    auto kern = split_tn_kernel<MM, NN, TNW, DYM, PKP, BP>;
+    static Pn2PerDevice raised;
+    if (pn2_raise_dynamic_lds(reinterpret_cast<const void *>(kern), raised) != PN2_OK) return PN2_ELAUNCH;
+    return launch_wgrad_wgs(kern, g, PKP, BP, MB, NB, NW, lds, s);
+}
+
+template <int MM, int NN, int TNW, int DYM, bool XACT, int PKP, int BP>
+int launch_wgrad_full(WgradArgs g, hipStream_t s) {
+    constexpr int MB = (MM + 31) / 32, NB = (NN + 31) / 32;
+    constexpr int NW = MB * (NB / TNW), LDA = MB * 32 + 4, LDB = NB * 32 + 4;
+    constexpr size_t lds = sizeof(float) * (2 * BP * LDA + 2 * BP * LDB + 4 * MB * 32 + 3 * NB * 32 + 4 * 64 * NW);
+    static_assert(lds <= 160 * 1024, "LDS");
+    auto kern = wgrad_full_kernel<MM, NN, TNW, DYM, XACT, PKP, BP, false>;
+    if (g.dbias != nullptr) return PN2_EUNSUPPORTED;              // (eval-mode bias gradients: the streamed kernel)
+    static Pn2PerDevice raised;
+    if (pn2_raise_dynamic_lds(reinterpret_cast<const void *>(kern), raised) != PN2_OK) return PN2_ELAUNCH;
+    return launch_wgrad_wgs(kern, g, PKP, BP, MB, NB, NW, lds, s);
+}
+
 }  // namespace
 
 // wide weight gradients (C_out x C_in): 256 x 196 and 256 x 128 on the max-pool's sparse dZ (groups of 64 or 128), 196 x 128 and
 // 128 x 128 dense; the input is always a BatchNorm + ReLU of the previous layer's output here
-int pn2_wide_wgrad(const float *dZ, int ldz, const float *dZp, int ldo, const int32_t *arg, int Kpool, const float *Y, int ldy,
-                   const float *coef, const float *X, int ldx, const float *x_affine, float *dW, int lddw, float *dbias,
-                   int64_t P, int M, int N, LazyCoef lc, hipStream_t s, float *workspace) {
+int pn2_wide_wgrad(const UpGrad &up, const float *X, int ldx, const float *x_affine, float *dW, int lddw, float *dbias, int64_t P,
+                   int M, int N, hipStream_t s, float *workspace) {
     const int on = pn2_opt(PN2_OPT_WIDE) && pn2_opt(PN2_OPT_WIDE_WGRAD);
     const int min_rows = pn2_opt(PN2_OPT_WIDE_WGRAD_MIN_ROWS);
-    if (!on || P < min_rows || x_affine == nullptr || ldy != ((M + 3) & ~3) || ldx != ((N + 3) & ~3)) return PN2_EUNSUPPORTED;
+    const float *const dZ = up.dZ; const int Kpool = up.Kpool;
+    if (!on || P < min_rows || x_affine == nullptr || up.ldy != round4(M) || ldx != round4(N)) return PN2_EUNSUPPORTED;
     if (!dZ && (Kpool <= 0 || P % Kpool != 0)) return PN2_EUNSUPPORTED;
-    if (dZ && ldz != ldy) return PN2_EUNSUPPORTED;                 // (one lane offset serves Y and dZ)
+    if (dZ && up.ldz != up.ldy) return PN2_EUNSUPPORTED;           // (one lane offset serves Y and dZ)
     WgradArgs g{};
-    g.Y = Y; g.ldy = ldy; g.dZ = dZ; g.ldz = ldz; g.dZp = dZp; g.arg = arg; g.ldo = ldo; g.coef = coef; g.X = X; g.ldx = ldx;
-    g.x_aff = x_affine; g.dW = dW; g.lddw = lddw; g.dbias = dbias; g.P = P; g.M = M; g.N = N; g.lc = lc; g.ws = workspace;
+    fill_dz(g, up); g.Y = up.Y; g.ldy = up.ldy; g.coef = up.coef; g.X = X; g.ldx = ldx;
+    g.x_aff = x_affine; g.dW = dW; g.lddw = lddw; g.dbias = dbias; g.P = P; g.M = M; g.N = N; g.lc = up.lc; g.ws = workspace;
     if (pn2_opt(PN2_OPT_SPLIT) && pn2_opt(PN2_OPT_SPLIT_WGRAD) && dbias == nullptr && P % 16 == 0) {
 #define SPLIT_WGRAD(MM, NN, TNW, PKP, BP)                                                                                \
         if (M == MM && N == NN && P % BP == 0 && (PKP == 0 ? dZ != nullptr : (dZ == nullptr && Kpool == PKP)))          \

@@ -7,13 +7,9 @@
 //     out5 = bn5(conv5(.)) (no ReLU) is never stored: the loader applies bn5 to the saved pre-BN rows.
 // Here: the data gradient into per-source outputs, and the backward reduction of bn5, whose output feeds both the max over the
 // cloud (out_max) and convs1 (dense).
-#include "pn2_common.h"
-#include "bn_affine.h"
-#include "mlp_loaders.h"
+#include "mlp_host.h"
 
 namespace {
-
-inline int round4(int x) { return (x + 3) & ~3; }
 
 // dZ[g K + k, c] = dDense[g K + k, c] + (k == arg[g, c] ? dPool[g, c] : 0); red += sum dZ, sum dZ * yhat (yhat = (y - mean) * invstd).
 // A thread owns one column quad and walks the rows q, q + 4, ... of its workgroup's row range (group / position advanced
