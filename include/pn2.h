@@ -1060,6 +1060,72 @@ int pn2_sample_image(const int32_t *pix, const uint8_t *image, int B, int H, int
  * channel_order, a null pointer with N > 0. */
 int pn2_hsv_to_rgb(const float *hsv, int ld, int64_t N, int channel_order, uint8_t *out, pn2_stream_t stream);
 
+/* ---- panoptic quality: PQ / SQ / RQ counts of instance labels (csrc/panoptic.hip), added within ABI 15 (additive) ---------------------
+ * Scores what pn2_voxel_components-style instance ids are worth against a ground truth: per class the matched segments (tp), the
+ * unmatched predicted and ground-truth segments (fp, fn) and the sum of the matches' IoU.  THE RULE IS WRITTEN FROM MEMORY OF THE
+ * SEMANTICKITTI API'S PanopticEval (addBatchPanoptic, getPQ) AND IS UNVERIFIED AGAINST THE API, which was not available where this was
+ * written.  tests/panoptic_ref.py states it in numpy, np.unique per class and side, as the API writes it.
+ * Inputs, B clouds in pn2_scan_filter's conventions (device-side row_begin / row_count int64[B], a host bound max_rows; every count is
+ * read on the device and clamped to [0, max_rows], rows at or beyond a count are never read, so a captured call stays valid when the
+ * counts change):
+ *   pred_sem, pred_inst, gt_sem, gt_inst   int32[rows] each; cloud b is rows [row_begin[b], row_begin[b] + row_count[b]);
+ *   rows        host: how many rows the four arrays hold (rows >= max_rows).  A cloud whose rows would leave [0, rows) is skipped WHOLE
+ *               (nothing of it is read, it adds nothing) and sets PN2_PANOPTIC_ERR_ROWS;
+ *   C           classes;   include  int32[C] (device): non-zero = the class is evaluated;
+ *   things      int32[C] (device) or NULL.  Where it is given and zero, the instance id of that class counts as 0 on BOTH sides (applied
+ *               before rule 5's sign test): one segment per stuff class, what the API's driver script does before it calls the evaluator;
+ *   min_points  int32 >= 0 (the API uses 30).
+ * Which rows take part:
+ *    1. a row takes part iff 0 <= gt_sem < C and include[gt_sem] != 0.  Any other row is dropped from BOTH sides: the API's removal of
+ *       ignored ground-truth rows, which shrinks the predicted segments too;
+ *    2. a gt_sem outside [0, C) also sets PN2_PANOPTIC_ERR_CLASS.
+ * Segments:
+ *    3. a participating row belongs to the ground-truth segment (cloud, gt_sem, gt_inst) if gt_inst >= 0;
+ *    4. and to the predicted segment (cloud, pred_sem, pred_inst) if pred_inst >= 0, 0 <= pred_sem < C and include[pred_sem] != 0;
+ *    5. a negative id: the row has no segment on that side (the API adds 1 and masks out 0);
+ *    6. the same id under two classes is two segments; clouds never share segments;
+ *    7. a segment's area is its row count.
+ * Matching:
+ *    8. the intersection of a ground-truth and a predicted segment of the SAME class in the same cloud is the number of rows in both;
+ *       union = area_gt + area_pred - inter;
+ *    9. the pair is a match iff 2 * inter > union, in integers (= the API's inter / union > 0.5 in fp64 for every union < 2^31);
+ *   10. a segment has at most one match (two disjoint overlaps cannot both exceed half of it).
+ * Counts, per class:  11. tp = matches;  12. fn = ground-truth segments with area >= min_points and no match;  13. fp = predicted
+ *   segments with area >= min_points and no match.
+ * IoU sum, per class:
+ *   14. for each match q = double(inter) / double(union), ONE IEEE fp64 division: the API's iou, bit for bit;
+ *   15. t = q * 2^53 is an exact integer in (2^52, 2^53];
+ *   16. the table accumulates iou_hi += t >> 32 and iou_lo += t & 0xFFFFFFFF as int64;
+ *   17. the class's IoU sum is the integer S = iou_hi * 2^32 + iou_lo over 2^53, taken on the host as one correctly rounded division.
+ * A stated deviation: the API adds the q in fp64, scan by scan; here the sum is exact and rounded once.  The two differ by at most
+ *   n_tp * 2^-52 * sum (all terms are positive; each of at most n_tp additions errs by at most 2^-53 of a partial sum that is at most
+ *   the total; the factor 2 covers second-order terms).
+ * The scores are the host's (fp64, the API's eps = 1e-15): sq = iou / max(tp, eps), rq = tp / max(tp + 0.5 fp + 0.5 fn, eps),
+ *   pq = sq * rq, means over the included classes (pointnet12_amd/metrics.py: panoptic_scores).
+ * table (int64, 8-byte aligned): [C, 5] with table_stride == 0 (pooled over the clouds), or cloud b's [C, 5] at table + b * table_stride
+ *   (table_stride >= 5 * C); columns tp, fp, fn, iou_hi, iou_lo.  The call ADDS into it; the caller zeroes it: an evaluation pass
+ *   accumulates on the device and reads back once.  Rows of excluded classes stay as they were.
+ * Four plain launches on the caller's stream sized by max_rows; no host synchronisation, no allocation, no thread waits for another
+ * thread's write.  Everything that crosses threads is an integer atomic (compare-and-swap, add): the table is the same from run to
+ * run, byte for byte, whatever the order of the rows.
+ * err (device int, caller zeroes, may be NULL) receives bits disjoint from every other PN2_*_ERR_* bit:
+ *   PN2_PANOPTIC_ERR_CLASS  a gt_sem outside [0, C): the row is dropped;
+ *   PN2_PANOPTIC_ERR_ROWS   a cloud whose row_begin / row_count leaves the buffers: skipped whole.
+ * workspace: pn2_panoptic_workspace_bytes(B, max_rows) bytes of device memory, 16-byte aligned; it may hold anything on entry (per
+ * cloud three tables of the power of two >= 2 * max_rows slots of 16 bytes: ground-truth segments, predicted segments, pairs).
+ * PN2_EINVAL without a launch, no output touched: a null required pointer (all but things and err), C < 1, B < 1 or B > 65535,
+ * max_rows < 0 or > PN2_VOXEL_MAX_ROWS, rows < max_rows, min_points < 0, a table_stride in (0, 5 * C), a pointer that is not 4-byte
+ * (row_begin / row_count / table: 8-byte, workspace: 16-byte) aligned; pn2_panoptic_workspace_bytes returns PN2_EINVAL for such
+ * B / max_rows.  Out of scope: PQ-dagger, the API's semantic-IoU half (pn2_seg_confusion serves it), tracking metrics, a matching
+ * threshold other than 0.5, more than 2^31 - 1 ids or classes. */
+#define PN2_PANOPTIC_ERR_CLASS 256
+#define PN2_PANOPTIC_ERR_ROWS 512
+int64_t pn2_panoptic_workspace_bytes(int B, int64_t max_rows);
+int pn2_panoptic_count(const int32_t *pred_sem, const int32_t *pred_inst, const int32_t *gt_sem, const int32_t *gt_inst,
+                       const int64_t *row_begin, const int64_t *row_count, int B, int64_t max_rows, int64_t rows, int C,
+                       const int32_t *include, const int32_t *things, int min_points, int64_t *table, int64_t table_stride, int *err,
+                       void *workspace, pn2_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

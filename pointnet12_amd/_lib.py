@@ -123,6 +123,8 @@ SIGNATURES = {
     "pn2_voxel_components_workspace_bytes": (_i64, [_i, _i64]),
     "pn2_voxel_components": (_i, [_vp, _i, _vp, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp,
                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pn2_panoptic_workspace_bytes": (_i64, [_i, _i64]),
+    "pn2_panoptic_count": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _i, _vp, _vp, _i, _vp, _i64, _vp, _vp, _vp]),
 }
 
 
@@ -143,6 +145,7 @@ VOXEL_ERR_RANGE, VOXEL_ERR_ROWS = 1, 2   # PN2_VOXEL_ERR_* of include/pn2.h
 SEGMENT_MAX_COLS = 16    # PN2_SEGMENT_MAX_COLS: the widest pn2_segment_mean / pn2_segment_mean_bwd call
 SEGMENT_ERR_RANGE, SEGMENT_ERR_NONFINITE = 4, 8      # PN2_SEGMENT_ERR_* (disjoint from VOXEL_ERR_*: they share VoxelGrid.error_flag)
 CLUSTER_ERR_INDEX, CLUSTER_ERR_CELL, CLUSTER_ERR_CAP, CLUSTER_ERR_ROWS = 16, 32, 64, 128     # PN2_CLUSTER_ERR_* (disjoint from both)
+PANOPTIC_ERR_CLASS, PANOPTIC_ERR_ROWS = 256, 512     # PN2_PANOPTIC_ERR_* (disjoint from all of the above)
 
 
 class BnLazy(ctypes.Structure):
@@ -201,7 +204,8 @@ class _Timed:
                                                    "pn2_ball_query_workspace_bytes", "pn2_point_transform_workspace_bytes",
                                                    "pn2_group_colsum_workspace_bytes", "pn2_chamfer_nn_workspace_bytes",
                                                    "pn2_scan_filter_workspace_bytes", "pn2_voxel_grid_workspace_bytes",
-                                                   "pn2_segment_reduce_workspace_bytes", "pn2_voxel_components_workspace_bytes"):
+                                                   "pn2_segment_reduce_workspace_bytes", "pn2_voxel_components_workspace_bytes",
+                                                   "pn2_panoptic_workspace_bytes"):
             return fn
 
         def timed(*args):

@@ -242,6 +242,23 @@ def write_labels(fn, labels, instances=None):
     words.astype("<u4").tofile(fn)
 
 
+def split_label_words(words, device=None):
+    """``.label`` words -> ``(semantic, instance)`` int32 tensors on ``device``: the low and the high 16 bits, the inverse of what
+    ``write_labels`` packs.  ``words``: a uint32 (or int32: the same bits) array or tensor of any shape; ``device`` None: a tensor's
+    own device, the GPU for an array.  A few elementwise device operations, nothing is read back."""
+    if isinstance(words, torch.Tensor):
+        if words.element_size() != 4 or words.is_floating_point():
+            raise ValueError("split_label_words: the words must be 32-bit integers (got %s)" % words.dtype)
+        w = words.reshape(-1).contiguous().view(torch.int32)
+        w = w if device is None else w.to(device)
+    else:
+        arr = np.ascontiguousarray(words).reshape(-1)
+        if arr.dtype.kind not in "iu" or arr.dtype.itemsize != 4:
+            raise ValueError("split_label_words: the words must be 32-bit integers (got %s)" % arr.dtype)
+        w = _upload_words(arr, "cuda" if device is None else device)
+    return w & 0xFFFF, (w >> 16) & 0xFFFF                                # (an arithmetic shift: the mask drops the copies of the sign)
+
+
 def _upload_words(words, device):
     return torch.from_numpy(np.ascontiguousarray(words).view(np.int32)).to(device)     # the same 32 bits (torch has no uint32 math)
 

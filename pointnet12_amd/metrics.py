@@ -343,3 +343,240 @@ def test_kitti_semseg(model, loader, model_name, num_classes, class_names):
     acc = np.mean(accuracy)
     miou = np.mean(categorical_iou[1:])
     return acc, miou
+
+
+# ----------------------------------------------------------------------------------------------- panoptic quality (csrc/panoptic.hip)
+# PQ / SQ / RQ of instance labels (``VoxelGrid.components``, ``label_scan(..., instances=)``) against a ground truth.  The rule is the
+# one of include/pn2.h ("panoptic quality"): WRITTEN FROM MEMORY OF THE SEMANTICKITTI API'S ``PanopticEval`` AND UNVERIFIED AGAINST IT.
+# ``pn2_panoptic_count`` adds per class the integers tp, fp, fn and the two halves of the exact IoU sum into a table on the device;
+# ``panoptic_scores`` does the API's few divisions on the host.  One stated deviation: the API adds the IoUs in fp64 scan by scan, here
+# the sum is exact and rounded once (they differ by at most ``tp * 2^-52`` of the sum).
+PANOPTIC_COLUMNS = ("tp", "fp", "fn", "iou_hi", "iou_lo")
+_PANOPTIC_EPS = 1e-15                                                    # the API's
+_panoptic_const = {}                                                     # (what, device, ...) -> a small constant device tensor
+
+
+def _const(key, make):
+    t = _panoptic_const.get(key)
+    if t is None:
+        t = _panoptic_const[key] = make()
+    return t
+
+
+def _class_mask(mask, C, device, what):
+    """None -> None; an int32 ``[C]`` device tensor as it is; anything else (a list, a bool tensor) uploaded as one."""
+    if mask is None:
+        return None
+    if isinstance(mask, torch.Tensor) and mask.dtype == torch.int32 and mask.device == device and mask.is_contiguous():
+        m = mask
+    else:
+        m = torch.as_tensor(np.asarray(mask.cpu() if isinstance(mask, torch.Tensor) else mask).astype(np.int32)).to(device)
+    if m.dim() != 1 or m.numel() != C:
+        raise ValueError("panoptic_counts: %s must have one entry per class (%d), got %s" % (what, C, tuple(m.shape)))
+    return m
+
+
+def panoptic_workspace(B, max_rows, device="cuda"):
+    """The ``work=`` buffer of ``panoptic_counts`` for calls of ``B`` clouds of at most ``max_rows`` rows each."""
+    nbytes = _lib.load().pn2_panoptic_workspace_bytes(int(B), int(max_rows))
+    if nbytes < 0:
+        raise _lib.Pn2Error("panoptic_workspace: B = %d, max_rows = %d are not supported" % (B, max_rows))
+    return torch.empty(max(int(nbytes), 16), device=device, dtype=torch.uint8)
+
+
+def panoptic_counts(pred_sem, pred_inst, gt_sem, gt_inst, num_classes, include=None, things=None, min_points=30, row_begin=None,
+                    row_count=None, max_rows=None, per_cloud=False, out=None, err=None, work=None):
+    """The panoptic table of predicted ``(pred_sem, pred_inst)`` against ``(gt_sem, gt_inst)``: int64 ``[C, 5]`` pooled over the
+    clouds, ``[B, C, 5]`` with ``per_cloud``; columns ``tp, fp, fn, iou_hi, iou_lo`` (``panoptic_scores`` reads them).
+
+    The four inputs are integer device tensors of one shape: ``[N]`` (one cloud), ``[B, N]`` (B clouds), or flat with
+    ``row_begin`` / ``row_count`` (int64 ``[B]`` DEVICE tensors, clouds back to back as ``ScanFilter.filter`` takes them; ``max_rows``:
+    a host bound of every count, None: all rows).  A negative instance id means "no segment"; ``include`` (``[C]``, None: every
+    class) names the evaluated classes -- a row whose ``gt_sem`` is excluded leaves BOTH sides -- and ``things`` (``[C]`` or None)
+    the classes whose ids count; the ids of the others are taken as 0, one segment per stuff class.  A ``gt_sem`` outside ``[0, C)``
+    drops the row and sets ``_lib.PANOPTIC_ERR_CLASS`` in ``err`` (int32 ``[1]`` device tensor, caller zeroes, may be None); a cloud
+    whose rows leave the tensors is skipped whole (``PANOPTIC_ERR_ROWS``).
+
+    The counts are ADDED into ``out``.  With int32 inputs, ``out=``, ``work=`` (``panoptic_workspace``) and int32 device masks the call
+    allocates nothing and reads nothing back: it can be captured in a graph, and a captured call stays valid when the content of
+    ``row_count`` changes.  The table is the same from run to run and under any permutation of a cloud's rows, byte for byte."""
+    tensors = (pred_sem, pred_inst, gt_sem, gt_inst)
+    for t in tensors:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.Pn2Error("panoptic_counts: the labels must live on the GPU: this package has no CPU path")
+        if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+            raise RuntimeError("panoptic_counts: the labels must have an integer dtype (got %s)" % t.dtype)
+        if t.shape != gt_sem.shape:
+            raise ValueError("panoptic_counts: the four label tensors must have one shape")
+    C, dev = int(num_classes), gt_sem.device
+    if C < 1:
+        raise ValueError("panoptic_counts: num_classes = %d" % C)
+    if (row_begin is None) != (row_count is None):
+        raise ValueError("panoptic_counts: row_begin and row_count go together")
+    rows = int(gt_sem.numel())
+    if row_begin is not None:
+        if gt_sem.dim() != 1:
+            raise ValueError("panoptic_counts: with row_begin / row_count the labels are flat [rows] tensors")
+        B = int(row_begin.numel())
+        for t in (row_begin, row_count):
+            if not t.is_cuda or t.dtype != torch.int64 or t.numel() != B or not t.is_contiguous():
+                raise ValueError("panoptic_counts: row_begin and row_count must be int64 [B] device tensors")
+        max_rows = rows if max_rows is None else int(max_rows)
+    elif gt_sem.dim() == 2:
+        B, N = int(gt_sem.shape[0]), int(gt_sem.shape[1])
+        row_begin = _const(("begin", dev, B, N), lambda: torch.arange(B, device=dev, dtype=torch.int64) * N)
+        row_count = _const(("count", dev, B, N), lambda: torch.full((B,), N, device=dev, dtype=torch.int64))
+        max_rows = N
+    elif gt_sem.dim() == 1:
+        B = 1
+        row_begin = _const(("begin", dev, 1, rows), lambda: torch.zeros(1, device=dev, dtype=torch.int64))
+        row_count = _const(("count", dev, 1, rows), lambda: torch.full((1,), rows, device=dev, dtype=torch.int64))
+        max_rows = rows
+    else:
+        raise ValueError("panoptic_counts: labels must be [N], [B, N] or flat with row_begin / row_count, got %s" % (tuple(gt_sem.shape),))
+    shape = (B, C, 5) if per_cloud else (C, 5)
+    if out is None:
+        out = torch.zeros(shape, device=dev, dtype=torch.int64)
+    elif out.dtype != torch.int64 or out.device != dev or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError("panoptic_counts: out must be a contiguous int64 %s tensor on %s" % (shape, dev))
+    if B == 0:
+        return out
+    flat = [t.detach().reshape(-1).to(torch.int32).contiguous() for t in tensors]       # (int32 contiguous tensors pass as they are)
+    include = _const(("ones", dev, C), lambda: torch.ones(C, device=dev, dtype=torch.int32)) if include is None else \
+        _class_mask(include, C, dev, "include")
+    things = _class_mask(things, C, dev, "things")
+    if err is not None and (err.dtype != torch.int32 or err.device != dev or err.numel() < 1):
+        raise ValueError("panoptic_counts: err must be an int32 device tensor")
+    lib = _lib.load()
+    need = lib.pn2_panoptic_workspace_bytes(B, max_rows)
+    if need < 0:
+        raise _lib.Pn2Error("panoptic_counts: B = %d, max_rows = %d are not supported" % (B, max_rows))
+    if work is None:
+        work = panoptic_workspace(B, max_rows, dev)
+    elif work.dtype != torch.uint8 or work.device != dev or work.numel() < need or not work.is_contiguous():
+        raise ValueError("panoptic_counts: work must be a uint8 device tensor of at least %d bytes (panoptic_workspace)" % need)
+    _check(lib.pn2_panoptic_count(_p(flat[0]), _p(flat[1]), _p(flat[2]), _p(flat[3]), _p(row_begin), _p(row_count), B, max_rows, rows, C,
+                                  _p(include), _p(things), int(min_points), _p(out), 5 * C if per_cloud else 0, _p(err), _p(work),
+                                  _lib.stream()), "pn2_panoptic_count")
+    return out
+
+
+def panoptic_scores(table, include=None):
+    """The scores of a panoptic table (tensor or array ``[C, 5]``; leading axes -- clouds, updates -- are summed first), on the host
+    in fp64 with the API's ``eps = 1e-15``: ``sq = iou / max(tp, eps)``, ``rq = tp / max(tp + 0.5 fp + 0.5 fn, eps)``,
+    ``pq = sq * rq``, and their means over the included classes (``include``: ``[C]``, None: all).  Returns a dict with ``pq``,
+    ``sq``, ``rq``, ``pq_per_class``, ``sq_per_class``, ``rq_per_class``, ``tp``, ``fp``, ``fn`` (int64 ``[C]``) and ``iou_sum``
+    (fp64 ``[C]``): per class the integer ``iou_hi * 2^32 + iou_lo`` over ``2^53``, one correctly rounded division of the EXACT sum of
+    the matches' fp64 IoUs."""
+    t = table.detach().cpu().numpy() if isinstance(table, torch.Tensor) else np.asarray(table)
+    if t.ndim < 2 or t.shape[-1] != 5:
+        raise ValueError("panoptic_scores: the table must be [..., C, 5], got %s" % (t.shape,))
+    t = t.astype(np.int64).reshape(-1, t.shape[-2], 5)
+    C = t.shape[1]
+    totals = [[sum(int(v) for v in t[:, c, k]) for k in range(5)] for c in range(C)]       # Python integers: no overflow, no order
+    tp, fp, fn = (np.array([r[k] for r in totals], np.int64) for k in range(3))
+    iou = np.array([((r[3] << 32) + r[4]) / (1 << 53) for r in totals], np.float64)          # int / int: correctly rounded
+    inc = np.ones(C, bool) if include is None else \
+        np.asarray(include.cpu() if isinstance(include, torch.Tensor) else include).reshape(-1) != 0
+    if inc.shape[0] != C:
+        raise ValueError("panoptic_scores: include must have one entry per class (%d)" % C)
+    tpf, fpf, fnf = tp.astype(np.float64), fp.astype(np.float64), fn.astype(np.float64)
+    sq = iou / np.maximum(tpf, _PANOPTIC_EPS)
+    rq = tpf / np.maximum(tpf + 0.5 * fpf + 0.5 * fnf, _PANOPTIC_EPS)
+    pq = sq * rq
+    mean = lambda v: float(v[inc].mean()) if inc.any() else 0.0
+    return {"pq": mean(pq), "sq": mean(sq), "rq": mean(rq), "pq_per_class": pq, "sq_per_class": sq, "rq_per_class": rq,
+            "tp": tp, "fp": fp, "fn": fn, "iou_sum": iou}
+
+
+class PanopticEvaluator:
+    """The panoptic table of one evaluation pass, kept on the device (modelled on ``SegEvaluator``): every ``update`` ADDS a batch's
+    counts into it -- with ``per_cloud`` each cloud gets a table of its own on a tape that grows by doubling -- and ``tables()``
+    reads it back, the only synchronisation of the pass: int64 ``[C, 5]``, or ``[clouds, C, 5]``.  ``scores()`` is
+    ``panoptic_scores`` of that.  ``error_flag`` (device int32) collects ``_lib.PANOPTIC_ERR_*`` over the pass; ``check()`` reads it
+    back and raises."""
+
+    def __init__(self, num_classes, include=None, things=None, min_points=30, per_cloud=False, device="cuda"):
+        self.num_classes = int(num_classes)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.Pn2Error("PanopticEvaluator: the HIP device is the only implementation")
+        C = self.num_classes
+        self.include = torch.ones(C, device=self.device, dtype=torch.int32) if include is None else \
+            _class_mask(include, C, self.device, "include")
+        self.things = _class_mask(things, C, self.device, "things")
+        self.min_points = int(min_points)
+        self.per_cloud = bool(per_cloud)
+        self.error_flag = torch.zeros(1, device=self.device, dtype=torch.int32)
+        self.batches = []                                            # (first slot, slots, rows) per update
+        self._tape = torch.zeros(16 if self.per_cloud else 1, C, 5, device=self.device, dtype=torch.int64)
+        self._used = 0 if self.per_cloud else 1
+        self._work = None
+
+    def _reserve(self, k):
+        while self._used + k > self._tape.shape[0]:
+            grown = torch.zeros(2 * self._tape.shape[0], self.num_classes, 5, device=self.device, dtype=torch.int64)
+            grown[:self._used] = self._tape[:self._used]
+            self._tape = grown
+        return self._tape[self._used:self._used + k]
+
+    def update(self, pred_sem, pred_inst, gt_sem, gt_inst, row_begin=None, row_count=None, max_rows=None):
+        """One batch in any of ``panoptic_counts``' input shapes."""
+        if row_begin is not None:
+            B, bound = int(row_begin.numel()), int(gt_sem.numel()) if max_rows is None else int(max_rows)
+        elif gt_sem.dim() == 2:
+            B, bound = int(gt_sem.shape[0]), int(gt_sem.shape[1])
+        else:
+            B, bound = 1, int(gt_sem.numel())
+        need = _lib.load().pn2_panoptic_workspace_bytes(B, bound)
+        if need < 0:
+            raise _lib.Pn2Error("PanopticEvaluator.update: B = %d, max_rows = %d are not supported" % (B, bound))
+        if self._work is None or self._work.numel() < need:
+            self._work = panoptic_workspace(B, bound, self.device)
+        slot = self._reserve(B) if self.per_cloud else self._tape[0]
+        if B > 0:
+            panoptic_counts(pred_sem, pred_inst, gt_sem, gt_inst, self.num_classes, self.include, self.things, self.min_points,
+                            row_begin, row_count, max_rows, per_cloud=self.per_cloud, out=slot, err=self.error_flag, work=self._work)
+        if self.per_cloud:
+            self.batches.append((self._used, B, int(gt_sem.numel())))
+            self._used += B
+        else:
+            self.batches.append((0, 1, int(gt_sem.numel())))
+
+    def update_scan(self, scan_labels, scan_instances, gt_words, learning_map, labels_are_raw=True):
+        """One scan as ``FrameSegmenter.label_scan(..., instances=)`` leaves it against its ``.label`` file.  ``scan_labels`` /
+        ``scan_instances``: the result's entries of those names (``scan_instances`` holds ``id + 1`` and 0 for "none", which becomes
+        id -1 here); ``gt_words``: the ground truth's uint32 words (array or 32-bit tensor, ``kitti.split_label_words`` splits them);
+        ``learning_map``: int32 DEVICE look-up table raw id -> class of this evaluator, -1 where the map has none (``ScanFilter.lut``).
+        Both semantic halves go through it (``labels_are_raw=False``: ``scan_labels`` already holds this evaluator's classes).  A raw
+        id outside the table becomes class -1: the row is dropped and ``error_flag`` gets ``PANOPTIC_ERR_CLASS``."""
+        from . import kitti
+        gt_raw, gt_inst = kitti.split_label_words(gt_words, self.device)
+        lut = learning_map.to(device=self.device, dtype=torch.int32)
+
+        def mapped(raw):
+            raw = raw.to(torch.int64)
+            inside = (raw >= 0) & (raw < lut.numel())
+            return torch.where(inside, lut[raw.clamp(0, lut.numel() - 1)], -1).to(torch.int32)
+
+        pred_sem = mapped(scan_labels.reshape(-1)) if labels_are_raw else scan_labels.reshape(-1).to(torch.int32)
+        pred_inst = scan_instances.reshape(-1).to(torch.int32) - 1
+        if pred_sem.numel() != gt_raw.numel():
+            raise ValueError("update_scan: %d predicted rows, %d ground-truth words" % (pred_sem.numel(), gt_raw.numel()))
+        self.update(pred_sem, pred_inst, mapped(gt_raw), gt_inst)
+
+    def tables(self):
+        t = self._tape[:self._used].cpu().numpy()
+        return t if self.per_cloud else t[0]
+
+    def scores(self):
+        return panoptic_scores(self.tables(), self.include)
+
+    def check(self):
+        """Reads ``error_flag`` back: ``KeyError`` for a ground-truth class outside ``[0, C)``, ``ValueError`` for a cloud whose
+        rows left the tensors."""
+        flag = int(self.error_flag.item())
+        if flag & _lib.PANOPTIC_ERR_CLASS:
+            raise KeyError("a ground-truth class lies outside [0, num_classes)")
+        if flag & _lib.PANOPTIC_ERR_ROWS:
+            raise ValueError("PanopticEvaluator: a cloud's row_begin / row_count leaves the label tensors")
