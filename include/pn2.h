@@ -346,8 +346,10 @@ int pn2_conv1x1_wgrad_ws(const float *dZ, int ldz, const float *dZp, int ldo, co
  * and the input rows alone (ABI 9).  The BatchNorm-backward terms of dY = c0*dZ + q1*(y - mean) + q0 (model/pointnet_util.py:195-197,
  * backward) are linear in sums the forward already fixed: with s = sum_p x_p, S = sum_p x_p x_p^T and y_p = W x_p + b,
  *     dW[c][j] += c0[c] * sum_p dZ[p,c] x[p,j] + q1[c] * ((W S)[c][j] + (b[c] - mean[c]) * s[j]) + q0[c] * s[j]
- * -- Y is never read (half the bytes of pn2_conv1x1_wgrad on these layers); s and S are accumulated by the same pass (fp64 across
- * workgroups) and the closed-form part is added once, by the workgroup that finishes last.  `coef` as for pn2_conv1x1_wgrad
+ * -- Y is never read (half the bytes of pn2_conv1x1_wgrad on these layers); s and S are accumulated by the same pass, in fp64 from
+ * the first product on (the mean of x cancels between W S and (b - mean) s^T: an error of S is amplified by mean^2 / variance of
+ * the input columns), and the closed-form part is added once, by the workgroup that finishes last.  Only the columns [0, N) of X,
+ * W and dW and [0, M) of dZ are touched, whatever the pitches hold behind them.  `coef` as for pn2_conv1x1_wgrad
  * (rows c0, q1, q0, mean of pitch round4(M); realised from `coef_lazy` when given); W [M, N] (pitch ldw) and bias [M] are the
  * layer's parameters; `scratch`: pn2_conv1x1_wgrad_cf_scratch_bytes() bytes, 16-byte aligned, ZEROED by the caller (left dirty).
  * dZ == NULL (ABI 11): sum_p dZ[p,c] x[p,j] is already in `scratch` -- pn2_conv1x1_bwd_first of the NEXT layer added it there --
@@ -380,7 +382,10 @@ int pn2_conv1x1_bwd_pair(const float *dZ, int ldz, const float *dZp, int ldo, co
  * 4 P (2 C_in) bytes instead of 4 P (C_out + 2 C_in), and the forward writes no Y (pn2_conv1x1_fwd_pool with Y == NULL).
  * Partial products leave as one slab per workgroup and are summed in a fixed order: dW is run-to-run identical.
  * bias: the conv bias [C_out].  scratch: pn2_conv1x1_bwd_cf_scratch_bytes(C_out, C_in) bytes, 256-byte aligned, contents need
- * not be initialised.  Training-mode BatchNorm, prev_affine != NULL.  pn2_conv1x1_bwd_cf_supported(): 1 where the call runs
+ * not be initialised.  Of dZp / arg only the columns [0, C_out) are read, whatever the pitch ldo holds behind them (arg's pad may
+ * be garbage); dXout (pitch ldxo >= C_in, any) is written in [0, C_in) only.  Every row count P % Kpool == 0 from the threshold on
+ * is taken: one 32-row chunk per workgroup up to min(CUs, 256) workgroups, round-robin beyond.
+ * Training-mode BatchNorm, prev_affine != NULL.  pn2_conv1x1_bwd_cf_supported(): 1 where the call runs
  * (128 x 96 and 128 x 64 with Kpool a power of two >= 32, from pn2_res_supported()'s row count on, library options SPLIT /
  * SPLIT_RES / POOL_CF on); PN2_EUNSUPPORTED otherwise. */
 int pn2_conv1x1_bwd_cf_supported(int64_t P, int C_out, int C_in, int Kpool);
@@ -396,7 +401,8 @@ int pn2_conv1x1_bwd_cf(const float *dZp, int ldo, const int32_t *arg, int Kpool,
  * form) needs only sum_p dZ[p, c] X0[p, j] from it, which this call forms from its dX tiles and adds into THAT call's scratch
  * (cf_scratch: pn2_conv1x1_wgrad_cf_scratch_bytes() bytes, zeroed by the caller, then handed to pn2_conv1x1_wgrad_cf with
  * dZ == NULL) -- dX itself is never written.  dense dZ, prev_affine / prev_red required (training-mode BatchNorm), X0 16-byte
- * aligned with pitch ld0 >= 12, ld0 % 4 == 0 (pad columns zero).  prev_red receives the first layer's two reductions as in
+ * aligned with pitch ld0 >= 12, ld0 % 4 == 0 (pad columns zero: the columns [0, 12) of every row are read whatever N0 is, nothing
+ * behind them; the finishing pn2_conv1x1_wgrad_cf writes the columns [0, N0) of the first layer's dW).  prev_red receives the first layer's two reductions as in
  * pn2_conv1x1_bwd.  _supported(): 1 for 96 x 64 and 64 x 64 with P % 64 == 0 from pn2_res_supported()'s row count on (options
  * SPLIT, SPLIT_RES, FUSE_FIRST on); PN2_EUNSUPPORTED otherwise (call pn2_conv1x1_bwd). */
 int pn2_conv1x1_bwd_first_supported(int64_t P, int C_out, int C_in, int N0);

@@ -1618,11 +1618,16 @@ namespace {
 // forward already fixed: with s = sum_p x_p, S = sum_p x_p x_p^T and y_p = W x_p + b,
 //     dW[c][j] = c0[c] sum_p dZ[p,c] x[p,j]  +  q1[c] ((W S)[c][j] + (b[c] - mean[c]) s[j])  +  q0[c] s[j]
 // so Y is not read at all: 872 of the 962 MB per MSG-SemSeg step that the general skinny kernel moved for sa1's three first
-// layers were dZ + Y.  Both sums are v_mfma_f32_16x16x4_f32 products straight from the loaded registers (lane = 16 k + n holds
+// layers were dZ + Y.  Both sums are 16 x 16 x 4 MFMA products straight from the loaded registers (lane = 16 k + n holds
 // dZ[p0 + k][c0 + n] resp. x[p0 + k][n]: the A operand of S = X^T X is the SAME register as its B operand), column 15 of the
-// row operand is a constant 1, so S[15][j] = s[j]; the S partials leave the fp32 accumulators for fp64 every 64 rows.  The
-// closed-form part needs the COMPLETE moments: the workgroup that draws the last ticket adds it, once, in fp64.
+// row operand is a constant 1, so S[15][j] = s[j].  The moments are accumulated in fp64 from the first product on
+// (v_mfma_f64_16x16x4_f64 on the converted register: a product of two floats is exact there): in q1 (W S + (b - mean) s^T) the
+// mean of the input cancels, P mean mean^T against the (b - mean) s^T term, so an error of S is amplified by mean^2 / variance
+// of the input columns -- with float32 accumulators flushed every 64 rows that error alone put dW at 4.1e-6 of its largest
+// entry on a self-consistent BatchNorm block (tests/test_mlp_cf_seams_gpu.py, 80 x 3 on 511 rows).  The closed-form part
+// needs the COMPLETE moments: the workgroup that draws the last ticket adds it, once, in fp64.
 typedef float cf_f32x4 __attribute__((ext_vector_type(4)));
+typedef double cf_f64x4 __attribute__((ext_vector_type(4)));
 
 constexpr int CF_REPL = PN2_CF_REPL;                              // scratch replicas: 1 / 8 of the workgroups add into each
 
@@ -1644,13 +1649,12 @@ __global__ __launch_bounds__(256) void wgrad_first_cf_kernel(const float *__rest
     const bool xin = n < N;
     const float fill = n == 15 ? 1.f : 0.f;
     const int nc = xin ? n : 0;                                   // pad lanes re-read column 0 (replaced by `fill`): never past a row
-    cf_f32x4 acc[NB], sacc = {0.f, 0.f, 0.f, 0.f};
-    double sd[4] = {0.0, 0.0, 0.0, 0.0};
+    cf_f32x4 acc[NB];
+    cf_f64x4 sd = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int b = 0; b < NB; ++b) acc[b] = cf_f32x4{0.f, 0.f, 0.f, 0.f};
     const int64_t groups = (P + 3) >> 2;                          // 4 rows per MFMA
     const int64_t stride = (int64_t)gridDim.x * 4 * U;
-    int rows64 = 0;
     // Whole trips (U groups of 4 rows, all inside P) address everything as a WAVE-UNIFORM base (scalar arithmetic) plus one
     // loop-invariant 32-bit lane offset per operand; only the last, ragged trip of the launch checks rows per lane.
     const unsigned lo_z = (unsigned)k * (unsigned)ldz + (unsigned)(NB * n), lo_x = (unsigned)k * (unsigned)ldx + (unsigned)nc;
@@ -1701,19 +1705,13 @@ __global__ __launch_bounds__(256) void wgrad_first_cf_kernel(const float *__rest
 #pragma unroll
                 for (int b = 0; b < NB; ++b) acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][b], x[u], acc[b], 0, 0, 0);
             }
-            sacc = __builtin_amdgcn_mfma_f32_16x16x4f32(x[u], x[u], sacc, 0, 0, 0);
-        }
-        rows64 += 4 * U;
-        if (rows64 >= 64) {                                       // the moment partials move to fp64 every 64 rows
-            rows64 = 0;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { sd[r] += (double)sacc[r]; sacc[r] = 0.f; }
+            const double xd = (double)x[u];
+            sd = __builtin_amdgcn_mfma_f64_16x16x4f64(xd, xd, sd, 0, 0, 0);
         }
     }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) sd[r] += (double)sacc[r];
-    // D[i][j] of a 16 x 16 tile sits in lane 16 (i / 4) + j, register i % 4: fold the four waves through LDS, then one set of
-    // atomics per workgroup into ITS replica of the scratch (CF_REPL replicas: 1 / 8 of the adders per address)
+    // D[i][j] of a 16 x 16 float tile sits in lane 16 (i / 4) + j, register i % 4 (the fp64 tile of the moments: lane
+    // 16 (i % 4) + j, register i / 4): fold the four waves through LDS, then one set of atomics per workgroup into ITS replica
+    // of the scratch (CF_REPL replicas: 1 / 8 of the adders per address)
 #pragma unroll
     for (int b = 0; b < NB; ++b)
 #pragma unroll
@@ -1728,7 +1726,7 @@ __global__ __launch_bounds__(256) void wgrad_first_cf_kernel(const float *__rest
         atomicAdd(part + (rep * M + NB * i + b) * 16 + j, fold[0][b][q] + fold[1][b][q] + fold[2][b][q] + fold[3][b][q]);
     }
     {
-        const int q = t, l2 = q >> 2, r = q & 3, i = 4 * (l2 >> 4) + r, j = l2 & 15;
+        const int q = t, l2 = q >> 2, r = q & 3, i = (l2 >> 4) + 4 * r, j = l2 & 15;          // (the fp64 tile's rows)
         if (j < N && (i < N || i == 15)) atomicAdd(mom + rep * 256 + i * 16 + j, sfold[0][q] + sfold[1][q] + sfold[2][q] + sfold[3][q]);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // this thread's atomics are performed (tail_is_last_block)

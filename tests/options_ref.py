@@ -63,6 +63,7 @@ _TN = _MLP + "::test_tn_options_on_the_streamed_weight_gradient"
 _WIDE = _MLP + "::test_wide_and_resident_options_at_their_row_thresholds"
 _TWO = _MLP + "::test_two_phase_weight_gradient_flush_through_caller_scratch"
 _SEAMS = "test_mlp_seams_gpu"
+_CF = "test_mlp_cf_seams_gpu"
 
 LEDGER = {
     # ---- csrc/geometry.hip
@@ -108,9 +109,12 @@ LEDGER = {
     "SPLIT_K256": [(0, _WIDE)],
     "SPLIT_NARROW": [(0, "test_mlp_gpu::test_pool_in_gemm_epilogue_equals_the_pooling_pass")],
     "SPLIT_RES": [(0, "test_mlp_gpu::test_bf16_split_kernels_against_the_fp32_pipe"), (2, _WIDE)],
-    "FUSE_FIRST": [("0 vs 1", "test_mlp_gpu::test_shared_mlp_with_the_fused_first_layer_option")],
+    "FUSE_FIRST": [("0 vs 1", "test_mlp_gpu::test_shared_mlp_with_the_fused_first_layer_option"),
+                   (1, _CF + "::test_fused_backward_with_the_first_layers_sums_at_its_seams")],
     "SPLIT_WG2": [(0, "test_geometry_gpu::test_fps_beside_the_pooled_split_forward_is_index_exact"), NOTE_GRID],
-    "POOL_CF": [(0, "test_mlp_gpu::test_fused_backward_kernel_vs_fp64_on_fixed_operands"), (2, "test_mlp_gpu::test_shared_mlp_negative_and_zero_gamma")],
+    "POOL_CF": [(0, "test_mlp_gpu::test_fused_backward_kernel_vs_fp64_on_fixed_operands"),
+                (1, _CF + "::test_pooled_backward_from_the_input_with_pool_cf_1_takes_128x96_only"),
+                (2, "test_mlp_gpu::test_shared_mlp_negative_and_zero_gamma"), (2, _CF + "::test_pooled_backward_from_the_input_at_its_seams")],
     "SPLIT_RES_MIN_TILES_128": ("threshold", _SEAMS + "::test_fused_backward_with_a_ragged_tail"),
     "SPLIT_MIN_ROWS_128": ("threshold", _SEAMS + "::test_forward_at_the_row_thresholds_and_ragged_tails"),
     "RING": "bit-equal pair tested in test_mlp_gpu::test_ring_forward_option_is_bit_equal",
