@@ -1132,6 +1132,55 @@ int pn2_panoptic_count(const int32_t *pred_sem, const int32_t *pred_inst, const 
                        const int32_t *include, const int32_t *things, int min_points, int64_t *table, int64_t table_stride, int *err,
                        void *workspace, pn2_stream_t stream);
 
+/* ---- Lovasz-Softmax loss: the surrogate of mean IoU (csrc/lovasz.hip), added within ABI 15 (additive) ---------------------------------
+ * Berman, Triki, Blaschko, "The Lovasz-Softmax loss", CVPR 2018.  The reference repository has no such criterion.  THE RULE IS WRITTEN
+ * FROM THE PAPER AND FROM MEMORY OF THE AUTHORS' PUBLISHED lovasz_softmax_flat / lovasz_grad AND IS UNVERIFIED AGAINST THAT CODE, which
+ * was not available where this was written.  tests/lovasz_ref.py states it in numpy; tests/test_lovasz_cpu.py holds it to an fp64 torch
+ * evaluation of the cumulative-sum formulation.
+ * Inputs: x float32, R rows of C <= 64 classes in pn2_cross_entropy_*'s two layouts (inner == 0: x[r * ld + c], ld >= C; inner > 0:
+ *   x[(r / inner) * C * inner + c * inner + r % inner]); target int64[R]; images >= 1 divides R: image b is rows [b * R / images,
+ *   (b + 1) * R / images) (with inner > 0 and images > 1, inner == R / images).
+ * Probabilities: from_logits != 0: p = softmax(x_r) exactly as pn2_cross_entropy_bwd recomputes it, expf((x - max) - logsum), logsum =
+ *   logf of the four-way interleaved sum of expf(x - max); log-probabilities are therefore a valid input.  from_logits == 0: p = x.
+ * Which rows take part: a row takes part iff target != ignore_index and 0 <= target < C; any other row takes no part, as if it had been
+ *   compacted away; an out-of-range target that is not ignore_index also turns the loss NaN (the contract of pn2_nll_loss_*).
+ * Segments: one per (image, class).  Segment (b, c) is counted iff (class_mask == NULL or class_mask[c] != 0) and (present_only == 0 or
+ *   the segment has at least one foreground row).
+ * Per segment, over its participating rows:
+ *    1. fg = [target == c];
+ *    2. e = fl32(|fg - p|), one float32 subtraction;
+ *    3. the rows are ordered by e descending, NaN the largest (every NaN equal), as torch.sort orders them;
+ *    4. EQUAL ERRORS COME IN ASCENDING ROW NUMBER (a stable sort; the authors' torch.sort leaves ties undefined);
+ *    5. with k the 1-based rank, F_k the foreground rows among the first k and G the segment's foreground count, all integers:
+ *         J_k = 1.0 - double(G - F_k) / double(G + k - F_k),  J_0 = 0,  c_k = J_k - J_{k-1}  in fp64
+ *       (bit for bit the authors' cumulative-sum form; c_k >= 0 and sum_k c_k <= 1);
+ *    6. the segment's loss is l = sum_k double(e_(k)) * c_k.
+ * Reduction: per image the mean of l over its counted segments (0 when none is counted), then the mean over ALL images.
+ * Gradients: dp[r, c] = float32((w * c_rank(r, c)) * sgn(p - fg)), w = 1.0 / (double(counted segments of the image) * double(images));
+ *   sgn(d) = (0 < d) - (d < 0): sgn(0) = 0 as torch.abs, and 0 for NaN; dp is 0 for rows and segments that take no part.
+ *   pn2_lovasz_bwd: dx[r, c] = g * (p_c * (dp_c - sum_j p_j * dp_j)) with from_logits (the sum in float32 in class order, p recomputed
+ *   as above), g * dp[r, c] otherwise; g = *grad_out is read on the device; dx is written in x's layout, pad columns are never touched.
+ * Outputs of pn2_lovasz_fwd: dp float[R, C] (dense); prob float[R, C] or NULL: the probabilities the forward used; loss: one float
+ *   (float32 of the fp64 mean: tile partials of 1024 elements, a segment's tiles, the classes and the images each summed in a fixed order).
+ * NaN, +inf and e > 1 are ordered per the rule (the sort takes all 32 key bits: four passes of 8), nothing is refused for its values.
+ * The forward is 17 plain launches on the caller's stream (keys; 4 x histogram / scan / scatter; foreground count / scan; finalise;
+ * reduce); no host synchronisation, no allocation, no workgroup waits on another, positions come from prefix sums of integer counts:
+ * the outputs are byte-identical from run to run.  pn2_lovasz_tile_rows() is the tile (elements of a segment per workgroup).
+ * workspace: pn2_lovasz_workspace_bytes(R, C, images) bytes of device memory, 16-byte aligned; it may hold anything on entry.  Two
+ *   key and two payload buffers of images * C * (R / images) words dominate it: 16 bytes per (row, class) plus 1 KiB of digit counts per
+ *   (segment, tile) -- 39 MB of buffers at 16 x 8 000 x 19, 243 MB at 16 x 50 000 x 19.
+ * PN2_EINVAL without a launch, no output touched: a null required pointer (all but class_mask and prob), R < 1, C < 1 or C > 64,
+ *   images < 1 or not a divisor of R, R / images >= 2^30, R * C >= 2^36, ld < C with inner == 0, inner < 0 or not a divisor of R,
+ *   inner > 0 and images > 1 with inner != R / images, a workspace that is not 16-byte aligned;  pn2_lovasz_workspace_bytes returns
+ *   PN2_EINVAL for such R / C / images.  Out of scope: the binary hinge, class weights, soft targets, fp16 / bf16 inputs. */
+int pn2_lovasz_tile_rows(void);
+int64_t pn2_lovasz_workspace_bytes(int64_t R, int C, int images);
+int pn2_lovasz_fwd(const float *x, int ld, int64_t inner, const int64_t *target, int64_t R, int C, int images, int64_t ignore_index,
+                   int from_logits, const int32_t *class_mask, int present_only, void *workspace, float *dp, float *prob, float *loss,
+                   pn2_stream_t stream);
+int pn2_lovasz_bwd(const float *x, int ld, int64_t inner, const float *dp, int64_t R, int C, int from_logits, const float *grad_out,
+                   float *dx, pn2_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

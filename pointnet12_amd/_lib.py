@@ -125,6 +125,10 @@ SIGNATURES = {
                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pn2_panoptic_workspace_bytes": (_i64, [_i, _i64]),
     "pn2_panoptic_count": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _i, _vp, _vp, _i, _vp, _i64, _vp, _vp, _vp]),
+    "pn2_lovasz_tile_rows": (_i, []),
+    "pn2_lovasz_workspace_bytes": (_i64, [_i64, _i, _i]),
+    "pn2_lovasz_fwd": (_i, [_vp, _i, _i64, _vp, _i64, _i, _i, _i64, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "pn2_lovasz_bwd": (_i, [_vp, _i, _i64, _vp, _i64, _i, _i, _vp, _vp, _vp]),
 }
 
 
@@ -205,7 +209,7 @@ class _Timed:
                                                    "pn2_group_colsum_workspace_bytes", "pn2_chamfer_nn_workspace_bytes",
                                                    "pn2_scan_filter_workspace_bytes", "pn2_voxel_grid_workspace_bytes",
                                                    "pn2_segment_reduce_workspace_bytes", "pn2_voxel_components_workspace_bytes",
-                                                   "pn2_panoptic_workspace_bytes"):
+                                                   "pn2_panoptic_workspace_bytes", "pn2_lovasz_workspace_bytes", "pn2_lovasz_tile_rows"):
             return fn
 
         def timed(*args):

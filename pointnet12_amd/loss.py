@@ -10,6 +10,10 @@ chip with fp64 partials combined in a fixed order.
 class-index targets: the criterion of the SemanticKITTI loop, ``nn.CrossEntropyLoss()(logits.transpose(2, 1), target)``
 (pcdseg.py:178-179: no weight, the input is the model's ``[B, N, C]`` output seen through a class-dim-1 view).  One
 launch each way (``pn2_cross_entropy_fwd`` / ``_bwd``), the input read where it lies, 4 bytes per row kept for the backward.
+
+``lovasz_softmax`` / ``LovaszSoftmax`` are the Lovasz-Softmax loss (Berman, Triki, Blaschko, CVPR 2018), the surrogate of mean IoU
+that SemanticKITTI baselines add to cross-entropy; the reference has none.  One segmented stable radix sort orders every
+(image, class) segment at once (``pn2_lovasz_fwd`` / ``_bwd``), with no read-back, so it captures into the step graph.
 """
 import torch
 
@@ -186,3 +190,120 @@ class CrossEntropyLoss(torch.nn.Module):
 
     def forward(self, input, target):
         return cross_entropy(input, target, self.weight, self.ignore_index, self.reduction, self.label_smoothing)
+
+
+# ------------------------------------------------------------------------------------------------------------ Lovasz-Softmax
+_lovasz_ws = {}          # (device, stream, bytes) -> the sort's workspace: it holds nothing between calls, one per shape is enough
+
+
+def _lovasz_workspace(nbytes, device):
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(nbytes, device=device, dtype=torch.uint8)      # the graph's own pool keeps it alive with the graph
+    key = (device.index, torch.cuda.current_stream(device).cuda_stream, nbytes)
+    ws = _lovasz_ws.get(key)
+    if ws is None:
+        ws = _lovasz_ws[key] = torch.empty(nbytes, device=device, dtype=torch.uint8)
+    return ws
+
+
+class _LovaszSoftmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, target, class_mask, present_only, images, ignore_index, from_logits, layout):
+        lib, st = _lib.load(), _lib.stream()
+        R, ld, inner = layout
+        C = x.shape[1]
+        nbytes = int(lib.pn2_lovasz_workspace_bytes(R, C, images))
+        if nbytes < 0:
+            raise _lib.Pn2Error("lovasz_softmax: %d rows of %d classes in %d images are beyond the kernels' index range" % (R, C, images))
+        ws = _lovasz_workspace(nbytes, x.device)
+        dp = torch.empty(R, C, device=x.device, dtype=torch.float32)
+        loss = torch.empty((), device=x.device, dtype=torch.float32)
+        _lib.check(lib.pn2_lovasz_fwd(_p(x), ld, inner, _p(target), R, C, images, ignore_index, int(from_logits), _p(class_mask),
+                                      int(present_only), _p(ws), _p(dp), None, _p(loss), st), "pn2_lovasz_fwd")
+        ctx.save_for_backward(x, dp)
+        ctx.meta = (R, C, ld, inner, int(from_logits))
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad):
+        lib, st = _lib.load(), _lib.stream()
+        x, dp = ctx.saved_tensors
+        R, C, ld, inner, from_logits = ctx.meta
+        grad = grad.contiguous().float()
+        dx = torch.empty_strided(x.shape, x.stride(), device=x.device, dtype=torch.float32)      # the input's own layout
+        _lib.check(lib.pn2_lovasz_bwd(_p(x), ld, inner, _p(dp), R, C, from_logits, _p(grad), _p(dx), st), "pn2_lovasz_bwd")
+        return dx, None, None, None, None, None, None, None
+
+
+_lovasz_masks = {}       # (device, C, classes) -> int32[C] on the device: a list of classes is copied there once
+
+
+def lovasz_softmax(input, target, classes="present", per_image=False, ignore_index=-100, from_logits=True):
+    """The Lovasz-Softmax loss (Berman, Triki, Blaschko, CVPR 2018), the surrogate that optimises mean IoU; the rule is stated in
+    include/pn2.h (``pn2_lovasz_fwd``) and in numpy in tests/lovasz_ref.py.
+
+    input float32 on the GPU, ``[R, C]`` or ``[B, C, d1, ...]`` (classes in dim 1, C <= 64) in the layouts :func:`cross_entropy`
+    reads in place; logits or log-probabilities with ``from_logits`` (the softmax is part of the kernel), probabilities without.
+    target int64 ``[R]`` / ``[B, d1, ...]``; rows equal to ``ignore_index`` take no part.  ``classes``: "present" (classes with at
+    least one target row), "all", or a list of class ids.  ``per_image`` (``[B, C, ...]`` inputs only): the loss of every image,
+    then the mean over all B.  One segmented stable radix sort serves every class at once; nothing is read back to the host, so
+    forward and backward capture into a graph when target already is an int64 tensor on the input's device (a list of classes is
+    uploaded once, by the first call that names it: make that call before the capture, as a warm-up step does).  The gradient
+    comes back with the input's strides."""
+    if input.dtype != torch.float32:
+        raise TypeError("lovasz_softmax: float32 input expected, got %s" % input.dtype)
+    if target.is_floating_point():
+        raise NotImplementedError("lovasz_softmax: class-probability targets are not supported, class indices only")
+    if input.dim() < 2:
+        raise ValueError("lovasz_softmax: input must be [R, C] or [B, C, d1, ...], got %s" % (tuple(input.shape),))
+    if tuple(target.shape) != tuple(input.shape[:1] + input.shape[2:]):
+        raise ValueError("lovasz_softmax: input %s wants a target of shape %s, got %s"
+                         % (tuple(input.shape), tuple(input.shape[:1] + input.shape[2:]), tuple(target.shape)))
+    C = input.shape[1]
+    if C > 64:
+        raise _lib.Pn2Error("lovasz_softmax: %d classes, the kernels hold a row of at most 64" % C)
+    if input.numel() == 0:
+        raise ValueError("lovasz_softmax: empty input")
+    if per_image and input.dim() < 3:
+        raise _lib.Pn2Error("lovasz_softmax: per_image needs a [B, C, d1, ...] input, got %s" % (tuple(input.shape),))
+    if isinstance(classes, str):
+        if classes not in ("present", "all"):
+            raise ValueError("lovasz_softmax: classes must be 'present', 'all' or a list of class ids, got %r" % (classes,))
+        ids = None
+    else:
+        ids = tuple(sorted(set(int(c) for c in classes)))
+        if any(c < 0 or c >= C for c in ids):
+            raise ValueError("lovasz_softmax: class ids %r outside [0, %d)" % (ids, C))
+    layout = _ce_layout(input)
+    if layout is None:
+        raise _lib.Pn2Error("lovasz_softmax: input of shape %s and strides %s is neither row-major rows of classes nor "
+                            "contiguous [B, C, N]; lay it out as one of the two" % (tuple(input.shape), input.stride()))
+    if not input.is_cuda:
+        raise _lib.Pn2Error("lovasz_softmax: input must be a GPU tensor (the HIP library is the only implementation)")
+    images = input.shape[0] if per_image else 1
+    if images > 1 and layout[2] not in (0, layout[0] // images):
+        raise _lib.Pn2Error("lovasz_softmax: per_image cannot read a transposed [R, C] as images")
+    target = target.to(device=input.device, dtype=torch.int64).contiguous()
+    mask = None
+    if ids is not None:
+        key = (input.device.index, C, ids)
+        mask = _lovasz_masks.get(key)
+        if mask is None:
+            m = torch.zeros(C, dtype=torch.int32)
+            m[list(ids)] = 1
+            mask = _lovasz_masks[key] = m.to(input.device)
+    return _LovaszSoftmax.apply(input, target, mask, classes == "present", images, int(ignore_index), bool(from_logits), layout)
+
+
+class LovaszSoftmax(torch.nn.Module):
+    """:func:`lovasz_softmax` as a module, with the same arguments."""
+
+    def __init__(self, classes="present", per_image=False, ignore_index=-100, from_logits=True):
+        super().__init__()
+        self.classes = classes
+        self.per_image = per_image
+        self.ignore_index = ignore_index
+        self.from_logits = from_logits
+
+    def forward(self, input, target):
+        return lovasz_softmax(input, target, self.classes, self.per_image, self.ignore_index, self.from_logits)

@@ -1,0 +1,17 @@
+"""CPU: the generated gfx950 code of csrc/lovasz.hip uses no scratch (tools/check_isa.py, unchanged; hipcc cross-compiles without a
+GPU).  The packed-fp32 check of tests/test_isa_cpu.py disassembles the whole built library, this file's kernels included."""
+import os
+import shutil
+import subprocess
+import sys
+
+import pytest
+
+from conftest import ROOT
+
+
+@pytest.mark.skipif(shutil.which("hipcc") is None, reason="no hipcc")
+def test_lovasz_kernels_do_not_spill():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_isa.py"), "scratch", "lovasz.hip"], capture_output=True,
+                       text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr

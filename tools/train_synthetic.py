@@ -4,12 +4,14 @@ resident raw scans -> pn2_prepare_clouds -> PointNet2SemSeg forward -> nll_loss 
 bucket -> (gradient all-reduce when launched under torch.distributed.run) -> pn2_adam_step, StepLR as semseg.py:113.
 ``--optimizer SGD`` takes the other branch of semseg.py:103-104 (SGD, lr=0.01, momentum=0.9) -> pn2_sgd_step.
 ``--loss ce`` takes the SemanticKITTI loop's criterion instead, ``CrossEntropyLoss()(net(...).transpose(2, 1), target)``
-(pcdseg.py:178-179) -> pn2_cross_entropy_fwd / _bwd on the transposed view, no copy.
+(pcdseg.py:178-179) -> pn2_cross_entropy_fwd / _bwd on the transposed view, no copy.  ``--loss lovasz`` trains on the Lovasz-Softmax
+surrogate of mean IoU alone (pn2_lovasz_fwd / _bwd on the same view), ``--loss ce+lovasz`` on the sum of the two, the usual
+SemanticKITTI recipe; both capture under ``--graph`` like the others.
 
 Labels are a function of the normalised height and intensity, so the loss must fall; the script prints the loss
 curve and the all-inclusive throughput (loader + step + optimiser), which bench.py's metric deliberately excludes.
 
-    python tools/train_synthetic.py --steps 200 --batch 16 --npoints 4096 [--msg] [--graph] [--optimizer SGD] [--loss ce]
+    python tools/train_synthetic.py --steps 200 --batch 16 --npoints 4096 [--msg] [--graph] [--optimizer SGD] [--loss ce|lovasz|ce+lovasz]
 """
 import argparse
 import json
@@ -22,7 +24,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pointnet12_amd import graph, loader, optim, parallel, pointnet2, synthetic as syn   # noqa: E402
-from pointnet12_amd.loss import CrossEntropyLoss, nll_loss                                # noqa: E402
+from pointnet12_amd.loss import CrossEntropyLoss, LovaszSoftmax, nll_loss                 # noqa: E402
 
 CLASSES = 13
 
@@ -50,7 +52,8 @@ def main():
     ap.add_argument("--graph", action="store_true", help="capture zero-grad + forward + loss + backward + Adam")
     ap.add_argument("--lr", type=float, default=1e-3, help="Adam's learning rate (SGD takes the reference's 0.01)")
     ap.add_argument("--optimizer", choices=("Adam", "SGD"), default="Adam")
-    ap.add_argument("--loss", choices=("nll", "ce"), default="nll", help="ce: the criterion of pcdseg.py:178-179")
+    ap.add_argument("--loss", choices=("nll", "ce", "lovasz", "ce+lovasz"), default="nll",
+                    help="ce: the criterion of pcdseg.py:178-179; lovasz: the Lovasz-Softmax loss; ce+lovasz: their sum")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -72,11 +75,17 @@ def main():
     lab = torch.empty(args.batch, args.npoints, device=dev, dtype=torch.int64)
 
     criterion = CrossEntropyLoss()
+    lovasz = LovaszSoftmax()
 
     def compute():
         opt.zero_grad()                                            # free after the first step (fused into the optimiser's)
         if args.loss == "ce":
             loss = criterion(net(pts.transpose(2, 1)).transpose(2, 1), lab)
+        elif args.loss == "lovasz":
+            loss = lovasz(net(pts.transpose(2, 1)).transpose(2, 1), lab)
+        elif args.loss == "ce+lovasz":
+            logits = net(pts.transpose(2, 1)).transpose(2, 1)
+            loss = criterion(logits, lab) + lovasz(logits, lab)
         else:
             loss = nll_loss(net(pts.transpose(2, 1)).reshape(-1, CLASSES), lab.reshape(-1))
         loss.backward()
@@ -104,7 +113,7 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     print(json.dumps({"net": "msg" if args.msg else "ssg", "graph": args.graph,
-                      **({"optimizer": "SGD"} if args.optimizer == "SGD" else {}), **({"loss": "ce"} if args.loss == "ce" else {}), "steps": args.steps,
+                      **({"optimizer": "SGD"} if args.optimizer == "SGD" else {}), **({"loss": args.loss} if args.loss != "nll" else {}), "steps": args.steps,
                       "batch": args.batch, "npoints": args.npoints, "ms_per_step_all_in": round(dt / args.steps * 1e3, 3),
                       "points_per_s_all_in": round(args.batch * args.npoints * args.steps / dt),
                       "loss_first": curve[0][1], "loss_last": curve[-1][1], "curve": curve}))
