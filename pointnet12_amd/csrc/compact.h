@@ -3,7 +3,7 @@
 // from run to run.  Three launches, a launch boundary is the only ordering between them:
 //   a flag kernel     one workgroup per tile of kCompactTile rows, built on pn2_compact_flag_tile: a one-byte flag per row and the
 //                     tile's kept count (__ballot + popcount per wave, the four waves summed through LDS);
-//   pn2_compact_offsets_kernel   one wave per cloud: exclusive prefix sum of its tiles' counts (64 tiles per step, shuffles), the
+//   pn2_compact_offsets_kernel   one wave per cloud: exclusive prefix sum of its tiles' counts (pn2_wave_row_excl_scan), the
 //                     cloud's kept count, the caller's "row_count above max_rows" bit;
 //   a write kernel    one workgroup per tile, built on pn2_compact_write_tile: rank inside the wave from the ballot, the sixteen
 //                     64-row segments of the tile ordered through LDS; the caller's lambda stores every kept row at its rank.
@@ -11,6 +11,7 @@
 // the workgroup: both helpers hold a barrier), so a captured launch sized by max_rows stays valid when the device-side count changes.
 #pragma once
 #include "pn2_common.h"
+#include "wave_ops.h"
 
 constexpr int kCompactTile = 1024;                                  // rows per workgroup of the flag and the write pass
 static_assert(PN2_SCAN_TILE == kCompactTile && PN2_VOXEL_TILE == kCompactTile, "both entry points share this code and its tile");
@@ -35,21 +36,15 @@ struct Pn2Compact {
     int *tile_offset(void *base) const { return reinterpret_cast<int *>(flags(base) + flag_bytes + word_bytes); }
 };
 
-// The flag pass of one tile with `left` rows (1 .. kCompactTile) inside the cloud: keep_row(i) is evaluated for i < left only;
-// every row of the tile gets its flag, the ones beyond the cloud 0; one store of the tile's count.
-template <class Keep>
-__device__ __forceinline__ void pn2_compact_flag_tile(int left, unsigned char *__restrict__ flags_of_tile, int *__restrict__ tile_count,
-                                                      Keep keep_row) {
+// How many of a tile's kCompactTile rows satisfy pred(i), i = round * kCompactThreads + thread: a ballot and a popcount per wave and
+// round, the wave totals summed through LDS, one store of the count.  Holds one barrier.
+template <class Pred>
+__device__ __forceinline__ void pn2_compact_count_tile(int *__restrict__ tile_count, Pred pred) {
     __shared__ int s_count[kCompactWaves];
-    int kept = 0;
+    int n = 0;
 #pragma unroll
-    for (int r = 0; r < kCompactRounds; ++r) {
-        const int i = r * kCompactThreads + (int)threadIdx.x;
-        const bool keep = i < left && keep_row(i);
-        flags_of_tile[i] = keep ? 1 : 0;
-        kept += __popcll(__ballot(keep));
-    }
-    if ((threadIdx.x & (PN2_WAVE - 1)) == 0) s_count[threadIdx.x / PN2_WAVE] = kept;
+    for (int r = 0; r < kCompactRounds; ++r) n += __popcll(__ballot(pred(r * kCompactThreads + (int)threadIdx.x)));
+    if ((threadIdx.x & (PN2_WAVE - 1)) == 0) s_count[threadIdx.x / PN2_WAVE] = n;
     __syncthreads();
     if (threadIdx.x == 0) {
         int total = 0;
@@ -59,28 +54,50 @@ __device__ __forceinline__ void pn2_compact_flag_tile(int left, unsigned char *_
     }
 }
 
-// The write pass of one tile: emit(i, rank) for every kept row i of the tile, rank = kept rows of the tile before it.
-template <class Emit>
-__device__ __forceinline__ void pn2_compact_write_tile(const unsigned char *__restrict__ flags_of_tile, Emit emit) {
+// The flag pass of one tile with `left` rows (1 .. kCompactTile) inside the cloud: keep_row(i) is evaluated for i < left only;
+// every row of the tile gets its flag, the ones beyond the cloud 0; one store of the tile's count.
+template <class Keep>
+__device__ __forceinline__ void pn2_compact_flag_tile(int left, unsigned char *__restrict__ flags_of_tile, int *__restrict__ tile_count,
+                                                      Keep keep_row) {
+    pn2_compact_count_tile(tile_count, [&](int i) {
+        const bool keep = i < left && keep_row(i);
+        flags_of_tile[i] = keep ? 1 : 0;
+        return keep;
+    });
+}
+
+// rank[r] = the flagged rows of the tile before this thread's row of round r (itself not counted): inside its 64-row segment from
+// the ballot, the sixteen segments of the tile ordered through LDS.  Holds one barrier.
+__device__ __forceinline__ void pn2_compact_rank_tile(const bool (&flag)[kCompactRounds], int (&rank)[kCompactRounds]) {
     __shared__ int s_seg[kCompactSegments];
     const int lane = threadIdx.x & (PN2_WAVE - 1), wave = threadIdx.x / PN2_WAVE;
-    bool keep[kCompactRounds];
-    int rank[kCompactRounds];
 #pragma unroll
     for (int r = 0; r < kCompactRounds; ++r) {
-        keep[r] = flags_of_tile[r * kCompactThreads + (int)threadIdx.x] != 0;
-        const unsigned long long m = __ballot(keep[r]);
-        rank[r] = __popcll(m & ((1ull << lane) - 1ull));            // kept rows of this segment before this lane
+        const unsigned long long m = __ballot(flag[r]);
+        rank[r] = __popcll(m & ((1ull << lane) - 1ull));            // flagged rows of this segment before this lane
         if (lane == 0) s_seg[r * kCompactWaves + wave] = __popcll(m);
     }
     __syncthreads();
-    int before = 0, seg = 0;                                        // kept rows of the tile in the segments before segment `seg`
+    int before = 0, seg = 0;                                        // flagged rows of the tile in the segments before segment `seg`
 #pragma unroll
     for (int r = 0; r < kCompactRounds; ++r) {
         const int mine = r * kCompactWaves + wave;
         for (; seg < mine; ++seg) before += s_seg[seg];
-        if (keep[r]) emit(r * kCompactThreads + (int)threadIdx.x, before + rank[r]);
+        rank[r] += before;
     }
+}
+
+// The write pass of one tile: emit(i, rank) for every kept row i of the tile, rank = kept rows of the tile before it.
+template <class Emit>
+__device__ __forceinline__ void pn2_compact_write_tile(const unsigned char *__restrict__ flags_of_tile, Emit emit) {
+    bool keep[kCompactRounds];
+    int rank[kCompactRounds];
+#pragma unroll
+    for (int r = 0; r < kCompactRounds; ++r) keep[r] = flags_of_tile[r * kCompactThreads + (int)threadIdx.x] != 0;
+    pn2_compact_rank_tile(keep, rank);
+#pragma unroll
+    for (int r = 0; r < kCompactRounds; ++r)
+        if (keep[r]) emit(r * kCompactThreads + (int)threadIdx.x, rank[r]);
 }
 
 namespace {
@@ -93,23 +110,9 @@ __global__ __launch_bounds__(PN2_WAVE) void pn2_compact_offsets_kernel(const int
     const int b = blockIdx.x, lane = threadIdx.x;
     const int n = pn2_clamped_rows(row_count, b, max_rows);
     const int active = (int)(((int64_t)n + kCompactTile - 1) / kCompactTile);          // <= tiles: n <= max_rows
-    const int *cnt = tile_count + (int64_t)b * tiles;
-    int *off = tile_offset + (int64_t)b * tiles;
-    int carry = 0;                                                  // kept rows before this step: at most n < 2^31
-    for (int first = 0; first < active; first += PN2_WAVE) {
-        const int i = first + lane;
-        const int v = i < active ? cnt[i] : 0;
-        int incl = v;
-#pragma unroll
-        for (int d = 1; d < PN2_WAVE; d <<= 1) {
-            const int up = __shfl_up(incl, d, PN2_WAVE);
-            if (lane >= d) incl += up;
-        }
-        if (i < active) off[i] = carry + incl - v;
-        carry += __shfl(incl, PN2_WAVE - 1, PN2_WAVE);
-    }
+    const int kept = pn2_wave_row_excl_scan(tile_count + (int64_t)b * tiles, tile_offset + (int64_t)b * tiles, active);    // at most n < 2^31
     if (lane == 0) {
-        out_count[b] = carry;
+        out_count[b] = kept;
         if (err != nullptr && row_count[b] > max_rows) atomicOr(err, rows_bit);
     }
 }

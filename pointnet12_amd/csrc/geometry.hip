@@ -8,6 +8,7 @@
 // so every fused step below is an explicit __builtin_fmaf and nothing else may contract.
 #include "pn2_common.h"
 #include "pair_dist.h"                    // sq_norm3, pair_dist (shared with knn.hip)
+#include "wave_ops.h"
 #include <stdlib.h>
 
 namespace {
@@ -222,16 +223,7 @@ __global__ __launch_bounds__(THREADS) void fps_pruned_kernel(const float *__rest
         int c[CPT], sum = 0;
 #pragma unroll
         for (int i = 0; i < CPT; ++i) { c[i] = hist[t * CPT + i]; sum += c[i]; }
-        int x = sum;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int y = __shfl_up(x, d, 64);
-            if (lane >= d) x += y;
-        }
-        if (lane == 63) wsum[wave] = x;
-        __syncthreads();
-        int base = x - sum;
-        for (int w = 0; w < wave; ++w) base += wsum[w];
+        int base = pn2_block_excl_scan(sum, wsum);
 #pragma unroll
         for (int i = 0; i < CPT; ++i) { hist[t * CPT + i] = base; base += c[i]; }
     }
@@ -412,16 +404,7 @@ __global__ __launch_bounds__(THREADS) void fps_rows_kernel(const float *__restri
         int c[CPT], sum = 0;
 #pragma unroll
         for (int i = 0; i < CPT; ++i) { c[i] = hist[t * CPT + i]; sum += c[i]; }
-        int x = sum;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int y = __shfl_up(x, d, 64);
-            if (lane >= d) x += y;
-        }
-        if (lane == 63) wsum[wave] = x;
-        __syncthreads();
-        int base = x - sum;
-        for (int w = 0; w < wave; ++w) base += wsum[w];
+        int base = pn2_block_excl_scan(sum, wsum);
 #pragma unroll
         for (int i = 0; i < CPT; ++i) { hist[t * CPT + i] = base; base += c[i]; }
     }
@@ -801,16 +784,7 @@ __global__ __launch_bounds__(1024) void bq_order_kernel(const float *__restrict_
         int c[CPT], sum = 0;
 #pragma unroll
         for (int i = 0; i < CPT; ++i) { c[i] = hist[t * CPT + i]; sum += c[i]; }
-        int x = sum;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int y = __shfl_up(x, d, 64);
-            if (lane >= d) x += y;
-        }
-        if (lane == 63) wsum[wave] = x;
-        __syncthreads();
-        int base = x - sum;
-        for (int w = 0; w < wave; ++w) base += wsum[w];
+        int base = pn2_block_excl_scan(sum, wsum);
 #pragma unroll
         for (int i = 0; i < CPT; ++i) { hist[t * CPT + i] = base; base += c[i]; }
     }

@@ -10,6 +10,7 @@
 // the input is the model's [B, N, C] output seen class-dim-1): log-softmax, NLL and label smoothing in one pass each way,
 // with the same fp64 partials and ticket.
 #include "pn2_common.h"
+#include "softmax_row.h"
 
 namespace {
 
@@ -173,9 +174,7 @@ enum { kReduceNone = 0, kReduceMean = 1, kReduceSum = 2 };
 
 template <int KC, int MODE>
 __device__ __forceinline__ int64_t ce_row_base(int64_t r, int ld, int64_t inner, int C) {
-    if (MODE != kClassStrided) return r * ld;
-    const int64_t b = r / inner;
-    return b * C * inner + (r - b * inner);
+    return MODE != kClassStrided ? r * ld : pn2_class_strided_base(r, inner, C);
 }
 
 template <int KC, int MODE>
@@ -193,26 +192,8 @@ __device__ __forceinline__ void ce_load_row(const float *__restrict__ row, int64
             }
         }
     } else {
-        const int64_t step = MODE == kClassStrided ? inner : 1;
-#pragma unroll
-        for (int c = 0; c < KC; ++c)
-            if (c < C) v[c] = row[c * step];
+        pn2_load_row_strided<KC>(row, MODE == kClassStrided ? inner : 1, C, v);
     }
-}
-
-// v <- v - max(v) over the C leading entries; returns log sum exp(v) (four interleaved partial sums: the tree shape of ATen's
-// own row sum, see log_softmax_bwd_kernel)
-template <int KC>
-__device__ __forceinline__ float ce_center_logsum(int C, float (&v)[KC]) {
-    float m = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < KC; ++c)
-        if (c < C) m = fmaxf(m, v[c]);
-    float s4[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int c = 0; c < KC; ++c)
-        if (c < C) { v[c] -= m; s4[c & 3] += expf(v[c]); }
-    return logf((s4[0] + s4[1]) + (s4[2] + s4[3]));
 }
 
 // the class weights (1 without a weight vector) in LDS, and their sum in a fixed order
@@ -238,7 +219,7 @@ __global__ __launch_bounds__(kThreads) void ce_fwd_kernel(const float *__restric
         asm volatile("" ::: "memory");      // keeps the weights in LDS: hoisted out of this loop they cost up to 64 more registers
         float v[KC];
         ce_load_row<KC, MODE>(x + ce_row_base<KC, MODE>(r, ld, inner, C), inner, C, v);
-        const float logs = ce_center_logsum<KC>(C, v);
+        const float logs = pn2_center_logsum<KC>(C, v);
         logsum[r] = logs;
         const int64_t t = target[r];
         double l = 0.0;

@@ -16,15 +16,15 @@
 //                   fp64 partial of e * c_k summed in a fixed tree;
 //   reduce          one workgroup: tile partials per segment in a fixed order, the means, the NaN of an out-of-range target.
 // Every sum across threads is an integer count or an fp64 sum of fixed shape: the outputs are byte-identical from run to run.
-#include "pn2_common.h"
+#include "compact.h"
+#include "softmax_row.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / PN2_WAVE;
-constexpr int kTile = 1024;                       // elements of one segment per workgroup of the sort, scan and finalise passes
-constexpr int kRounds = kTile / kThreads;         // element = round * kThreads + thread: row order is (round, wave, lane)
-constexpr int kSegs = kRounds * kWaves;           // 64-element runs of a tile, in row order
+// Every pass runs compact.h's workgroup; the sort, scan and finalise passes take its tile: kCompactTile elements of one segment,
+// element = round * kThreads + thread, so row order is (round, wave, lane): kCompactSegments 64-element runs.
+constexpr int kThreads = kCompactThreads;
+constexpr int kWaves = kCompactWaves;
 constexpr int kRadix = 256;
 static_assert(kRadix == kThreads, "one thread per digit value in the scatter pass");
 constexpr int kMaxClasses = 64;
@@ -36,7 +36,7 @@ struct Layout {                                   // the parts of the workspace,
     Layout(int64_t R, int C, int images) {
         N = R / images;
         S = (int64_t)images * C;
-        nt = pn2_cdiv(N, kTile);
+        nt = pn2_cdiv(N, kCompactTile);
         key_bytes = pn2_round16(S * N * 4);
         hist_bytes = pn2_round16(S * kRadix * nt * 4);
         tot_bytes = pn2_round16(S * kRadix * 4);
@@ -50,50 +50,20 @@ struct Layout {                                   // the parts of the workspace,
     int64_t bytes() const { return 4 * key_bytes + hist_bytes + tot_bytes + tile_bytes + g_bytes + part_bytes + seg_bytes + bad_bytes; }
 };
 
-// exclusive prefix sum of one int per thread over the workgroup (wave scans by shuffle, the four wave totals through LDS)
-__device__ __forceinline__ int block_excl_scan(int v, int *s_wave) {
-    const int lane = threadIdx.x & (PN2_WAVE - 1), wave = threadIdx.x / PN2_WAVE;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < PN2_WAVE; d <<= 1) {
-        const int up = __shfl_up(incl, d, PN2_WAVE);
-        if (lane >= d) incl += up;
-    }
-    if (lane == PN2_WAVE - 1) s_wave[wave] = incl;
-    __syncthreads();
-    int before = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w)
-        if (w < wave) before += s_wave[w];
-    return before + incl - v;
-}
-
 // ------------------------------------------------------------------------------------------------------------------ key pass
-// p of a row exactly as pn2_cross_entropy_bwd recomputes it: expf((x - max) - logf(sum)), the sum as four interleaved partial sums
+// p of a row exactly as pn2_cross_entropy_bwd recomputes it (softmax_row.h): expf((x - max) - logf(sum))
 template <int KC>
 __device__ __forceinline__ void row_probabilities(const float *__restrict__ row, int64_t step, int C, int from_logits, float (&v)[KC]) {
-#pragma unroll
-    for (int c = 0; c < KC; ++c)
-        if (c < C) v[c] = row[c * step];
+    pn2_load_row_strided<KC>(row, step, C, v);
     if (!from_logits) return;
-    float m = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < KC; ++c)
-        if (c < C) m = fmaxf(m, v[c]);
-    float s4[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int c = 0; c < KC; ++c)
-        if (c < C) { v[c] -= m; s4[c & 3] += expf(v[c]); }
-    const float logs = logf((s4[0] + s4[1]) + (s4[2] + s4[3]));
+    const float logs = pn2_center_logsum<KC>(C, v);
 #pragma unroll
     for (int c = 0; c < KC; ++c)
         if (c < C) v[c] = expf(v[c] - logs);
 }
 
 __device__ __forceinline__ int64_t row_base(int64_t r, int ld, int64_t inner, int C) {
-    if (inner == 0) return r * ld;
-    const int64_t b = r / inner;
-    return b * C * inner + (r - b * inner);
+    return inner == 0 ? r * ld : pn2_class_strided_base(r, inner, C);
 }
 
 template <int KC>
@@ -142,9 +112,9 @@ __global__ __launch_bounds__(kThreads) void hist_kernel(const unsigned *__restri
     const int tile = (int)(blockIdx.x - seg * nt);
     h[threadIdx.x] = 0;
     __syncthreads();
-    const int64_t first = (int64_t)tile * kTile;
+    const int64_t first = (int64_t)tile * kCompactTile;
 #pragma unroll
-    for (int r = 0; r < kRounds; ++r) {
+    for (int r = 0; r < kCompactRounds; ++r) {
         const int64_t i = first + r * kThreads + threadIdx.x;
         if (i < N) atomicAdd(&h[(keys[seg * N + i] >> shift) & (kRadix - 1)], 1);      // a count: the same whatever the order
     }
@@ -152,26 +122,12 @@ __global__ __launch_bounds__(kThreads) void hist_kernel(const unsigned *__restri
     hist[(seg * kRadix + threadIdx.x) * nt + tile] = h[threadIdx.x];
 }
 
-// One wave per row of nt counts: the row becomes its exclusive prefix sum, totals[row] its sum (64 counts a step, a carry between)
+// One wave per row of nt counts: the row becomes its exclusive prefix sum, totals[row] its sum
 __global__ __launch_bounds__(kThreads) void row_scan_kernel(int *__restrict__ data, int *__restrict__ totals, int64_t rows, int nt) {
-    const int lane = threadIdx.x & (PN2_WAVE - 1);
     const int64_t row = (int64_t)blockIdx.x * kWaves + threadIdx.x / PN2_WAVE;
     if (row >= rows) return;                                             // uniform over the wave
-    int *d = data + row * nt;
-    int carry = 0;
-    for (int first = 0; first < nt; first += PN2_WAVE) {
-        const int i = first + lane;
-        const int v = i < nt ? d[i] : 0;
-        int incl = v;
-#pragma unroll
-        for (int s = 1; s < PN2_WAVE; s <<= 1) {
-            const int up = __shfl_up(incl, s, PN2_WAVE);
-            if (lane >= s) incl += up;
-        }
-        if (i < nt) d[i] = carry + incl - v;
-        carry += __shfl(incl, PN2_WAVE - 1, PN2_WAVE);
-    }
-    if (lane == 0) totals[row] = carry;
+    const int total = pn2_wave_row_excl_scan(data + row * nt, data + row * nt, nt);
+    if ((threadIdx.x & (PN2_WAVE - 1)) == 0) totals[row] = total;
 }
 
 // element -> base of its digit in the segment + its digit's elements in earlier tiles + in earlier 64-runs of this tile + in
@@ -180,22 +136,22 @@ __global__ __launch_bounds__(kThreads) void scatter_kernel(const unsigned *__res
                                                            unsigned *__restrict__ keys_out, unsigned *__restrict__ pays_out,
                                                            const int *__restrict__ offs, const int *__restrict__ totals, int64_t N,
                                                            int nt, int shift) {
-    __shared__ int cnt[kSegs * kRadix];
+    __shared__ int cnt[kCompactSegments * kRadix];
     __shared__ int base[kRadix];
     __shared__ int s_wave[kWaves];
     const int64_t seg = blockIdx.x / nt;
     const int tile = (int)(blockIdx.x - seg * nt);
     const int lane = threadIdx.x & (PN2_WAVE - 1), wave = threadIdx.x / PN2_WAVE;
-    for (int i = threadIdx.x; i < kSegs * kRadix; i += kThreads) cnt[i] = 0;
-    const int before = block_excl_scan(totals[seg * kRadix + threadIdx.x], s_wave);
+    for (int i = threadIdx.x; i < kCompactSegments * kRadix; i += kThreads) cnt[i] = 0;
+    const int before = pn2_block_excl_scan(totals[seg * kRadix + threadIdx.x], s_wave);
     base[threadIdx.x] = before + offs[(seg * kRadix + threadIdx.x) * nt + tile];
     __syncthreads();
-    const int64_t first = (int64_t)tile * kTile;
-    unsigned key[kRounds], pay[kRounds];
-    int rank[kRounds];
-    bool valid[kRounds];
+    const int64_t first = (int64_t)tile * kCompactTile;
+    unsigned key[kCompactRounds], pay[kCompactRounds];
+    int rank[kCompactRounds];
+    bool valid[kCompactRounds];
 #pragma unroll
-    for (int r = 0; r < kRounds; ++r) {
+    for (int r = 0; r < kCompactRounds; ++r) {
         const int64_t i = first + r * kThreads + threadIdx.x;
         valid[r] = i < N;
         key[r] = valid[r] ? keys_in[seg * N + i] : 0u;
@@ -216,7 +172,7 @@ __global__ __launch_bounds__(kThreads) void scatter_kernel(const unsigned *__res
     {
         int run = 0;                                                     // thread d: digit d's counts over the runs, in row order
 #pragma unroll
-        for (int s = 0; s < kSegs; ++s) {
+        for (int s = 0; s < kCompactSegments; ++s) {
             const int v = cnt[s * kRadix + threadIdx.x];
             cnt[s * kRadix + threadIdx.x] = run;
             run += v;
@@ -224,7 +180,7 @@ __global__ __launch_bounds__(kThreads) void scatter_kernel(const unsigned *__res
     }
     __syncthreads();
 #pragma unroll
-    for (int r = 0; r < kRounds; ++r) {
+    for (int r = 0; r < kCompactRounds; ++r) {
         if (!valid[r]) continue;
         const unsigned digit = (key[r] >> shift) & (kRadix - 1);
         const int64_t pos = (int64_t)base[digit] + cnt[(r * kWaves + wave) * kRadix + digit] + rank[r];
@@ -238,25 +194,10 @@ __global__ __launch_bounds__(kThreads) void scatter_kernel(const unsigned *__res
 // ---------------------------------------------------------------------------------------------------------- scan and finalise
 __global__ __launch_bounds__(kThreads) void fg_count_kernel(const unsigned *__restrict__ pays, int *__restrict__ tile_fg, int64_t N,
                                                             int nt) {
-    __shared__ int s_count[kWaves];
     const int64_t seg = blockIdx.x / nt;
     const int tile = (int)(blockIdx.x - seg * nt);
-    const int64_t first = (int64_t)tile * kTile;
-    int n = 0;
-#pragma unroll
-    for (int r = 0; r < kRounds; ++r) {
-        const int64_t i = first + r * kThreads + threadIdx.x;
-        const bool fg = i < N && (pays[seg * N + i] & kFgBit) != 0u;
-        n += __popcll(__ballot(fg));
-    }
-    if ((threadIdx.x & (PN2_WAVE - 1)) == 0) s_count[threadIdx.x / PN2_WAVE] = n;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int total = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) total += s_count[w];
-        tile_fg[seg * nt + tile] = total;
-    }
+    const int64_t first = (int64_t)tile * kCompactTile;
+    pn2_compact_count_tile(tile_fg + seg * nt + tile, [&](int i) { return first + i < N && (pays[seg * N + first + i] & kFgBit) != 0u; });
 }
 
 // is class c of image b counted, and how many of the image's classes are
@@ -276,7 +217,6 @@ __global__ __launch_bounds__(kThreads) void finalise_kernel(const unsigned *__re
                                                             const int *__restrict__ tile_off, const int *__restrict__ G, int64_t N,
                                                             int nt, int C, int images, const int32_t *__restrict__ class_mask,
                                                             int present_only, float *__restrict__ dp, double *__restrict__ partial) {
-    __shared__ int s_run[kSegs];
     __shared__ double s_sum[kWaves];
     const int64_t seg = blockIdx.x / nt;
     const int tile = (int)(blockIdx.x - seg * nt);
@@ -287,35 +227,31 @@ __global__ __launch_bounds__(kThreads) void finalise_kernel(const unsigned *__re
     const int ncounted = counted_classes(G, class_mask, present_only, b, C, c, &counted);
     const double w = counted ? 1.0 / ((double)ncounted * (double)images) : 0.0;
     const int64_t g = G[seg];
-    const int64_t first = (int64_t)tile * kTile;
-    unsigned key[kRounds], pay[kRounds];
-    int incl[kRounds];
-    bool valid[kRounds];
+    const int64_t first = (int64_t)tile * kCompactTile;
+    unsigned key[kCompactRounds], pay[kCompactRounds];
+    int fg_before[kCompactRounds];                                      // foreground rows of the tile before this one
+    bool valid[kCompactRounds], fg[kCompactRounds];
 #pragma unroll
-    for (int r = 0; r < kRounds; ++r) {
+    for (int r = 0; r < kCompactRounds; ++r) {
         const int64_t i = first + r * kThreads + threadIdx.x;
         valid[r] = i < N;
         key[r] = valid[r] ? keys[seg * N + i] : kKeyAbsent;
         pay[r] = valid[r] ? pays[seg * N + i] : 0u;
-        const unsigned long long m = __ballot((pay[r] & kFgBit) != 0u);
-        incl[r] = __popcll(m & ((2ull << lane) - 1ull));                 // foreground rows of this run up to and including this lane
-        if (lane == 0) s_run[r * kWaves + wave] = __popcll(m);
+        fg[r] = (pay[r] & kFgBit) != 0u;
     }
-    __syncthreads();
+    pn2_compact_rank_tile(fg, fg_before);
     double sum = 0.0;
-    int before = tile_off[seg * nt + tile], s = 0;
+    const int before = tile_off[seg * nt + tile];
 #pragma unroll
-    for (int r = 0; r < kRounds; ++r) {
-        const int mine = r * kWaves + wave;
-        for (; s < mine; ++s) before += s_run[s];
+    for (int r = 0; r < kCompactRounds; ++r) {
         if (!valid[r]) continue;
         const unsigned n = pay[r] & kRowMask;
         float out = 0.f;
         if (key[r] != kKeyAbsent && counted) {
             const float e = __uint_as_float(key[r] == 0u ? 0x7FC00000u : 0x7FFFFFFFu - key[r]);
             const int64_t k = first + r * kThreads + threadIdx.x + 1;    // 1-based rank: rows that take no part sort behind every real one
-            const int64_t F = before + incl[r];
-            const int64_t Fp = F - ((pay[r] & kFgBit) ? 1 : 0);
+            const int64_t Fp = before + fg_before[r];
+            const int64_t F = Fp + (fg[r] ? 1 : 0);
             const double Jk = 1.0 - (double)(g - F) / (double)(g + k - F);
             const double Jp = k == 1 ? 0.0 : 1.0 - (double)(g - Fp) / (double)(g + (k - 1) - Fp);
             const double ck = Jk - Jp;
@@ -424,7 +360,7 @@ int check_layout(int ld, int64_t inner, int64_t R, int C) {
 
 extern "C" {
 
-int pn2_lovasz_tile_rows(void) { return kTile; }
+int pn2_lovasz_tile_rows(void) { return kCompactTile; }
 
 int64_t pn2_lovasz_workspace_bytes(int64_t R, int C, int images) {
     if (check_shape(R, C, images) != PN2_OK) return PN2_EINVAL;

@@ -16,6 +16,7 @@
 // flushed with 64-bit integer atomics: integer adds commute, the table is bit-identical however the workgroups were scheduled.
 #include "pn2_common.h"
 #include "row_argmax.h"
+#include "wave_ops.h"
 
 #include <algorithm>
 
@@ -60,16 +61,9 @@ __global__ __launch_bounds__(kThreads) void seg_confusion_kernel(const float *__
             live = t != ignore_index;
             bin = (t >= 0 && t < C ? (int)t : C) * C + arg;
         }
-        for (int round = 0; round < kAggregateRounds; ++round) {
-            const unsigned long long waiting = __ballot(live);
-            if (waiting == 0ull) break;
-            const int leader = __ffsll((long long)waiting) - 1;
-            const int its = __shfl(bin, leader, PN2_WAVE);
-            const bool same = live && bin == its;
-            const unsigned long long votes = __ballot(same);
-            if (lane == leader) atomicAdd(mine + its, (unsigned)__popcll(votes));
-            live = live && !same;
-        }
+        live = pn2_wave_combine<kAggregateRounds>(bin, live, [&](bool, int leader, unsigned long long votes) {
+            if (lane == leader) atomicAdd(mine + bin, (unsigned)__popcll(votes));
+        });
         if (live) atomicAdd(mine + bin, 1u);
     }
     __syncthreads();

@@ -14,13 +14,14 @@
 //                      exceed half of it), adds tp and the two halves of the IoU's 53-bit integer;
 //     residue_kernel   one thread per segment slot of both tables: unmatched with area >= min_points adds fn / fp.
 //   A scan's road is ONE segment of tens of thousands of rows: the lanes of a wave that hold the same key are found with ballots
-//   (kRounds leaders, as metrics.hip does for its bins; whatever is left goes lane by lane), ONE lane claims the slot and adds the
+//   (pn2_wave_combine, kRounds leaders; whatever is left goes lane by lane), ONE lane claims the slot and adds the
 //   count of its voters, and hands the slot to them with a shuffle.  The match and residue launches do the same per class.
 //   -DPN2_PANOPTIC_COMBINE=0 (make XFLAGS=...) builds the uncombined form for measurements; integer addition is associative: the bytes
 //   are the same either way.  No thread waits for another thread's write; every probe loop is bounded by its table.
 //
 // This file is built with -ffp-contract=off: the IoU is ONE IEEE fp64 division, scaled by an exact power of two.
 #include "slot_table.h"
+#include "wave_ops.h"
 
 #ifndef PN2_PANOPTIC_COMBINE
 #define PN2_PANOPTIC_COMBINE 1
@@ -31,9 +32,8 @@ namespace {
 constexpr int kThreads = 256;
 constexpr bool kCombine = PN2_PANOPTIC_COMBINE != 0;
 constexpr int kRounds = 4;                                          // keys a wave combines with ballots before its lanes go alone
-constexpr unsigned kGridCap = 1u << 16;                             // workgroups per cloud of the grid-stride clear
 constexpr int kColumns = 5;                                         // tp, fp, fn, iou_hi, iou_lo
-static_assert(kThreads == kSlotThreads, "clear_kernel fills its tables with pn2_slot_fill");
+static_assert(kThreads == kSlotThreads, "clear_kernel fills its tables with pn2_slot_fill; the grids come from pn2_slot_blocks");
 
 struct alignas(16) Slot {
     unsigned long long key;                                         // segments: class << 32 | id; pairs: gt slot << 32 | pred slot
@@ -56,36 +56,21 @@ __device__ __forceinline__ int claim_and_add(Slot *table, unsigned mask, unsigne
     int slot = -1;
     if (kCombine) {
         const int lane = threadIdx.x & (PN2_WAVE - 1);
-        for (int round = 0; round < kRounds; ++round) {
-            const unsigned long long waiting = __ballot(live);
-            if (waiting == 0ull) break;                             // (uniform over the wave)
-            const int leader = __ffsll((long long)waiting) - 1;
-            const unsigned long long its = __shfl(key, leader, PN2_WAVE);
-            const bool same = live && key == its;
-            const unsigned long long votes = __ballot(same);
+        live = pn2_wave_combine<kRounds>(key, live, [&](bool voter, int leader, unsigned long long votes) {
             int s = -1;
             if (lane == leader) {
                 s = pn2_slot_claim(table, mask, key);
                 if (s >= 0) atomicAdd(&table[s].count, __popcll(votes));
             }
             s = __shfl(s, leader, PN2_WAVE);
-            if (same) {
-                slot = s;
-                live = false;
-            }
-        }
+            if (voter) slot = s;
+        });
     }
     if (live) {
         slot = pn2_slot_claim(table, mask, key);                    // (never -1: a table holds at most as many keys as the cloud has rows)
         if (slot >= 0) atomicAdd(&table[slot].count, 1);
     }
     return slot;
-}
-
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, PN2_WAVE);
-    return v;
 }
 
 __device__ __forceinline__ void add_i64(int64_t *word, unsigned long long value) {
@@ -182,22 +167,15 @@ __global__ __launch_bounds__(kThreads) void match_kernel(const int64_t *__restri
     }
     int64_t *dst = out + (int64_t)b * out_stride;
     if (kCombine) {                                                 // the matches of one class in this wave are added by one lane
-        const int lane = threadIdx.x & (PN2_WAVE - 1);
-        for (int round = 0; round < kRounds; ++round) {
-            const unsigned long long waiting = __ballot(live);
-            if (waiting == 0ull) break;                             // (uniform over the wave; most waves hold no match at all)
-            const int leader = __ffsll((long long)waiting) - 1;
-            const unsigned its = __shfl(cls, leader, PN2_WAVE);
-            const bool same = live && cls == its;
-            const unsigned long long votes = __ballot(same);
-            const unsigned long long sum_hi = wave_sum_u64(same ? hi : 0ull), sum_lo = wave_sum_u64(same ? lo : 0ull);
+        const int lane = threadIdx.x & (PN2_WAVE - 1);              // (most waves hold no match at all)
+        live = pn2_wave_combine<kRounds>(cls, live, [&](bool voter, int leader, unsigned long long votes) {
+            const unsigned long long sum_hi = pn2_wave_sum_u64(voter ? hi : 0ull), sum_lo = pn2_wave_sum_u64(voter ? lo : 0ull);
             if (lane == leader) {
                 add_i64(dst + (int64_t)cls * kColumns + 0, (unsigned long long)__popcll(votes));
                 add_i64(dst + (int64_t)cls * kColumns + 3, sum_hi);
                 add_i64(dst + (int64_t)cls * kColumns + 4, sum_lo);
             }
-            live = live && !same;
-        }
+        });
     }
     if (live) {
         add_i64(dst + (int64_t)cls * kColumns + 0, 1ull);
@@ -229,21 +207,12 @@ __global__ __launch_bounds__(kThreads) void residue_kernel(const int64_t *__rest
     int64_t *dst = out + (int64_t)b * out_stride;
     if (kCombine) {
         const int lane = threadIdx.x & (PN2_WAVE - 1);
-        for (int round = 0; round < kRounds; ++round) {
-            const unsigned long long waiting = __ballot(live);
-            if (waiting == 0ull) break;                             // (uniform over the wave)
-            const int leader = __ffsll((long long)waiting) - 1;
-            const int64_t its = (int64_t)__shfl((long long)word, leader, PN2_WAVE);
-            const bool same = live && word == its;
-            const unsigned long long votes = __ballot(same);
+        live = pn2_wave_combine<kRounds>((long long)word, live, [&](bool, int leader, unsigned long long votes) {
             if (lane == leader) add_i64(dst + word, (unsigned long long)__popcll(votes));
-            live = live && !same;
-        }
+        });
     }
     if (live) add_i64(dst + word, 1ull);
 }
-
-inline unsigned blocks_for(int64_t items) { return (unsigned)(items <= 0 ? 1 : pn2_cdiv(items, kThreads)); }
 
 }  // namespace
 
@@ -267,14 +236,13 @@ int pn2_panoptic_count(const int32_t *pred_sem, const int32_t *pred_inst, const 
     const int64_t cap = pn2_slot_capacity(max_rows);
     Slot *tables = static_cast<Slot *>(workspace);
     const hipStream_t s = pn2_s(stream);
-    const unsigned clear_blocks = blocks_for(cap) < kGridCap ? blocks_for(cap) : kGridCap;
-    hipLaunchKernelGGL(clear_kernel, dim3(clear_blocks, (unsigned)B), dim3(kThreads), 0, s, row_begin, row_count, (int)max_rows, rows,
+    hipLaunchKernelGGL(clear_kernel, dim3(pn2_slot_clear_blocks(cap), (unsigned)B), dim3(kThreads), 0, s, row_begin, row_count, (int)max_rows, rows,
                        reinterpret_cast<uint4 *>(tables), cap);
-    hipLaunchKernelGGL(count_kernel, dim3(blocks_for(max_rows), (unsigned)B), dim3(kThreads), 0, s, pred_sem, pred_inst, gt_sem, gt_inst,
+    hipLaunchKernelGGL(count_kernel, dim3(pn2_slot_blocks(max_rows), (unsigned)B), dim3(kThreads), 0, s, pred_sem, pred_inst, gt_sem, gt_inst,
                        row_begin, row_count, (int)max_rows, rows, C, include, things, tables, cap, err);
-    hipLaunchKernelGGL(match_kernel, dim3(blocks_for(cap), (unsigned)B), dim3(kThreads), 0, s, row_begin, row_count, (int)max_rows, rows,
+    hipLaunchKernelGGL(match_kernel, dim3(pn2_slot_blocks(cap), (unsigned)B), dim3(kThreads), 0, s, row_begin, row_count, (int)max_rows, rows,
                        tables, cap, table, table_stride);
-    hipLaunchKernelGGL(residue_kernel, dim3(blocks_for(2 * cap), (unsigned)B), dim3(kThreads), 0, s, row_begin, row_count, (int)max_rows,
+    hipLaunchKernelGGL(residue_kernel, dim3(pn2_slot_blocks(2 * cap), (unsigned)B), dim3(kThreads), 0, s, row_begin, row_count, (int)max_rows,
                        rows, tables, cap, min_points, table, table_stride);
     return pn2_launch_status();
 }

@@ -15,6 +15,7 @@
 // 2x SLOWER than the atomics), and ~10x fewer atomics than the element-wise scatter.
 #include "pn2_common.h"
 #include "bn_affine.h"
+#include "wave_ops.h"
 #include <stdlib.h>
 
 namespace {
@@ -36,7 +37,7 @@ __global__ __launch_bounds__(256) void invert_count_kernel(const int64_t *__rest
 __global__ __launch_bounds__(1024) void invert_scan_kernel(int *__restrict__ counts, int T, int *__restrict__ offsets) {
     __shared__ int wsum[16];
     __shared__ int carry_s;
-    const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int b = blockIdx.x, t = threadIdx.x;
     int *cnt = counts + (int64_t)b * T;
     int *off = offsets + (int64_t)b * (T + 1);
     if (t == 0) carry_s = 0;
@@ -44,21 +45,10 @@ __global__ __launch_bounds__(1024) void invert_scan_kernel(int *__restrict__ cou
     for (int base = 0; base < T; base += 1024) {
         const int i = base + t;
         const int v = i < T ? cnt[i] : 0;
-        int x = v;                                         // inclusive scan inside the wave
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int y = __shfl_up(x, d, 64);
-            if (lane >= d) x += y;
-        }
-        if (lane == 63) wsum[wave] = x;
-        __syncthreads();
-        int wbase = 0;
-        for (int w = 0; w < wave; ++w) wbase += wsum[w];
-        const int carry = carry_s;
-        const int excl = carry + wbase + x - v;
+        const int excl = pn2_block_excl_scan(v, wsum) + carry_s;
         if (i < T) { off[i] = excl; cnt[i] = excl; }
         __syncthreads();
-        if (t == 1023) carry_s = carry + wbase + x;
+        if (t == 1023) carry_s = excl + v;
         __syncthreads();
     }
     if (t == 0) off[T] = carry_s;
@@ -89,7 +79,7 @@ __global__ __launch_bounds__(1024) void invert_lds_kernel(const int64_t *__restr
                                                           int *__restrict__ offsets) {
     extern __shared__ int inv_lds[];                      // hist[T], then wsum[16], carry
     int *hist = inv_lds, *wsum = inv_lds + T, *carry_s = wsum + 16;
-    const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int b = blockIdx.x, t = threadIdx.x;
     const int64_t *src = idx + (int64_t)b * M;
     int *mem = members + (int64_t)b * M, *own = owners + (int64_t)b * M;
     for (int i = t; i < T; i += 1024) hist[i] = 0;
@@ -107,21 +97,10 @@ __global__ __launch_bounds__(1024) void invert_lds_kernel(const int64_t *__restr
     for (int base = 0; base < T; base += 1024) {          // exclusive scan in place (chunks of 1024, carry in LDS)
         const int i = base + t;
         const int c = i < T ? hist[i] : 0;
-        int x = c;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int y = __shfl_up(x, d, 64);
-            if (lane >= d) x += y;
-        }
-        if (lane == 63) wsum[wave] = x;
-        __syncthreads();
-        int wbase = 0;
-        for (int w = 0; w < wave; ++w) wbase += wsum[w];
-        const int carry = *carry_s;
-        const int excl = carry + wbase + x - c;
+        const int excl = pn2_block_excl_scan(c, wsum) + *carry_s;
         if (i < T) { hist[i] = excl; offsets[(int64_t)b * (T + 1) + i] = excl; }
         __syncthreads();
-        if (t == 1023) *carry_s = carry + wbase + x;
+        if (t == 1023) *carry_s = excl + c;
         __syncthreads();
     }
     const int total = *carry_s;

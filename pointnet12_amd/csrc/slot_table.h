@@ -72,6 +72,14 @@ __device__ __forceinline__ void pn2_slot_fill(uint4 *__restrict__ table, int64_t
     for (int64_t i = (int64_t)blockIdx.x * kSlotThreads + threadIdx.x; i < slots; i += (int64_t)gridDim.x * kSlotThreads) table[i] = pattern;
 }
 
+// workgroups of kSlotThreads threads for one thread per item (a grid is never empty), and for a grid-stride clear of `slots` slots
+constexpr int64_t kSlotGridCap = 1 << 16;
+static inline unsigned pn2_slot_blocks(int64_t items) { return (unsigned)(items <= 0 ? 1 : pn2_cdiv(items, kSlotThreads)); }
+static inline unsigned pn2_slot_clear_blocks(int64_t slots) {      // (capped before it is narrowed: voxel.hip clears B tables in one grid)
+    const int64_t blocks = slots <= 0 ? 1 : pn2_cdiv(slots, kSlotThreads);
+    return (unsigned)(blocks < kSlotGridCap ? blocks : kSlotGridCap);
+}
+
 namespace {
 
 __global__ __launch_bounds__(kSlotThreads) void pn2_slot_clear_kernel(uint4 *__restrict__ table, int64_t slots, uint4 pattern) {

@@ -5,7 +5,7 @@
 //   pn2_voxel_grid   at most six plain launches on the caller's stream, no thread ever waits for another thread's write: the
 //   open-addressing table of slot_table.h, then the stable tile compaction of compact.h over "row i stands for its voxel":
 //     pn2_slot_clear_kernel every slot of every cloud's table to (key = EMPTY, lowest row = INT_MAX, population = 0);
-//     voxel_insert_kernel   one thread per row: the cell key of include/pn2.h in fp64, pn2_slot_claim, then atomicMin of the row
+//     voxel_insert_kernel   one thread per row: the cell key of include/pn2.h in fp64 (voxel_cell.h), pn2_slot_claim, then atomicMin of the row
 //                           number and atomicAdd of the population on that slot; the row's slot is remembered in the workspace,
 //                           so no later pass probes again;
 //     voxel_flag_kernel     a LATER launch (the launch boundary orders it behind every insert): row i stands for its voxel iff the
@@ -18,15 +18,14 @@
 //   minimum, the population an integer sum, the order a prefix sum over row numbers.  The result is the same from run to run.
 //
 // This file is built with -ffp-contract=off: q = floor(((double)p - origin) / voxel) is two separately rounded fp64 operations.
-#include <cmath>
 #include "compact.h"
 #include "slot_table.h"
+#include "voxel_cell.h"
 
 namespace {
 
 constexpr int kThreads = 256;                                      // of the one-thread-per-row passes
 constexpr int kNoRow = 0x7FFFFFFF;
-constexpr int kClearBlocks = 1 << 16;
 
 struct alignas(16) Slot {
     unsigned long long key;
@@ -34,18 +33,6 @@ struct alignas(16) Slot {
     int pop;                                                        // valid rows in the voxel
 };
 static_assert(sizeof(Slot) == 16, "one slot is one 16-byte word");
-
-struct Grid {
-    double origin[3], voxel[3];
-};
-
-// the cell of one coordinate, biased to [0, 2^21); false: outside the grid (or not finite)
-__device__ __forceinline__ bool cell_of(float p, double origin, double voxel, unsigned long long &biased) {
-    const double q = floor(((double)p - origin) / voxel);
-    if (!(q >= -1048576.0 && q < 1048576.0)) return false;
-    biased = (unsigned long long)((long long)q + 1048576ll);
-    return true;
-}
 
 template <bool kVec4>
 __global__ __launch_bounds__(kThreads) void voxel_insert_kernel(const float *__restrict__ pts, int ld,
@@ -71,10 +58,8 @@ __global__ __launch_bounds__(kThreads) void voxel_insert_kernel(const float *__r
             const float *p = pts + row * ld;
             x = p[0], y = p[1], z = p[2];
         }
-        unsigned long long cx, cy, cz;
-        if (cell_of(x, grid.origin[0], grid.voxel[0], cx) && cell_of(y, grid.origin[1], grid.voxel[1], cy) &&
-            cell_of(z, grid.origin[2], grid.voxel[2], cz)) {
-            const unsigned long long key = (cx << 42) | (cy << 21) | cz;
+        unsigned long long key;
+        if (pn2_cell_key_of(x, y, z, grid, key)) {
             Slot *tab = table + (int64_t)b * cap;
             slot = pn2_slot_claim(tab, cap - 1, key);
             if (slot >= 0) {                                        // (always: the cloud has at most cap / 2 rows)
@@ -185,11 +170,7 @@ int pn2_voxel_grid(const float *pts, int ld, const int32_t *labels_in, const int
     PN2_CHECK_ARG(pn2_slot_shape_ok(B, max_rows) && ld >= 3 && ld <= 16);
     PN2_CHECK_ARG(pn2_aligned(pts, 4) && pn2_aligned(out_points, 4) && pn2_aligned(workspace, 16));
     Grid grid;
-    for (int a = 0; a < 3; ++a) {
-        PN2_CHECK_ARG(std::isfinite(origin[a]) && std::isfinite(voxel[a]) && voxel[a] > 0.0);
-        grid.origin[a] = origin[a];
-        grid.voxel[a] = voxel[a];
-    }
+    PN2_CHECK_ARG(pn2_grid_from(origin, voxel, grid));
     const Carve ws(B, max_rows);
     const int tiles = ws.compact.tiles;
     const int64_t cap = ws.cap, rows_pad = (int64_t)tiles * kCompactTile, slots = (int64_t)B * cap;
@@ -202,9 +183,8 @@ int pn2_voxel_grid(const float *pts, int ld, const int32_t *labels_in, const int
     const bool vec4 = ld == 4 && pn2_aligned(pts, 16) && pn2_aligned(out_points, 16);
     const hipStream_t s = pn2_s(stream);
     const dim3 by_tile((unsigned)tiles, (unsigned)B), by_row((unsigned)(rows_pad / kThreads), (unsigned)B);
-    const int64_t clear_blocks = pn2_cdiv(slots, kSlotThreads);
-    hipLaunchKernelGGL(pn2_slot_clear_kernel, dim3((unsigned)(clear_blocks < kClearBlocks ? clear_blocks : kClearBlocks)),
-                       dim3(kSlotThreads), 0, s, reinterpret_cast<uint4 *>(table), slots, pn2_slot_empty((unsigned)kNoRow, 0u));
+    hipLaunchKernelGGL(pn2_slot_clear_kernel, dim3(pn2_slot_clear_blocks(slots)), dim3(kSlotThreads), 0, s, reinterpret_cast<uint4 *>(table),
+                       slots, pn2_slot_empty((unsigned)kNoRow, 0u));
     if (vec4)
         hipLaunchKernelGGL(voxel_insert_kernel<true>, by_row, dim3(kThreads), 0, s, pts, ld, row_begin, row_count, (int)max_rows, grid,
                            table, (unsigned)cap, row_slot, rows_pad, err);

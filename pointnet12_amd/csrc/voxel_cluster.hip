@@ -5,7 +5,7 @@
 //   pn2_voxel_components   eight plain launches on the caller's stream, no thread ever waits for another thread's write:
 //     cluster_clear_kernel   every slot of every cloud's table (slot_table.h) to EMPTY, parent[v] = v, the two per-root counters 0;
 //     cluster_insert_kernel  one thread per voxel: does it take part, the cell key of its representative row (fp64, the rule of
-//                            voxel.hip), pn2_slot_claim, the voxel's rank as the payload; the key is remembered per voxel;
+//                            voxel_cell.h), pn2_slot_claim, the voxel's rank as the payload; the key is remembered per voxel;
 //     cluster_link_kernel    a LATER launch, one thread per (voxel, half-neighbour): the 3, 9 or 13 offsets whose first non-zero
 //                            entry is +1 (the other half is the neighbour's job), a read-only probe (pn2_slot_find), then a
 //                            lock-free union on parent[].  INVARIANT: parent[x] <= x, and parent[x] lies in x's component.  Every
@@ -22,15 +22,14 @@
 //   integer sums and the ids are prefix sums over ranks.  The result is the same from run to run.
 //
 // This file is built with -ffp-contract=off: q = floor(((double)p - origin) / voxel) is two separately rounded fp64 operations.
-#include <cmath>
 #include "compact.h"
 #include "slot_table.h"
+#include "voxel_cell.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kNoRank = 0x7FFFFFFF;
-constexpr long long kCells = 1ll << 21;                             // biased cells per axis
 
 struct alignas(16) Slot {
     unsigned long long key;
@@ -38,10 +37,6 @@ struct alignas(16) Slot {
     int unused;
 };
 static_assert(sizeof(Slot) == 16, "one slot is one 16-byte word");
-
-struct Grid {
-    double origin[3], voxel[3];
-};
 
 struct Rule {
     int half;                                                       // half-neighbours per voxel: 3, 9 or 13
@@ -57,14 +52,6 @@ __device__ __forceinline__ void half_offset(int h, int &dx, int &dy, int &dz) {
     dx = (int)((code >> 4) & 3u) - 1;
     dy = (int)((code >> 2) & 3u) - 1;
     dz = (int)(code & 3u) - 1;
-}
-
-// the cell of one coordinate, biased to [0, 2^21); false: outside the grid (or not finite)
-__device__ __forceinline__ bool cell_of(float p, double origin, double voxel, unsigned long long &biased) {
-    const double q = floor(((double)p - origin) / voxel);
-    if (!(q >= -1048576.0 && q < 1048576.0)) return false;
-    biased = (unsigned long long)((long long)q + 1048576ll);
-    return true;
 }
 
 __device__ __forceinline__ int load_parent(const int *p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
@@ -163,10 +150,7 @@ __global__ __launch_bounds__(kThreads) void cluster_insert_kernel(const float *_
                 bits = PN2_CLUSTER_ERR_INDEX;                        // skipped, never addressed
             } else {
                 const float *p = pts + (row_begin[b] + r) * ld;
-                unsigned long long cx, cy, cz;
-                if (cell_of(p[0], grid.origin[0], grid.voxel[0], cx) && cell_of(p[1], grid.origin[1], grid.voxel[1], cy) &&
-                    cell_of(p[2], grid.origin[2], grid.voxel[2], cz)) {
-                    key = (cx << 42) | (cy << 21) | cz;
+                if (pn2_cell_key_of(p[0], p[1], p[2], grid, key)) {
                     Slot *tab = w.table + (int64_t)b * w.cap;
                     const int slot = pn2_slot_claim(tab, (unsigned)pn2_slot_capacity(nv) - 1u, key);
                     // (one writer per slot: a grid's voxels have distinct cells.  The minimum keeps a malformed input, two voxels
@@ -198,7 +182,7 @@ __global__ __launch_bounds__(kThreads) void cluster_link_kernel(const int64_t *_
     const long long nx = (long long)(key >> 42) + dx, ny = (long long)((key >> 21) & (kCells - 1)) + dy,
                     nz = (long long)(key & (kCells - 1)) + dz;
     if (nx < 0 || nx >= kCells || ny < 0 || ny >= kCells || nz < 0 || nz >= kCells) return;
-    const unsigned long long other = ((unsigned long long)nx << 42) | ((unsigned long long)ny << 21) | (unsigned long long)nz;
+    const unsigned long long other = pn2_cell_key((unsigned long long)nx, (unsigned long long)ny, (unsigned long long)nz);
     const Slot *tab = w.table + (int64_t)b * w.cap;
     const int slot = pn2_slot_find(tab, (unsigned)pn2_slot_capacity(nv) - 1u, other);
     if (slot < 0) return;
@@ -326,11 +310,7 @@ int pn2_voxel_components(const float *pts, int ld, const int64_t *row_begin, con
     PN2_CHECK_ARG(row_component == nullptr || inverse != nullptr);
     PN2_CHECK_ARG(pn2_aligned(pts, 4) && pn2_aligned(workspace, 16));
     Grid grid;
-    for (int a = 0; a < 3; ++a) {
-        PN2_CHECK_ARG(std::isfinite(origin[a]) && std::isfinite(voxel[a]) && voxel[a] > 0.0);
-        grid.origin[a] = origin[a];
-        grid.voxel[a] = voxel[a];
-    }
+    PN2_CHECK_ARG(pn2_grid_from(origin, voxel, grid));
     const Carve ws(B, max_rows);
     Rule rule;
     rule.half = connectivity == 6 ? 3 : (connectivity == 18 ? 9 : 13);

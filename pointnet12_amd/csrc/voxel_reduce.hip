@@ -33,7 +33,6 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / PN2_WAVE;
 constexpr int kNonFinite = 255;
 constexpr unsigned kQuietNan = 0x7FC00000u;
-constexpr unsigned kGridCap = 1u << 16;                             // workgroups per cloud of the grid-stride clears
 
 struct alignas(16) Pair {
     unsigned long long key;                                         // rank << 32 | label
@@ -41,7 +40,7 @@ struct alignas(16) Pair {
     int unused;
 };
 static_assert(sizeof(Pair) == 16, "one slot is one 16-byte word");
-static_assert(kThreads == kSlotThreads, "mode_clear_kernel fills its table with pn2_slot_fill");
+static_assert(kThreads == kSlotThreads, "mode_clear_kernel fills its table with pn2_slot_fill; the grids come from pn2_slot_blocks");
 
 // ----------------------------------------------------------------------------------------------------------------- the mean
 // What a lane of the two row passes works on: row i of cloud b (column c), its segment (-1: the lane takes no part) and, for the
@@ -327,7 +326,6 @@ inline int64_t mean_bytes(int B, int64_t max_rows, int C) {
 inline int64_t mode_bytes(int B, int64_t max_rows) {
     return (int64_t)B * pn2_slot_capacity(max_rows) * (int64_t)sizeof(Pair) + pn2_round16((int64_t)B * max_rows * 8);
 }
-inline unsigned blocks_for(int64_t items) { return (unsigned)(items <= 0 ? 1 : pn2_cdiv(items, kThreads)); }
 
 }  // namespace
 
@@ -355,7 +353,7 @@ int pn2_segment_mean(const float *values, int ld, int C, const int32_t *seg, con
     const bool row_per_lane = pn2_opt(PN2_OPT_SEGRED_LANES) == 0;   // (A/B: one row per lane, its columns in a loop)
     const int R = row_per_lane ? PN2_WAVE : PN2_WAVE / C;           // rows per wave of the two row passes
     const hipStream_t s = pn2_s(stream);
-    const dim3 by_word(blocks_for(max_rows * C), (unsigned)B), by_row(blocks_for(pn2_cdiv(max_rows, kWaves * R) * kThreads), (unsigned)B);
+    const dim3 by_word(pn2_slot_blocks(max_rows * C), (unsigned)B), by_row(pn2_slot_blocks(pn2_cdiv(max_rows, kWaves * R) * kThreads), (unsigned)B);
     int *count_here = n_points == nullptr ? rows_of : nullptr;
     hipLaunchKernelGGL(mean_clear_kernel, by_word, dim3(kThreads), 0, s, out_count, (int)max_rows, C, K, S, rows_of);
     if (pn2_opt(PN2_OPT_SEGRED_COMBINE)) {
@@ -380,7 +378,7 @@ int pn2_segment_mean_bwd(const float *grad_out, int ld_out, int C, const int32_t
     PN2_CHECK_ARG(grad_out && seg && row_begin && row_count && out_begin && out_count && n_points && grad_in);
     PN2_CHECK_ARG(pn2_slot_shape_ok(B, max_rows) && C >= 1 && C <= PN2_SEGMENT_MAX_COLS && ld_out >= C && ld_in >= C);
     PN2_CHECK_ARG(pn2_aligned(grad_out, 4) && pn2_aligned(grad_in, 4) && pn2_aligned(seg, 4) && pn2_aligned(n_points, 4));
-    hipLaunchKernelGGL(mean_bwd_kernel, dim3(blocks_for(max_rows * C), (unsigned)B), dim3(kThreads), 0, pn2_s(stream), grad_out, ld_out, C,
+    hipLaunchKernelGGL(mean_bwd_kernel, dim3(pn2_slot_blocks(max_rows * C), (unsigned)B), dim3(kThreads), 0, pn2_s(stream), grad_out, ld_out, C,
                        seg, row_begin, row_count, (int)max_rows, out_begin, out_count, n_points, grad_in, ld_in, err);
     return pn2_launch_status();
 }
@@ -394,9 +392,8 @@ int pn2_segment_mode(const int32_t *labels, const int32_t *seg, const int64_t *r
     Pair *table = static_cast<Pair *>(workspace);
     unsigned long long *winner = reinterpret_cast<unsigned long long *>(static_cast<unsigned char *>(workspace) + (int64_t)B * cap * (int64_t)sizeof(Pair));
     const hipStream_t s = pn2_s(stream);
-    const unsigned clear_blocks = blocks_for(cap) < kGridCap ? blocks_for(cap) : kGridCap;
-    const dim3 by_row(blocks_for(max_rows), (unsigned)B);
-    hipLaunchKernelGGL(mode_clear_kernel, dim3(clear_blocks, (unsigned)B), dim3(kThreads), 0, s, row_count, out_count, (int)max_rows,
+    const dim3 by_row(pn2_slot_blocks(max_rows), (unsigned)B);
+    hipLaunchKernelGGL(mode_clear_kernel, dim3(pn2_slot_clear_blocks(cap), (unsigned)B), dim3(kThreads), 0, s, row_count, out_count, (int)max_rows,
                        reinterpret_cast<uint4 *>(table), cap, winner);
     if (pn2_opt(PN2_OPT_SEGRED_COMBINE))
         hipLaunchKernelGGL(mode_insert_kernel<true>, by_row, dim3(kThreads), 0, s, labels, seg, row_begin, row_count, (int)max_rows,
@@ -404,7 +401,7 @@ int pn2_segment_mode(const int32_t *labels, const int32_t *seg, const int64_t *r
     else
         hipLaunchKernelGGL(mode_insert_kernel<false>, by_row, dim3(kThreads), 0, s, labels, seg, row_begin, row_count, (int)max_rows,
                            out_count, table, cap, err);
-    hipLaunchKernelGGL(mode_vote_kernel, dim3(blocks_for(cap), (unsigned)B), dim3(kThreads), 0, s, row_count, out_count, (int)max_rows, table,
+    hipLaunchKernelGGL(mode_vote_kernel, dim3(pn2_slot_blocks(cap), (unsigned)B), dim3(kThreads), 0, s, row_count, out_count, (int)max_rows, table,
                        cap, winner);
     hipLaunchKernelGGL(mode_decode_kernel, by_row, dim3(kThreads), 0, s, out_begin, out_count, (int)max_rows, winner, fill, out_labels, votes);
     return pn2_launch_status();
