@@ -846,6 +846,42 @@ int pn2_knn_vote(const int64_t *idx, const float *dist, const int64_t *cand_labe
                  const int64_t *n_query, int32_t fill, const int32_t *lut, int L, const int32_t *dst, int64_t out_stride,
                  int32_t *out, int32_t *err, pn2_stream_t stream);
 
+/* ---- local PCA: surface normals and covariance eigenvalues over neighbour lists (csrc/normals.hip), added within ABI 15 (purely
+ * additive: no version change) ----------
+ * For every row of idx: the covariance of the row's neighbourhood, its three eigenvalues and the unit eigenvector of the
+ * smallest (the surface normal).  One plain launch on the caller's stream; no allocation, no host synchronisation, no atomics
+ * except the OR into err; no output depends on the order in which lanes run, so the bytes are the same from run to run.
+ *   cand [B,M,ldc], query [B,N,ldq] fp32, 3 <= ld <= 16, columns 0..2 = x, y, z (a [., 4] scan is read where it lies).  query is
+ *        read only for the sign and may be NULL when viewpoint is NULL; a self-search passes the same pointer twice.
+ *   idx  [B,N,K] int64 as pn2_knn (or pn2_ball_query) writes it, any K >= 1.   dist [B,N,K] fp32, may be NULL (no cut-off).
+ *   n_query  device int64 [B] or NULL, pn2_knn's meaning: rows at and beyond the count are left untouched in every output.
+ *   viewpoint  device fp32 [B,3] or NULL.
+ *   normal [B,N,ldn] (ldn >= 3; ONLY columns 0..2 of each row are written: the pointer may be offset into a wider row),
+ *   eig fp32 [B,N,3], cov fp64 [B,N,6], count int32 [B,N]: each may be NULL.  err: device int32, caller zeroes, may be NULL.
+ * VALID SLOTS.  Slot k of a row is valid iff 0 <= idx[k] < M and !(dist[k] > max_d2) -- pn2_knn_vote's predicate: pn2_knn's
+ *   empty slots (idx = M) drop out.  n = the number of valid slots.  A candidate that appears several times counts once per
+ *   appearance (pn2_ball_query pads by repetition: those are its weights, as in the vote).
+ * COVARIANCE, IEEE fp64, one pass in ascending slot order, nothing fused.  p0 = the first valid slot's point;
+ *   d = double(p) - double(p0) (exact);  S1 += d;  S2_ab += d_a * d_b for the six a <= b;  m = S1 / n;
+ *   C_ab = S2_ab / n - m_a * m_b   (divisor n, not n - 1).   cov = xx, xy, xz, yy, yz, zz of C, bit for bit this statement.
+ *   (The shift by a member of the neighbourhood is what makes one pass safe: |d| is of the size of the neighbourhood.)
+ * EIGEN-SOLVE, fp64: l0 <= l1 <= l2 the eigenvalues of C, a computed value below zero written as +0.0; eig = the three rounded
+ *   to fp32; u = a unit eigenvector of l0.  Cyclic Jacobi, a fixed number of sweeps (csrc/sym_eig3.h): a C that is already
+ *   diagonal is not rotated, u is then the axis of its smallest entry, the lowest axis among equal entries.
+ * SIGN.  With a viewpoint v: s = (u_x w_x + u_y w_y) + u_z w_z in fp64, w = double(v) - double(q), q the row's query point;
+ *   u is flipped iff s < 0.  Without a viewpoint, or when s == 0: flipped iff u_z < 0; if u_z == 0, iff u_y < 0; if that is 0 too,
+ *   iff u_x < 0 (align with +z, then +y, then +x).  normal = the signed u rounded to fp32.
+ * DEGENERATE ROWS.  n < 3: normal = three +0.0, eig and cov what the rule gives (all +0.0 for n = 0), count = n,
+ *   *err |= PN2_PCA_ERR_FEW.  A valid slot's point not finite, or the query's while a viewpoint is in use: normal and eig are
+ *   the quiet NaN 0x7FC00000, cov 0x7FF8000000000000, count = n, *err |= PN2_PCA_ERR_NONFINITE (and not PN2_PCA_ERR_FEW).
+ * PN2_EINVAL, nothing launched and every output untouched: a null cand or idx, a viewpoint without a query, non-positive sizes,
+ * a pitch out of range (ldc, ldq of a given query outside [3,16], ldn < 3 with a normal), B > 65535, N > 2^31 - 256. */
+#define PN2_PCA_ERR_FEW 1
+#define PN2_PCA_ERR_NONFINITE 2
+int pn2_local_pca(const float *query, int ldq, const float *cand, int ldc, const int64_t *idx, const float *dist, int B, int N, int M,
+                  int K, float max_d2, const int64_t *n_query, const float *viewpoint, float *normal, int ldn, float *eig, double *cov,
+                  int32_t *count, int32_t *err, pn2_stream_t stream);
+
 /* ---- voxel-grid downsampling (csrc/voxel.hip), added within ABI 15 (purely additive: no version change) ------------------------------
  * One row per occupied cell of a regular grid, for a batch of B clouds that lie back to back in device memory (the conventions
  * of pn2_scan_filter: device-side row_begin / row_count / out_begin, a host bound max_rows that sizes the grid of workgroups and

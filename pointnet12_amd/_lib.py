@@ -114,6 +114,7 @@ SIGNATURES = {
     "pn2_scan_filter": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pn2_knn": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "pn2_knn_vote": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _i, _vp, _i, _vp, _i64, _vp, _vp, _vp]),
+    "pn2_local_pca": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "pn2_voxel_grid_workspace_bytes": (_i64, [_i, _i64]),
     "pn2_voxel_grid": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pn2_segment_reduce_workspace_bytes": (_i64, [_i, _i64, _i]),
@@ -143,6 +144,7 @@ IMAGE_RGB, IMAGE_HSV = 0, 1               # PN2_IMAGE_* of include/pn2.h: pn2_sa
 IMAGE_ERR_ROWS = 1                        # PN2_IMAGE_ERR_ROWS: a cloud's rows left the buffers and were skipped
 KNN_MAX_K = 32           # pn2_knn / pn2_knn_vote: larger K is PN2_EUNSUPPORTED
 KNN_ERR_LABEL, KNN_ERR_DST = 1, 2        # the err bits of pn2_knn_vote
+PCA_ERR_FEW, PCA_ERR_NONFINITE = 1, 2     # PN2_PCA_ERR_* of include/pn2.h: the err bits of pn2_local_pca
 VOXEL_TILE = 1024        # PN2_VOXEL_TILE of include/pn2.h: rows per workgroup of pn2_voxel_grid's compaction passes
 VOXEL_MAX_ROWS = 1 << 29                 # PN2_VOXEL_MAX_ROWS: the largest max_rows of pn2_voxel_grid
 VOXEL_ERR_RANGE, VOXEL_ERR_ROWS = 1, 2   # PN2_VOXEL_ERR_* of include/pn2.h

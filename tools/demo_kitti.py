@@ -2,7 +2,7 @@
 """One frame of the reference's KITTI demo (``python pcdvis.py``) on the HIP library: scan -> labels -> pixels -> two images,
 three with ``--ego``.
 
-    python tools/demo_kitti.py [--out DIR] [--npoints 25000] [--seed 0] [--merge] [--time] [--raw [--labels-out FILE [--instances SIZE]]] [--ego CAMERA.json [--render-option FILE.json]] [--image FILE]
+    python tools/demo_kitti.py [--out DIR] [--npoints 25000] [--seed 0] [--merge] [--time] [--raw [--labels-out FILE [--instances SIZE]] [--normals K[:RADIUS]]] [--ego CAMERA.json [--render-option FILE.json]] [--image FILE]
     python tools/demo_kitti.py --root $KITTI_ROOT --part 01 --index 0 --calib DIR --config semantic-kitti.yaml [--checkpoint CKPT]
 
 Without ``--root`` the scan is synthetic (``synthetic.kitti_cloud``, un-normalised back to metres), the calibration is the one
@@ -35,6 +35,12 @@ for none, and the low halves are what they are without the option, byte for byte
 ``--voxel SIZE`` (with ``--raw``) downsamples the kept rows to one row per occupied cell of SIZE metres before the choice
 (``voxel.VoxelGrid``, ``pn2_voxel_grid``), which is then drawn from the voxel count.  ``--voxel-reduce mean`` shows each cell's mean row
 (centroid and mean remission, ``pn2_segment_mean``) instead of its first, ``--voxel-labels mode`` takes the cell's majority label.
+
+``--normals K[:RADIUS]`` (with ``--raw``) writes one more picture, ``normals.png``: the surface normal of every drawn row from its K
+nearest drawn rows (within RADIUS metres, if given), turned towards the scanner (``normals.estimate_normals(viewpoint="origin")``,
+``pn2_knn`` + ``pn2_local_pca``), as the camera view with colour ``round(127.5 * (n + 1))`` per component
+(``draw_2d_points(labels=None, colors=)``); a row with fewer than three neighbours in reach has a zero normal and is mid-grey.
+Without the option the tool's output is what it is without it, byte for byte.
 
 ``--time`` prints one JSON line with medians of 20 (device work included, host clock) for the post-network stages --
 predict + project + both images (``render_ms``), and the same as a captured graph (``render_graph_ms``) -- and beside them, in
@@ -214,6 +220,7 @@ def main():
     ap.add_argument("--labels-out", metavar="FILE", help="with --raw: label every row of the scan (label_scan) and write a .label file")
     ap.add_argument("--instances", type=float, metavar="SIZE",
                     help="with --labels-out: Euclidean clustering of the thing classes on a grid of SIZE metres; instance ids in the high halves")
+    ap.add_argument("--normals", metavar="K[:RADIUS]", help="with --raw: also write normals.png, the drawn rows' surface normals as colours")
     ap.add_argument("--voxel", type=float, metavar="SIZE", help="with --raw: voxel-grid downsample the kept rows at SIZE metres")
     ap.add_argument("--voxel-reduce", choices=("first", "mean"), default="first",
                     help="with --voxel: a cell is shown by its first row or by the mean of its rows")
@@ -266,6 +273,8 @@ def main():
         ap.error("--voxel-reduce / --voxel-labels need --voxel")
     if args.voxel is not None and not args.raw:
         ap.error("--voxel needs --raw")
+    if args.normals and not args.raw:
+        ap.error("--normals needs --raw")
     camera = V.PinholeCamera.from_json(args.ego) if args.ego else None
     option = V.RenderOption.from_json(args.render_option) if args.render_option else V.RenderOption()
     seg = V.FrameSegmenter(model, calib, colors if groups is None else groups.colors, npoints=args.npoints, image_size=size, groups=groups,
@@ -310,6 +319,15 @@ def main():
         painted = V.draw_2d_points(pix, None, out["point_colors"].to(torch.uint8), None, size)
         Image.fromarray(painted.cpu().numpy()).save(os.path.join(args.out, "painted.png"))
         print("%d of %d drawn rows inside the camera frame; wrote %s/painted.png" % (int(valid.sum()), args.npoints, args.out))
+    if args.normals:
+        from pointnet12_amd import normals as PN
+        k, _, radius = args.normals.partition(":")
+        n = PN.estimate_normals(seg.raw_rows, k=int(k), radius=float(radius) if radius else None, viewpoint="origin")
+        shade = torch.round(127.5 * (n + 1.0)).clamp(0, 255).to(torch.uint8)
+        picture = V.draw_2d_points(out["pix"], None, shade, None, size)
+        Image.fromarray(picture.cpu().numpy()).save(os.path.join(args.out, "normals.png"))
+        print("normals of %d drawn rows from %s neighbours%s, %d of them zero (fewer than three in reach); wrote %s/normals.png"
+              % (len(n), k, " within %s m" % radius if radius else "", int((n == 0).all(1).sum()), args.out))
     counts = torch.bincount(out["pred"], minlength=len(colors)).cpu().tolist()
     drawn = int((out["pix"][:, 0] != V.INT32_MIN).sum())
     print("scan of %d points resampled to %d; %d with a pixel, %d classes predicted; error flag %d; wrote %s/semantic.png and top_view.png"
