@@ -882,6 +882,60 @@ int pn2_local_pca(const float *query, int ldq, const float *cand, int ldc, const
                   int K, float max_d2, const int64_t *n_query, const float *viewpoint, float *normal, int ldn, float *eig, double *cov,
                   int32_t *count, int32_t *err, pn2_stream_t stream);
 
+/* ---- grid kNN: k nearest within a radius on a uniform grid (csrc/grid_knn.hip), added within ABI 15 (purely additive: no version
+ * change) ----------
+ * pn2_grid_build bins the candidates of B clouds by cell once; pn2_grid_knn lets every query look at the 27 cells around its own.
+ * Plain launches on the caller's stream (six for the build, one for a search); no allocation, no host synchronisation, no thread
+ * waits for another thread's write, no float atomics.  THE RESULT IS DEFINED BY THE GRID, not as "equal to brute force"; when
+ * cell[a] >= sqrt((double)max_d2) * (1 + 2^-20) on every axis it EQUALS the brute-force "K nearest with d2 <= max_d2" in the same
+ * arithmetic ("Grid kNN", has the derivation).
+ *   cand [B,M,ldc], query [B,N,ldq] fp32, 3 <= ld <= 16, columns 0..2 = x, y, z (a [., 4] scan is read where it lies): pn2_knn's dense
+ *        layout, so idx / dist feed pn2_knn_vote and pn2_local_pca unchanged.
+ *   n_cand / n_query  device int64 [B] or NULL (= M / N), clamped to [0,M] / [0,N]: only the first n_cand[b] candidates are indexed;
+ *        rows at and beyond n_query[b] are left untouched in every output.
+ *   origin, cell   HOST double[3] each: cell[a] finite and > 0, origin[a] finite (pn2_voxel_grid's check).
+ * CELL.  pn2_voxel_grid's rule, shared (csrc/voxel_cell.h): per axis q_a = floor(((double)p_a - origin[a]) / cell[a]), IEEE fp64, each
+ *   operation rounded on its own; a row is VALID iff -2^20 <= q_a < 2^20 on all three axes (NaN and +-inf fail); the key is the same
+ *   63-bit word.
+ * INVALID ROWS.  An invalid CANDIDATE is not indexed and never returned; it sets PN2_GRID_ERR_CAND (in pn2_grid_build's err).  An
+ *   invalid QUERY gets every slot empty and count = 0; it sets PN2_GRID_ERR_QUERY (in pn2_grid_knn's err).
+ * CANDIDATE SET of a query: the indexed candidates of its own cloud whose cell differs from the query's by d in {-1,0,1}^3 -- 27
+ *   cells, the centre included.  A neighbour cell outside [-2^20, 2^20) on any axis does not exist (checked per axis BEFORE the
+ *   key is formed).  Clouds never share cells, even at equal coordinates.
+ * DISTANCE.  Difference form in fp32, pn2_chamfer_nn's arithmetic at D = 3 bit for bit: t_a = q_a - p_a; d2 = t_x * t_x;
+ *   d2 = fmaf(t_y, t_y, d2); d2 = fmaf(t_z, t_z, d2).  (Deliberately not pn2_knn's expanded form: at scan scale that carries about
+ *   5e-4 m^2 of cancellation error, comparable with a small cut-off.)
+ * SELECTION.  The candidates of the set with d2 <= max_d2 take part (a NaN d2 fails; max_d2 = +inf is allowed: "the K nearest of the
+ *   27 cells").  The result is the first K of them in ascending (d2, candidate index) order, the compare lexicographic on the PAIR:
+ *   it does not depend on the order in which candidates are met.  Empty slots hold idx = M, dist = +inf as pn2_knn writes them.  A
+ *   candidate that appears several times among the M is several candidates.  There is no K <= M requirement: short rows pad.
+ *   idx int64 [B,N,K];  dist fp32 [B,N,K] or NULL;  count int32 [B,N] or NULL: the number of candidates that took part, NOT capped
+ *   by K (the ball's population: count > K says K truncated).  err: device int32, caller zeroes, may be NULL.
+ * SELF-SEARCH.  query == NULL (then N must equal M, ldq and n_query are ignored): the queries are the candidates themselves, the
+ *   coordinates the build copied; every row below the candidate count THE BUILD READ is written (an indexed row finds itself at
+ *   d2 = 0, an invalid row as above).  flags = PN2_GRID_VISIT_SORTED: lane i serves the i-th RECORD of the cell-sorted copy and
+ *   writes at that record's row, so neighbouring lanes walk the same cells; without it, and always with a query, lane i serves
+ *   row i.  The outputs are byte-identical either way.
+ * WORKSPACE.  pn2_grid_workspace_bytes(B, M) bytes of device memory, 16-byte aligned.  UNLIKE THE OTHER WORKSPACES OF THIS LIBRARY IT
+ *   PERSISTS: it may hold anything before pn2_grid_build, which fills it, and every pn2_grid_knn that uses it reads it (and
+ *   writes nothing to it), with the same B, M, origin and cell as the build.  One build serves any number of searches.  Per cloud:
+ *   a table of the power of two >= 2 * M slots of 16 bytes, a 16-byte record and a 4-byte word per row.
+ * Everything is the same from run to run, byte for byte: which slot a cell lands in and the order of the records inside a cell
+ * differ, but populations and starts are integer sums and the selection compares pairs.
+ * 1 <= K <= 32; K > 32: PN2_EUNSUPPORTED, nothing launched.  PN2_EINVAL, nothing launched and nothing written: a null cand / origin /
+ * cell / workspace / idx, B < 1 or B > 65535, M < 1 or M > PN2_VOXEL_MAX_ROWS, N < 1 or N > 2^31 - 256, K < 1, a pitch outside 3..16,
+ * a self-search with N != M, unknown flags, cand / query not 4-byte or workspace not 16-byte aligned, a bad grid;
+ * pn2_grid_workspace_bytes returns PN2_EINVAL for such B / M. */
+#define PN2_GRID_ERR_CAND 1
+#define PN2_GRID_ERR_QUERY 2
+#define PN2_GRID_VISIT_SORTED 1          /* flags of pn2_grid_knn */
+int64_t pn2_grid_workspace_bytes(int B, int64_t M);
+int pn2_grid_build(const float *cand, int ldc, int B, int M, const int64_t *n_cand, const double *origin, const double *cell,
+                   int32_t *err, void *workspace, pn2_stream_t stream);
+int pn2_grid_knn(const float *query, int ldq, int B, int N, int M, int K, float max_d2, const int64_t *n_query,
+                 const double *origin, const double *cell, const void *workspace, int flags,
+                 int64_t *idx, float *dist, int32_t *count, int32_t *err, pn2_stream_t stream);
+
 /* ---- voxel-grid downsampling (csrc/voxel.hip), added within ABI 15 (purely additive: no version change) ------------------------------
  * One row per occupied cell of a regular grid, for a batch of B clouds that lie back to back in device memory (the conventions
  * of pn2_scan_filter: device-side row_begin / row_count / out_begin, a host bound max_rows that sizes the grid of workgroups and

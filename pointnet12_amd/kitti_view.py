@@ -954,7 +954,7 @@ class FrameSegmenter:
         return out
 
     def label_scan(self, raw_scan, raw_label=None, scan_filter=None, rng="numpy", k=5, max_dist=1.0, lut=None, background=None,
-                   choice=None, max_rows=None, voxel=None, instances=None, image=None):
+                   choice=None, max_rows=None, voxel=None, instances=None, image=None, search="brute"):
         """``frame_raw``, then a label for EVERY row of the raw scan.  The network labels ``npoints`` rows drawn with
         replacement (about ``exp(-npoints / count)`` of the kept rows are never drawn); here each kept row takes the majority
         label of its ``k`` nearest drawn rows (``pointnet_util.propagate_labels``: queries = the kept rows' xyz with the
@@ -979,8 +979,11 @@ class FrameSegmenter:
         device); ``"kept_classes"`` (int32: the kept rows' predicted classes, the first ``count`` entries mean something) and
         ``"kept_instances"`` (int32: their ids, -1 for none -- an ``inverse``-style map for ``voxel.segment_mean``).  Ids are numbered by
         each instance's lowest kept row.  With a device generator nothing is read back.  ``kitti.write_labels(fn, scan_labels,
-        scan_instances)`` writes both halves of the ``.label`` words.  ``instances=None`` leaves this call exactly as it was."""
-        from . import pointnet_util as U
+        scan_instances)`` writes both halves of the ``.label`` words.  ``instances=None`` leaves this call exactly as it was.
+
+        ``search``: ``propagate_labels``' -- ``"grid"`` searches on a uniform grid of ``max_dist`` cells instead of by brute force
+        (it needs a ``max_dist``)."""
+        from . import neighbors, pointnet_util as U
         out = self.frame_raw(raw_scan, raw_label, scan_filter, rng, background, choice, max_rows, voxel, image)
         held = self._raw_state
         rows, n, M = held["rows"], self.npoints, int(raw_scan.shape[0])
@@ -991,10 +994,15 @@ class FrameSegmenter:
             work = held["knn"] = ((rows, k), torch.empty(rows, k, device=dev, dtype=torch.int64),
                                   torch.empty(rows, k, device=dev, dtype=torch.float32), torch.empty(rows, device=dev, dtype=torch.int32))
         _, idx, dist, scan_labels = work
+        grid_ws = ()
+        if search == "grid":
+            if held.get("grid_ws") is None or held["grid_ws"].numel() < neighbors.workspace_bytes(n, 1):
+                held["grid_ws"] = torch.empty(neighbors.workspace_bytes(n, 1), device=self.device, dtype=torch.uint8)
+            grid_ws = (held["grid_ws"],)
         scan_labels.zero_()
         U.propagate_labels(held["out"].points[:, :3].contiguous().view(1, rows, 3), self.raw_rows[:, :3].contiguous().view(1, n, 3),
                            self.pred.view(1, n), k=k, max_dist=max_dist, fill=0, lut=lut, dst=out["index"], out=scan_labels,
-                           n_query=out["count"], err=self.error_flag, work=(idx, dist))
+                           n_query=out["count"], err=self.error_flag, work=(idx, dist) + grid_ws, search=search)
         out["scan_labels"] = scan_labels[:M]
         if instances is not None:
             self._scan_instances(out, instances, held, idx, dist, k, max_dist, M)

@@ -4,13 +4,14 @@ under "local PCA" and in numpy in tests/normals_ref.py).
 The reference repository has no such function: like kNN, the voxel grid, clustering and Lovasz this is an extension.  For every
 point, the covariance of its neighbourhood (fp64, one pass), its three eigenvalues ``l0 <= l1 <= l2`` and the unit eigenvector
 of ``l0`` -- which way the surface faces, and how flat it is.  OUT OF SCOPE: a gradient through the normals; a consistent
-orientation by propagation along a spanning tree (the sign is per point: towards a viewpoint, or +z, +y, +x); a grid-accelerated
-neighbour search (``estimate_normals`` searches with ``pn2_knn``'s brute force: grid a large scan first); weighted neighbourhoods.
+orientation by propagation along a spanning tree (the sign is per point: towards a viewpoint, or +z, +y, +x); weighted
+neighbourhoods.  (``estimate_normals`` searches with ``pn2_knn``'s brute force by default; ``search="grid"`` takes the uniform grid of
+``neighbors.GridIndex`` instead, which is what a whole scan needs.)
 """
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, neighbors
 
 _p = _lib.ptr
 
@@ -39,16 +40,24 @@ def _counts(n, B, device, what):
 class NormalBuffers:
     """Everything ``estimate_normals`` / ``local_pca`` write, allocated once (``buffers``).  ``normal`` float32 [B,N,3], ``eig``
     float32 [B,N,3], ``cov`` float64 [B,N,6] (xx, xy, xz, yy, yz, zz), ``count`` int32 [B,N]; ``xyz`` / ``idx`` / ``dist``: the
-    packed copy and the neighbour lists of ``estimate_normals``; ``origin``: a zero viewpoint.  ``error_flag`` (device int32,
+    packed copy and the neighbour lists of ``estimate_normals``; ``origin``: a zero viewpoint.  ``grid`` (``search="grid"``): the
+    ``neighbors.GridBuffers`` of the grid search, whose ``idx`` / ``dist`` these then are.  ``error_flag`` (device int32,
     cleared at the start of every call that is given these buffers) collects ``_lib.PCA_ERR_FEW`` (a row with fewer than three
     valid neighbours: its normal is zero) and ``_lib.PCA_ERR_NONFINITE`` (a NaN / inf point: the row holds NaN)."""
 
-    def __init__(self, N, B, k, device, cov=True):
+    def __init__(self, N, B, k, device, cov=True, search="brute"):
         self.B, self.N, self.k = int(B), int(N), int(k)
         self.xyz = torch.zeros(B, N, 3, device=device, dtype=torch.float32)
         self.device = self.xyz.device                                # ("cuda" resolved to the current device's index)
-        self.idx = torch.zeros(B, N, k, device=device, dtype=torch.int64)
-        self.dist = torch.zeros(B, N, k, device=device, dtype=torch.float32)
+        self.grid = None
+        if search == "grid":
+            self.grid = neighbors.GridBuffers(N, B, N, k, self.device)
+            self.idx, self.dist = self.grid.idx, self.grid.dist
+        elif search == "brute":
+            self.idx = torch.zeros(B, N, k, device=device, dtype=torch.int64)
+            self.dist = torch.zeros(B, N, k, device=device, dtype=torch.float32)
+        else:
+            raise ValueError("normals.buffers: search must be \"brute\" or \"grid\"")
         self.normal = torch.zeros(B, N, 3, device=device, dtype=torch.float32)
         self.eig = torch.zeros(B, N, 3, device=device, dtype=torch.float32)
         self.cov = torch.zeros(B, N, 6, device=device, dtype=torch.float64) if cov else None
@@ -66,11 +75,12 @@ class NormalBuffers:
             raise ValueError("local_pca: a row has fewer than three valid neighbours; its normal is zero")
 
 
-def buffers(N, B=1, k=16, device="cuda", cov=True):
+def buffers(N, B=1, k=16, device="cuda", cov=True, search="brute"):
     """Preallocates for ``N`` rows per cloud, ``B`` clouds and ``k`` neighbours.  With ``buffers=`` a call allocates nothing, reads
     nothing back and captures into a graph that stays valid when the device-side counts (``n_points`` / ``n_query``) change.
-    (A ``viewpoint`` must then be a device tensor or ``"origin"``: a host triple would be copied in.)"""
-    return NormalBuffers(N, B, k, device, cov)
+    (A ``viewpoint`` must then be a device tensor or ``"origin"``: a host triple would be copied in.)  ``search="grid"`` adds the grid
+    search's workspace (``estimate_normals(search="grid")`` needs it; the brute-force search runs on such buffers too)."""
+    return NormalBuffers(N, B, k, device, cov, search)
 
 
 def _viewpoint(v, B, dev, buf, what):
@@ -182,7 +192,7 @@ def local_pca(points, idx, dist=None, query=None, max_dist=None, viewpoint=None,
 
 
 def estimate_normals(points, k=16, radius=None, viewpoint=None, n_points=None, out=None, out_col=0, return_eig=False, return_cov=False,
-                     return_count=False, err=None, buffers=None):
+                     return_count=False, err=None, buffers=None, search="brute"):
     """Normals of a cloud from its own points: a self-search for the ``min(k, M)`` nearest neighbours (``pn2_knn``; the point itself
     is one of them), of which those within ``radius`` count -- the "k nearest within r" search normal estimation conventionally
     uses -- then ``local_pca``.  ``points`` [M,ld] or [B,M,ld] float32 (a [., 4] scan as it lies; one packed xyz copy is made
@@ -190,8 +200,16 @@ def estimate_normals(points, k=16, radius=None, viewpoint=None, n_points=None, o
     ``n_points``: device int64 [B] (or host integers), only that many leading rows of each cloud are searched and written.
     The other arguments and the return value are ``local_pca``'s.
 
-    THE SEARCH IS BRUTE FORCE (M x M pairs: a 120 000-row scan against itself is 1.4e10): downsample or crop a large scan first
-    (``voxel.VoxelGrid``, ``kitti.ScanFilter``).  ``k`` above ``_lib.KNN_MAX_K`` raises."""
+    BY DEFAULT THE SEARCH IS BRUTE FORCE (M x M pairs: a 120 000-row scan against itself is 1.4e10).  ``search="grid"`` bins the
+    cloud on a uniform grid of cells one ``radius`` wide first (``neighbors.GridIndex``; it needs a ``radius``, else
+    ``ValueError``) and looks at 27 cells per row: the [., ld] rows are read where they lie, no packed copy is made, and the
+    neighbour lists go to ``local_pca`` with the same cut-off.  Its distances are in difference form, ``pn2_knn``'s in expanded
+    form: off a lattice the two may order near-ties differently, and a row that is not finite finds no neighbours
+    (``PCA_ERR_FEW``) instead of poisoning its own (``PCA_ERR_NONFINITE``).  ``k`` above ``_lib.KNN_MAX_K`` raises."""
+    if search not in ("brute", "grid"):
+        raise ValueError("estimate_normals: search must be \"brute\" or \"grid\"")
+    if search == "grid" and radius is None:
+        raise ValueError("estimate_normals: search=\"grid\" needs a radius (the grid's cell)")
     flat = isinstance(points, torch.Tensor) and points.dim() == 2
     pts = _points(points, "points")
     B, M, _ = pts.shape
@@ -202,9 +220,16 @@ def estimate_normals(points, k=16, radius=None, viewpoint=None, n_points=None, o
     if k > _lib.KNN_MAX_K:
         raise RuntimeError("estimate_normals: k (%d) > %d is not supported (there is no fallback path)" % (k, _lib.KNN_MAX_K))
     buf = buffers
-    if buf is not None:
-        if buf.B != B or buf.N != M or buf.k < k or buf.device != dev:
-            raise ValueError("estimate_normals: the buffers were made for B = %d, N = %d, k >= %d on %s" % (buf.B, buf.N, buf.k, buf.device))
+    if buf is not None and (buf.B != B or buf.N != M or buf.k < k or buf.device != dev):
+        raise ValueError("estimate_normals: the buffers were made for B = %d, N = %d, k >= %d on %s" % (buf.B, buf.N, buf.k, buf.device))
+    n_points = _counts(n_points, B, dev, "estimate_normals: n_points")
+    if search == "grid":
+        if buf is not None and buf.grid is None:
+            raise ValueError("estimate_normals: these buffers hold no grid workspace (normals.buffers(..., search=\"grid\"))")
+        index = neighbors.GridIndex(radius=radius).build(pts, n_cand=n_points, buffers=None if buf is None else buf.grid)
+        idx, dist = index.query_self(k, return_dist=True, buffers=None if buf is None else buf.grid)
+        xyz = pts
+    elif buf is not None:
         xyz = buf.xyz
         xyz.copy_(pts[:, :, :3])
         idx = buf.idx.reshape(-1)[:B * M * k].reshape(B, M, k)
@@ -213,8 +238,9 @@ def estimate_normals(points, k=16, radius=None, viewpoint=None, n_points=None, o
         xyz = pts[:, :, :3].contiguous()
         idx = torch.empty(B, M, k, device=dev, dtype=torch.int64)
         dist = torch.empty(B, M, k, device=dev, dtype=torch.float32)
-    n_points = _counts(n_points, B, dev, "estimate_normals: n_points")
-    _lib.check(_lib.load().pn2_knn(_p(xyz), _p(xyz), B, M, M, k, _p(n_points), _p(n_points), _p(idx), _p(dist), _lib.stream()), "pn2_knn")
+    if search == "brute":
+        _lib.check(_lib.load().pn2_knn(_p(xyz), _p(xyz), B, M, M, k, _p(n_points), _p(n_points), _p(idx), _p(dist), _lib.stream()),
+                   "pn2_knn")
     res = local_pca(xyz, idx, dist, query=xyz, max_dist=radius, viewpoint=viewpoint, n_query=n_points,
                     out=out if (out is None or not flat) else out[None], out_col=out_col, return_eig=return_eig, return_cov=return_cov,
                     return_count=return_count, err=err, buffers=buf)

@@ -464,7 +464,7 @@ def _i64_counts(n, B, device, what):
 
 
 def propagate_labels(query_xyz, cand_xyz, cand_labels, k=5, max_dist=None, fill=-1, lut=None, dst=None, out=None, n_query=None,
-                     n_cand=None, err=None, work=None):
+                     n_cand=None, err=None, work=None, search="brute"):
     """Every query point takes the majority label of its ``k`` nearest labelled points: ``pn2_knn`` then ``pn2_knn_vote``.
 
     ``query_xyz`` [B,N,3], ``cand_xyz`` [B,M,3] float32, ``cand_labels`` int64 [B,M] -> int32 [B,N] (or ``out``).  A neighbour
@@ -481,7 +481,17 @@ def propagate_labels(query_xyz, cand_xyz, cand_labels, k=5, max_dist=None, fill=
     candidate of its own -- deliberately: the copies are the draw's weights.
 
     With ``out`` the call allocates only the [B,N,k] neighbour scratch; ``work = (idx int64 [B,N,k], dist float32 [B,N,k])``
-    supplies that too, and a captured call then allocates nothing."""
+    supplies that too, and a captured call then allocates nothing.
+
+    ``search="grid"`` replaces ``pn2_knn``'s brute force by the uniform grid of ``neighbors.GridIndex`` (cells one ``max_dist`` wide,
+    27 of them per query); it needs a ``max_dist``, else ``ValueError``.  The vote is unchanged.  The grid's distances are in
+    difference form, the brute force's in expanded form: the labels agree wherever the two forms agree on which candidates lie
+    within ``max_dist`` and in which order (on a lattice, always).  ``work`` may then carry the grid's workspace as a third entry
+    (uint8, ``neighbors.workspace_bytes(M, B)``)."""
+    if search not in ("brute", "grid"):
+        raise ValueError("propagate_labels: search must be \"brute\" or \"grid\"")
+    if search == "grid" and max_dist is None:
+        raise ValueError("propagate_labels: search=\"grid\" needs a max_dist (the grid's cell)")
     query_xyz, cand_xyz = _gpu_f32(query_xyz, "query_xyz"), _gpu_f32(cand_xyz, "cand_xyz")
     if query_xyz.dim() != 3 or cand_xyz.dim() != 3 or query_xyz.shape[2] != 3 or cand_xyz.shape[2] != 3 or \
             query_xyz.shape[0] != cand_xyz.shape[0]:
@@ -515,7 +525,7 @@ def propagate_labels(query_xyz, cand_xyz, cand_labels, k=5, max_dist=None, fill=
         idx = torch.empty(B, N, k, device=dev, dtype=torch.int64)
         dist = torch.empty(B, N, k, device=dev, dtype=torch.float32)
     else:
-        idx, dist = work
+        idx, dist = work[0], work[1]
         if idx.dtype != torch.int64 or dist.dtype != torch.float32 or idx.numel() < B * N * k or dist.numel() < B * N * k or \
                 not idx.is_contiguous() or not dist.is_contiguous() or idx.device != dev or dist.device != dev:
             raise ValueError("propagate_labels: work must be (int64, float32) contiguous tensors of at least B * N * k entries")
@@ -524,7 +534,17 @@ def propagate_labels(query_xyz, cand_xyz, cand_labels, k=5, max_dist=None, fill=
     n_query, n_cand = _i64_counts(n_query, B, dev, "n_query"), _i64_counts(n_cand, B, dev, "n_cand")
     max_d2 = float("inf") if max_dist is None else float(np.float32(float(max_dist) ** 2))
     lib, st = _lib.load(), _lib.stream()
-    _check(lib.pn2_knn(_p(query_xyz), _p(cand_xyz), B, N, M, k, _p(n_query), _p(n_cand), _p(idx), _p(dist), st), "pn2_knn")
+    if search == "grid":
+        from . import neighbors
+        g = neighbors.GridIndex(radius=max_dist)                    # (the cell, checked; its cut-off is max_d2, the same float)
+        ws = work[2] if work is not None and len(work) > 2 else torch.empty(neighbors.workspace_bytes(M, B), device=dev, dtype=torch.uint8)
+        if ws.dtype != torch.uint8 or ws.device != dev or not ws.is_contiguous() or ws.numel() < neighbors.workspace_bytes(M, B):
+            raise ValueError("propagate_labels: the grid workspace must be a contiguous uint8 tensor of neighbors.workspace_bytes(M, B) bytes")
+        _check(lib.pn2_grid_build(_p(cand_xyz), 3, B, M, _p(n_cand), g._c_origin, g._c_cell, None, _p(ws), st), "pn2_grid_build")
+        _check(lib.pn2_grid_knn(_p(query_xyz), 3, B, N, M, k, max_d2, _p(n_query), g._c_origin, g._c_cell, _p(ws), 0, _p(idx), _p(dist),
+                                None, None, st), "pn2_grid_knn")
+    else:
+        _check(lib.pn2_knn(_p(query_xyz), _p(cand_xyz), B, N, M, k, _p(n_query), _p(n_cand), _p(idx), _p(dist), st), "pn2_knn")
     _check(lib.pn2_knn_vote(_p(idx), _p(dist), _p(cand_labels), B, N, M, k, max_d2, _p(n_query), int(fill), _p(lut),
                             0 if lut is None else int(lut.numel()), _p(dst), stride, _p(out), _p(err), st), "pn2_knn_vote")
     return out
