@@ -936,6 +936,61 @@ int pn2_grid_knn(const float *query, int ldq, int B, int N, int M, int K, float 
                  const double *origin, const double *cell, const void *workspace, int flags,
                  int64_t *idx, float *dist, int32_t *count, int32_t *err, pn2_stream_t stream);
 
+/* ---- ICP step: rigid scan registration on the grid index (csrc/icp.hip), added within ABI 15 (purely additive: no version
+ * change) ----------
+ * pn2_icp_step does ONE Gauss-Newton iteration of point-to-plane or point-to-point ICP for B source clouds, each against its own
+ * target cloud, which pn2_grid_build has binned.  Two plain launches on the caller's stream; no allocation, no host
+ * synchronisation, no float atomics, no thread waits for another thread's write.  tests/icp_ref.py restates the rule in numpy.
+ *   src [B,N,lds], tgt [B,M,ldt] fp32, 3 <= ld <= 16, columns 0..2 = x, y, z.   n_src  device int64 [B] or NULL (= N), clamped to [0,N].
+ *   tgt_normal [B,M,ldn] fp32, 3 <= ldn <= 16, only columns 0..2 are read (it may point into [.,6] rows); NULL for PN2_ICP_POINT.
+ *   origin, cell, grid_workspace: what pn2_grid_build was given and filled for tgt, with the same B, M.  max_d2: pn2_grid_knn's.
+ *   T  device fp64 [B,12], rows of [R | t] (3 x 4, row-major), read and written.   sums fp64 [B,28].   count int64 [B].
+ *   x fp64 [B,6].   status, iters int32 [B], read and written.   corr int64 [B,N] or NULL.   err int32, caller zeroes, or NULL.
+ *   workspace: pn2_icp_workspace_bytes(B, N) bytes of device memory, 8-byte aligned; it may hold anything.
+ * FROZEN CLOUDS.  A cloud whose status has PN2_ICP_CONVERGED or PN2_ICP_SINGULAR set on entry is frozen: none of its outputs is
+ *   touched and its rows are not walked.  PN2_ICP_EVAL_ONLY ignores the freeze (and does not read status).
+ * PER ROW i < n_src[b] of the other clouds, IEEE fp64, each operation rounded on its own, nothing fused:
+ *   s = double(src[i,0..2]);  p_a = ((R_a0 s_0 + R_a1 s_1) + R_a2 s_2) + t_a;  p32 = float(p).
+ *   j = pn2_grid_knn's K = 1 answer for the query p32 with this max_d2: the 27 cells, the fp32 difference-form distance, the
+ *   smallest (d2, index).  No candidate: the row takes no part, corr = M.  p32 not finite or outside the grid: the row takes no
+ *   part, corr = M, *err |= PN2_ICP_ERR_QUERY.  Otherwise corr = j,  q = double(tgt[j]),  e = p - q  (from p, not from p32).
+ *   PLANE: n = double(tgt_normal[j]); n not finite or three zeros (PN2_PCA_ERR_FEW's normal): the row takes no part (corr = j).
+ *     r = (n_x e_x + n_y e_y) + n_z e_z;   J = (c, n) with c_x = p_y n_z - p_z n_y, c_y = p_z n_x - p_x n_z, c_z = p_x n_y - p_y n_x.
+ *     The row's 28 terms: J_k J_l for the 21 pairs k <= l (row-major), J_k r (6), r r.
+ *   POINT: the same three times with n = (1,0,0), (0,1,0), (0,0,1), evaluated as written: 84 terms a row.
+ *   count = the rows that took part (rows, not residuals).
+ * SUMS.  sums[b] = the 28 fp64 sums of these terms: A's upper triangle row-major, b, E.  The order of summation is a function of
+ *   (B, N) alone and is not stated otherwise; it does not depend on how lanes are scheduled: the same bytes from run to run.
+ * SOLVE (not with PN2_ICP_EVAL_ONLY).  A x = -b by fp64 Cholesky in index order.  The cloud is SINGULAR if count < 6 (PLANE) or
+ *   count < 3 (POINT), or a pivot is <= 2^-40 times its original diagonal entry or is not finite: status |= PN2_ICP_SINGULAR,
+ *   *err |= PN2_ICP_ERR_SINGULAR, x = 0, T and iters untouched.  A sum or an entry of T that is not finite: the same with
+ *   PN2_ICP_ERR_NONFINITE in place of PN2_ICP_ERR_SINGULAR.
+ * UPDATE.  w = x[0..2], v = x[3..5], th = sqrt((w_0 w_0 + w_1 w_1) + w_2 w_2), tt = th th.  a = sin(th) / th, b = (1 - cos(th)) / tt;
+ *   below th = 2^-20: a = 1 - tt / 6, b = 1/2 - tt / 24.  K = [w]x, K2 = K K written out (K2_ii = -(w_j w_j + w_k w_k), j < k the
+ *   other two; K2_ij = w_i w_j).  D = (I + a K) + b K2.  R <- D R, t <- D t + v, each entry a left-to-right sum of three products
+ *   (+ v_i); iters += 1.  status |= PN2_ICP_CONVERGED iff th <= tol_rot and sqrt((v_0 v_0 + v_1 v_1) + v_2 v_2) <= tol_trans; the
+ *   update of that step is applied.  (The linearisation rotates about the origin of the target frame: DESIGN.md, "ICP".)
+ * PN2_ICP_EVAL_ONLY: sums, count and corr are written; no solve; T, x, status, iters are untouched and x / status / iters may be NULL.
+ * PN2_EINVAL, nothing launched and nothing written: a null src / tgt / origin / cell / grid_workspace / T / sums / count / workspace
+ * (x / status / iters without PN2_ICP_EVAL_ONLY), B < 1 or B > 65535, N < 1 or N > 2^31 - 256, M < 1 or M > PN2_VOXEL_MAX_ROWS, a pitch
+ * outside 3..16, PN2_ICP_PLANE without normals, an unknown metric or flag, a negative or non-finite tolerance, a bad grid, a
+ * misaligned pointer; pn2_icp_workspace_bytes returns PN2_EINVAL for such B / N. */
+#define PN2_ICP_POINT 0
+#define PN2_ICP_PLANE 1
+#define PN2_ICP_EVAL_ONLY 1        /* flags: accumulate and write sums/count/corr; no solve, T, x, status, iters untouched */
+#define PN2_ICP_CONVERGED 1        /* status bits */
+#define PN2_ICP_SINGULAR  2
+#define PN2_ICP_ERR_QUERY 1        /* err bits */
+#define PN2_ICP_ERR_SINGULAR 2
+#define PN2_ICP_ERR_NONFINITE 4
+int64_t pn2_icp_workspace_bytes(int B, int N);
+int pn2_icp_step(const float *src, int lds, int B, int N, const int64_t *n_src,
+                 const float *tgt, int ldt, int M, const float *tgt_normal, int ldn,
+                 const double *origin, const double *cell, const void *grid_workspace, float max_d2,
+                 int metric, int flags, double tol_rot, double tol_trans,
+                 double *T, double *sums, int64_t *count, double *x, int32_t *status, int32_t *iters,
+                 int64_t *corr, int32_t *err, void *workspace, pn2_stream_t stream);
+
 /* ---- voxel-grid downsampling (csrc/voxel.hip), added within ABI 15 (purely additive: no version change) ------------------------------
  * One row per occupied cell of a regular grid, for a batch of B clouds that lie back to back in device memory (the conventions
  * of pn2_scan_filter: device-side row_begin / row_count / out_begin, a host bound max_rows that sizes the grid of workgroups and

@@ -69,6 +69,24 @@ def read_scan(fn_velo, fn_label, learning_map, subset="all"):
     return points, label
 
 
+def read_poses(fn_poses, Tr=None):
+    """The dataset's ``poses.txt`` (one line per frame: the 12 numbers of a 3 x 4 ``[R | t]``, row-major, frame -> the sequence's
+    first CAMERA frame) -> float64 [F,4,4].  With the calibration's ``Tr`` (velodyne -> camera, 12 numbers, [3,4] or [4,4]) the
+    poses are returned in the SCANNER's frame, ``inv(Tr) @ P @ Tr``: ``inv(pose[i]) @ pose[j]`` is then what registering scan j to
+    scan i (``registration.icp``) should find.  Host-side numpy."""
+    rows = np.loadtxt(fn_poses, dtype=np.float64, ndmin=2)
+    if rows.shape[1] != 12:
+        raise ValueError("read_poses: every line must hold 12 numbers (got %d)" % rows.shape[1])
+    poses = np.tile(np.eye(4), (rows.shape[0], 1, 1))
+    poses[:, :3, :] = rows.reshape(-1, 3, 4)
+    if Tr is None:
+        return poses
+    tr = np.eye(4)
+    t = np.asarray(Tr, np.float64)
+    tr[:3, :] = t.reshape(3, 4) if t.size == 12 else t.reshape(4, 4)[:3, :]
+    return np.linalg.inv(tr) @ poses @ tr
+
+
 def _read_files(fn_velo, fn_label):
     points = np.fromfile(fn_velo, dtype=np.float32).reshape(-1, 4)
     raw = None
