@@ -991,6 +991,68 @@ int pn2_icp_step(const float *src, int lds, int B, int N, const int64_t *n_src,
                  double *T, double *sums, int64_t *count, double *x, int32_t *status, int32_t *iters,
                  int64_t *corr, int32_t *err, void *workspace, pn2_stream_t stream);
 
+/* ---- plane RANSAC: the dominant plane of a cloud, its least-squares refit, height above it (csrc/plane.hip), added within ABI 15
+ * (purely additive: no version change) ----------
+ * pn2_plane_ransac scores H three-point hypotheses per cloud and selects one (three launches); pn2_plane_refit does ONE
+ * least-squares round on that plane's inliers (two launches); pn2_plane_classify writes every row's signed distance, the inlier
+ * count and the inliers' mark (two launches).  Plain launches on the caller's stream; no allocation, no host synchronisation, no
+ * float atomics, no thread waits for another thread's write; the bytes are the same from run to run.  tests/plane_ref.py restates
+ * the rule in numpy.
+ *   pts [B,N,ld] fp32, 3 <= ld <= 16, columns 0..2 = x, y, z (a [., 4] scan is read where it lies).
+ *   n_points  device int64 [B] or NULL (= N), clamped to [0,N]: n below.
+ *   assign    device int32 [B,N] or NULL.  A row TAKES PART iff i < n and (assign is NULL or assign[b,i] < 0): planes are peeled off
+ *             one after another by calling again on the same assign.
+ *   axis      HOST double[3], finite, not zero; the entry point divides it by sqrt((a_x a_x + a_y a_y) + a_z a_z) in fp64.
+ *   workspace pn2_plane_workspace_bytes(B, N, H) bytes of device memory, 16-byte aligned; it may hold anything before
+ *             pn2_plane_ransac; pn2_plane_refit and pn2_plane_classify use a part of it whose place depends on (B, N) alone.
+ * SAMPLER.  Hypothesis h < H of cloud b names rows row(0), row(1), row(2), a pure integer function, all arithmetic mod 2^64:
+ *   x = seed * 0x9E3779B97F4A7C15 + (b << 40 | h << 8 | j);
+ *   x ^= x >> 30;  x *= 0xBF58476D1CE4E5B9;  x ^= x >> 27;  x *= 0x94D049BB133111EB;  x ^= x >> 31;   row(j) = ((x >> 32) * n) >> 32.
+ *   (This header is the definition, whatever generator the constants resemble.)
+ * HYPOTHESIS, fp64, each operation rounded on its own, nothing fused.  p_j = double(pts[row(j)]).  INVALID if n = 0, two of the rows
+ *   coincide, one takes no part, or one is not finite.  a = p_1 - p_0, b = p_2 - p_0, c = a x b componentwise
+ *   (c_x = a_y b_z - a_z b_y, c_y = a_z b_x - a_x b_z, c_z = a_x b_y - a_y b_x), l2 = (c_x c_x + c_y c_y) + c_z c_z; INVALID unless
+ *   l2 > 0 and finite; n = c / sqrt(l2) componentwise.  FLIP: with t = (n_x a_x + n_y a_y) + n_z a_z against the normalised axis, n is
+ *   negated iff t < 0, or t == 0 and the first non-zero component of n is negative.  Then t is taken again; INVALID if t < cos_max.
+ *   d = -((n_x p_0x + n_y p_0y) + n_z p_0z).  There is no retry: an invalid hypothesis is lost.
+ * SCORE.  r = ((n_x x + n_y y) + n_z z) + d in fp64 with (x, y, z) = double(row).  A row is an INLIER iff it takes part, is finite and
+ *   |r| <= threshold.  A row that takes part and is not finite sets PN2_PLANE_ERR_NONFINITE.  A hypothesis's score is its integer
+ *   inlier count; hyp_count int32 [B,H] or NULL receives it, -1 for an invalid hypothesis.
+ * SELECT.  The valid hypothesis with the largest count, the lowest h among equals: best_h int32 [B] (-1: no valid hypothesis),
+ *   best_count int64 [B] (then 0), plane fp64 [B,4] = its (n_x, n_y, n_z, d) bit for bit, status int32 [B] = 0.  No valid hypothesis, or
+ *   best_count < 3: plane = zeros, status = PN2_PLANE_NONE, *err |= PN2_PLANE_ERR_NONE, and pn2_plane_refit / pn2_plane_classify
+ *   write nothing of that cloud.
+ * REFIT (pn2_plane_refit, one round; callers run it `refine` times).  s = (-d) n, a point of the current plane.  Over the current
+ *   plane's inliers, q = double(p) - s, ten fp64 sums: count, q_x, q_y, q_z, q_x q_x, q_x q_y, q_x q_z, q_y q_y, q_y q_z, q_z q_z ->
+ *   sums fp64 [B,10] (each product rounded, then added).  The order of summation is a function of (B, N) alone and is not stated
+ *   otherwise.  m = sum q / count;  C_ab = sum q_a q_b / count - m_a m_b;  (l0 <= l1 <= l2, u) = the eigenvalues and the
+ *   eigenvector of l0 by csrc/sym_eig3.h (cyclic Jacobi, PN2_PCA_SWEEPS sweeps).  count < 3, or not l1 > 0, or u / l0 not finite:
+ *   status |= PN2_PLANE_DEGENERATE, plane and rmse stay.  Otherwise n = u with the FLIP above,
+ *   d = -((n_x (s_x + m_x) + n_y (s_y + m_y)) + n_z (s_z + m_z)), rmse[b] = sqrt(max(l0, 0)).  (No angle test: the refit of a
+ *   plane that passed it moves by the noise.)
+ * CLASSIFY (pn2_plane_classify).  With the plane as it stands: dist fp32 [B,N] or NULL, dist[b,i] = float(r) for EVERY row i < n,
+ *   rows that take no part included -- the height above the plane along axis; NaN for a row that is not finite.  count int64 [B] =
+ *   the inliers (among the rows that take part).  count < min_inliers: status |= PN2_PLANE_SMALL and assign is left alone;
+ *   otherwise, where assign is given, assign = plane_id for the inliers.  Rows at and beyond n are not written.
+ * PN2_EINVAL, nothing launched and nothing written: a null pts / plane / workspace / axis (ransac, refit) / required output, B < 1
+ * or B > 65535, N < 1 or N > 2^31 - 256, H < 1 or H > 65536, a pitch outside 3..16, a threshold that is not finite and >= 0, a
+ * cos_max that is not finite, an axis that is zero or not finite, plane_id < 0, a misaligned pointer (the workspace: 16 bytes);
+ * pn2_plane_workspace_bytes returns PN2_EINVAL for such B / N / H. */
+#define PN2_PLANE_NONE 1           /* status bits */
+#define PN2_PLANE_DEGENERATE 2
+#define PN2_PLANE_SMALL 4
+#define PN2_PLANE_ERR_NONFINITE 1  /* err bits */
+#define PN2_PLANE_ERR_NONE 2
+int64_t pn2_plane_workspace_bytes(int B, int N, int H);
+int pn2_plane_ransac(const float *pts, int ld, int B, int N, const int64_t *n_points, const int32_t *assign, int H, uint64_t seed,
+                     const double *axis, double cos_max, double threshold, double *plane, int32_t *hyp_count, int32_t *best_h,
+                     int64_t *best_count, int32_t *status, int32_t *err, void *workspace, pn2_stream_t stream);
+int pn2_plane_refit(const float *pts, int ld, int B, int N, const int64_t *n_points, const int32_t *assign, const double *axis,
+                    double threshold, double *plane, double *rmse, double *sums, int32_t *status, void *workspace, pn2_stream_t stream);
+int pn2_plane_classify(const float *pts, int ld, int B, int N, const int64_t *n_points, int32_t *assign, int32_t plane_id,
+                       int64_t min_inliers, double threshold, const double *plane, int32_t *status, float *dist, int64_t *count,
+                       void *workspace, pn2_stream_t stream);
+
 /* ---- voxel-grid downsampling (csrc/voxel.hip), added within ABI 15 (purely additive: no version change) ------------------------------
  * One row per occupied cell of a regular grid, for a batch of B clouds that lie back to back in device memory (the conventions
  * of pn2_scan_filter: device-side row_begin / row_count / out_begin, a host bound max_rows that sizes the grid of workgroups and

@@ -121,6 +121,10 @@ SIGNATURES = {
     "pn2_icp_workspace_bytes": (_i64, [_i, _i]),
     "pn2_icp_step": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _f, _i, _i, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                           _vp, _vp]),
+    "pn2_plane_workspace_bytes": (_i64, [_i, _i, _i]),
+    "pn2_plane_ransac": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, ctypes.c_uint64, _vp, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pn2_plane_refit": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pn2_plane_classify": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i64, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pn2_voxel_grid_workspace_bytes": (_i64, [_i, _i64]),
     "pn2_voxel_grid": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pn2_segment_reduce_workspace_bytes": (_i64, [_i, _i64, _i]),
@@ -156,6 +160,8 @@ ICP_POINT, ICP_PLANE = 0, 1              # PN2_ICP_* of include/pn2.h: pn2_icp_s
 ICP_EVAL_ONLY = 1        # PN2_ICP_EVAL_ONLY: pn2_icp_step's flag, sums / count / corr only
 ICP_CONVERGED, ICP_SINGULAR = 1, 2       # its status bits
 ICP_ERR_QUERY, ICP_ERR_SINGULAR, ICP_ERR_NONFINITE = 1, 2, 4         # its err bits
+PLANE_NONE, PLANE_DEGENERATE, PLANE_SMALL = 1, 2, 4      # PN2_PLANE_* of include/pn2.h: the status bits of the plane entry points
+PLANE_ERR_NONFINITE, PLANE_ERR_NONE = 1, 2               # their err bits
 PCA_ERR_FEW, PCA_ERR_NONFINITE = 1, 2     # PN2_PCA_ERR_* of include/pn2.h: the err bits of pn2_local_pca
 VOXEL_TILE = 1024        # PN2_VOXEL_TILE of include/pn2.h: rows per workgroup of pn2_voxel_grid's compaction passes
 VOXEL_MAX_ROWS = 1 << 29                 # PN2_VOXEL_MAX_ROWS: the largest max_rows of pn2_voxel_grid
@@ -224,7 +230,7 @@ class _Timed:
                                                    "pn2_scan_filter_workspace_bytes", "pn2_voxel_grid_workspace_bytes",
                                                    "pn2_segment_reduce_workspace_bytes", "pn2_voxel_components_workspace_bytes",
                                                    "pn2_panoptic_workspace_bytes", "pn2_lovasz_workspace_bytes", "pn2_lovasz_tile_rows",
-                                                   "pn2_grid_workspace_bytes", "pn2_icp_workspace_bytes"):
+                                                   "pn2_grid_workspace_bytes", "pn2_icp_workspace_bytes", "pn2_plane_workspace_bytes"):
             return fn
 
         def timed(*args):

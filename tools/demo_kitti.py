@@ -2,7 +2,7 @@
 """One frame of the reference's KITTI demo (``python pcdvis.py``) on the HIP library: scan -> labels -> pixels -> two images,
 three with ``--ego``.
 
-    python tools/demo_kitti.py [--out DIR] [--npoints 25000] [--seed 0] [--merge] [--time] [--raw [--labels-out FILE [--instances SIZE]] [--normals K[:RADIUS]]] [--ego CAMERA.json [--render-option FILE.json]] [--image FILE]
+    python tools/demo_kitti.py [--out DIR] [--npoints 25000] [--seed 0] [--merge] [--time] [--raw [--labels-out FILE [--instances SIZE]] [--normals K[:RADIUS]] [--ground THRESHOLD]] [--ego CAMERA.json [--render-option FILE.json]] [--image FILE]
     python tools/demo_kitti.py --root $KITTI_ROOT --part 01 --index 0 --calib DIR --config semantic-kitti.yaml [--checkpoint CKPT]
 
 Without ``--root`` the scan is synthetic (``synthetic.kitti_cloud``, un-normalised back to metres), the calibration is the one
@@ -44,6 +44,12 @@ nearest drawn rows (within RADIUS metres, if given), turned towards the scanner 
 ``pn2_knn`` + ``pn2_local_pca``), as the camera view with colour ``round(127.5 * (n + 1))`` per component
 (``draw_2d_points(labels=None, colors=)``); a row with fewer than three neighbours in reach has a zero normal and is mid-grey.
 Without the option the tool's output is what it is without it, byte for byte.
+
+``--ground THRESHOLD`` (with ``--raw``) writes one more picture, ``ground.png``: the drawn rows within THRESHOLD metres of the scan's
+ground plane -- ``plane.ground_labels(threshold=THRESHOLD, max_angle=15)``: RANSAC with the normal held within 15 degrees of +z, two
+least-squares refits (``pn2_plane_ransac`` / ``pn2_plane_refit`` / ``pn2_plane_classify``) -- in brown, the rest in green, as the camera
+view (``draw_2d_points(labels=None, colors=)``), and prints the plane.  No network is involved.  Without the option every output of
+the tool is what it is without it, byte for byte.
 
 ``--time`` prints one JSON line with medians of 20 (device work included, host clock) for the post-network stages --
 predict + project + both images (``render_ms``), and the same as a captured graph (``render_graph_ms``) -- and beside them, in
@@ -224,6 +230,7 @@ def main():
     ap.add_argument("--instances", type=float, metavar="SIZE",
                     help="with --labels-out: Euclidean clustering of the thing classes on a grid of SIZE metres; instance ids in the high halves")
     ap.add_argument("--normals", metavar="K[:RADIUS]", help="with --raw: also write normals.png, the drawn rows' surface normals as colours")
+    ap.add_argument("--ground", type=float, metavar="THRESHOLD", help="with --raw: also write ground.png, the drawn rows on / off the RANSAC ground plane")
     ap.add_argument("--search", choices=("brute", "grid"), default="brute",
                     help="the neighbour search of --labels-out and --normals: pn2_knn's brute force, or the uniform grid of neighbors.GridIndex "
                          "(--normals then needs a RADIUS)")
@@ -281,6 +288,8 @@ def main():
         ap.error("--voxel needs --raw")
     if args.normals and not args.raw:
         ap.error("--normals needs --raw")
+    if args.ground is not None and not args.raw:
+        ap.error("--ground needs --raw")
     camera = V.PinholeCamera.from_json(args.ego) if args.ego else None
     option = V.RenderOption.from_json(args.render_option) if args.render_option else V.RenderOption()
     seg = V.FrameSegmenter(model, calib, colors if groups is None else groups.colors, npoints=args.npoints, image_size=size, groups=groups,
@@ -334,6 +343,15 @@ def main():
         Image.fromarray(picture.cpu().numpy()).save(os.path.join(args.out, "normals.png"))
         print("normals of %d drawn rows from %s neighbours%s, %d of them zero (fewer than three in reach); wrote %s/normals.png"
               % (len(n), k, " within %s m" % radius if radius else "", int((n == 0).all(1).sum()), args.out))
+    if args.ground is not None:
+        from pointnet12_amd import plane as PL
+        buf = PL.buffers(len(seg.raw_rows), 1, 256, device=seg.raw_rows.device)
+        ground = PL.ground_labels(seg.raw_rows, threshold=args.ground, max_angle=15.0, buffers=buf) < 0
+        shade = torch.where(ground[:, None], torch.tensor([150, 100, 50], device=ground.device), torch.tensor([40, 200, 90], device=ground.device))
+        picture = V.draw_2d_points(out["pix"], None, shade.to(torch.uint8), None, size)
+        Image.fromarray(picture.cpu().numpy()).save(os.path.join(args.out, "ground.png"))
+        print("ground plane n = (%.4f, %.4f, %.4f), d = %.4f m, rmse %.4f m: %d of %d drawn rows within %g m of it; status %d; wrote %s/ground.png"
+              % (*buf.plane[0].cpu().tolist(), float(buf.rmse[0]), int(ground.sum()), len(ground), args.ground, int(buf.status[0]), args.out))
     counts = torch.bincount(out["pred"], minlength=len(colors)).cpu().tolist()
     drawn = int((out["pix"][:, 0] != V.INT32_MIN).sum())
     print("scan of %d points resampled to %d; %d with a pixel, %d classes predicted; error flag %d; wrote %s/semantic.png and top_view.png"
