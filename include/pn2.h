@@ -1053,6 +1053,59 @@ int pn2_plane_classify(const float *pts, int ld, int B, int N, const int64_t *n_
                        int64_t min_inliers, double threshold, const double *plane, int32_t *status, float *dist, int64_t *count,
                        void *workspace, pn2_stream_t stream);
 
+/* ---- FPFH: Fast Point Feature Histograms over neighbour lists (csrc/fpfh.hip), added within ABI 15 (purely additive: no version
+ * change) ----------
+ * 33 numbers per point, invariant to rigid motion (Rusu, Blodow, Beetz, ICRA 2009), from points, UNIT normals and a self-search's
+ * "k nearest within r" lists.  pn2_spfh counts three angle bins per neighbour pair (integers); pn2_fpfh, after a launch boundary,
+ * adds to every row's own histogram the 1 / d2 weighted mean of its neighbours' histograms.  One plain launch each on the caller's
+ * stream; no allocation, no host synchronisation, no atomics except the OR into err, no thread waits for another; the bytes are
+ * the same from run to run.  tests/fpfh_ref.py restates the rule in numpy.  THIS HEADER IS THE DEFINITION: it was written from the
+ * paper and is UNVERIFIED AGAINST OPEN3D / PCL.  THE DESCRIPTOR DEPENDS ON THE SIGN OF THE NORMALS.
+ *   points  [B,M,ldp] fp32, 3 <= ldp <= 16, columns 0..2 = x, y, z, read where they lie.
+ *   normals [B,M,ldn] fp32, 3 <= ldn <= 16, the normal in columns normal_col .. normal_col + 2; it may be the points' buffer
+ *           (a row x y z nx ny nz: ldn = 6, normal_col = 3).
+ *   idx     [B,M,K] int64 as pn2_knn / pn2_grid_knn's self-search write it (padding: idx = M), 1 <= K <= 32.  Row i of idx belongs to
+ *           point i: the search is a self-search.   max_d2 fp32, >= 0, +inf: no cut-off.
+ *   n_points  device int64 [B] or NULL (= M), clamped to [0,M]: n below.  Rows at and beyond n are neither read nor written.
+ * PAIR.  Slot s of row i with j = idx[i,s] is a PAIR iff, tested in this order,
+ *   (G1) 0 <= j < n;
+ *   (G2) p_i and p_j are finite; otherwise the slot is lost and *err |= PN2_FPFH_ERR_NONFINITE;
+ *   (G3) with dp = double(p_j) - double(p_i) (exact), d2 = (dp.x*dp.x + dp.y*dp.y) + dp.z*dp.z:  0 < d2 <= double(max_d2)
+ *        (the point itself and exact duplicates are not pairs);
+ *   (N1) n_i and n_j are finite; otherwise the slot is lost and *err |= PN2_FPFH_ERR_NONFINITE (only a slot that passed G1..G3
+ *        looks at the normals);
+ *   (N2) neither normal is three zeros (pn2_local_pca's PN2_PCA_ERR_FEW rows: lost without a flag);
+ *   (N3) |v| > 0 below.
+ *   G1..G3 are the GEOMETRIC HALF of the test.  Nothing is poisoned; a candidate listed twice is two slots.
+ * PAIR FEATURES, IEEE fp64, each operation rounded on its own, nothing fused; every dot product is (a.x*b.x + a.y*b.y) + a.z*b.z.
+ *   d = sqrt(d2);  a1 = (n_i . dp) / d;  a2 = (n_j . dp) / d.
+ *   If |a1| < |a2| the frame sits on j: n_s = n_j, n_t = n_i, dp = -dp, f3 = -a2.  Otherwise n_s = n_i, n_t = n_j, f3 = a1.
+ *   (Open3D's acos(|a1|) > acos(|a2|) without the two acos calls: a stated deviation at ties.)
+ *   v = dp x n_s  (v.x = dp.y n_s.z - dp.z n_s.y, v.y = dp.z n_s.x - dp.x n_s.z, v.z = dp.x n_s.y - dp.y n_s.x);  |v| = sqrt(v . v);
+ *   v = v / |v| component by component;  w = n_s x v, the same way.
+ *   f2 = v . n_t;   f1 = atan2((w . n_t) + 0.0, n_s . n_t)   (the + 0.0 turns -0 into +0: exactly antiparallel normals give +pi).
+ *   t1 = 11.0 * (f1 + pi) / (2.0 * pi), left to right, pi = 3.14159265358979323846;  t2 = 11.0 * (f2 + 1.0) * 0.5;
+ *   t3 = 11.0 * (f3 + 1.0) * 0.5;   b_k = floor(t_k) clamped to 0 .. 10 (a NaN: 0).
+ *   The pair adds 1 to c_i[b_1], c_i[11 + b_2], c_i[22 + b_3] and to m_i.  atan2 is the one operation that is not correctly
+ *   rounded everywhere: two implementations may differ on a pair whose t1 lies within a few 1e-15 of an integer.
+ * SPFH ROW (pn2_spfh's output, a public intermediate): uint8 [B,M,36], 4-byte aligned: bytes 0..32 = c_i, byte 33 = m_i (both at
+ *   most K <= 32), bytes 34..35 = 0.  m_i = 0: *err |= PN2_FPFH_ERR_EMPTY.
+ * FPFH ROW (pn2_fpfh's output): fp32 [B,M,33].  IEEE fp64, ascending slot order, nothing fused.
+ *   s_j[b] = (100.0 * c_j[b]) / m_j, 0 where m_j = 0.   Slot s of row i VOTES iff it passes G1..G3 (pn2_fpfh reads no normals; G2
+ *   sets PN2_FPFH_ERR_NONFINITE here too) and m_j > 0.   W_i = sum of 1.0 / d2 and A_i[b] = sum of s_j[b] / d2 over the voting
+ *   slots;   fpfh_i[b] = float(s_i[b] + (W_i > 0 ? A_i[b] / W_i : 0.0)).   m_i = 0: *err |= PN2_FPFH_ERR_EMPTY (the row then holds
+ *   its neighbours' mean alone, or zeros).  Each third of a row with m_i > 0 and a voter sums to 200.
+ * err: device int32, caller zeroes, may be NULL.
+ * PN2_EINVAL, nothing launched and nothing written: a null points / normals / idx / spfh / output, B < 1 or B > 65535, M < 1 or
+ * M > 2^31 - 256, K < 1, ldp or ldn outside 3..16, normal_col < 0 or normal_col + 3 > ldn, a negative or NaN max_d2, points / normals
+ * / spfh / fpfh_out not 4-byte or idx not 8-byte aligned.  K > 32: PN2_EUNSUPPORTED, nothing launched. */
+#define PN2_FPFH_ERR_EMPTY 1
+#define PN2_FPFH_ERR_NONFINITE 2
+int pn2_spfh(const float *points, int ldp, const float *normals, int ldn, int normal_col, const int64_t *idx, int B, int M, int K,
+             float max_d2, const int64_t *n_points, uint8_t *spfh_out, int32_t *err, pn2_stream_t stream);
+int pn2_fpfh(const float *points, int ldp, const int64_t *idx, const uint8_t *spfh, int B, int M, int K, float max_d2,
+             const int64_t *n_points, float *fpfh_out, int32_t *err, pn2_stream_t stream);
+
 /* ---- voxel-grid downsampling (csrc/voxel.hip), added within ABI 15 (purely additive: no version change) ------------------------------
  * One row per occupied cell of a regular grid, for a batch of B clouds that lie back to back in device memory (the conventions
  * of pn2_scan_filter: device-side row_begin / row_count / out_begin, a host bound max_rows that sizes the grid of workgroups and

@@ -125,6 +125,8 @@ SIGNATURES = {
     "pn2_plane_ransac": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, ctypes.c_uint64, _vp, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pn2_plane_refit": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pn2_plane_classify": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i64, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pn2_spfh": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
+    "pn2_fpfh": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "pn2_voxel_grid_workspace_bytes": (_i64, [_i, _i64]),
     "pn2_voxel_grid": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pn2_segment_reduce_workspace_bytes": (_i64, [_i, _i64, _i]),
@@ -162,6 +164,7 @@ ICP_CONVERGED, ICP_SINGULAR = 1, 2       # its status bits
 ICP_ERR_QUERY, ICP_ERR_SINGULAR, ICP_ERR_NONFINITE = 1, 2, 4         # its err bits
 PLANE_NONE, PLANE_DEGENERATE, PLANE_SMALL = 1, 2, 4      # PN2_PLANE_* of include/pn2.h: the status bits of the plane entry points
 PLANE_ERR_NONFINITE, PLANE_ERR_NONE = 1, 2               # their err bits
+FPFH_ERR_EMPTY, FPFH_ERR_NONFINITE = 1, 2   # PN2_FPFH_ERR_* of include/pn2.h: the err bits of pn2_spfh / pn2_fpfh
 PCA_ERR_FEW, PCA_ERR_NONFINITE = 1, 2     # PN2_PCA_ERR_* of include/pn2.h: the err bits of pn2_local_pca
 VOXEL_TILE = 1024        # PN2_VOXEL_TILE of include/pn2.h: rows per workgroup of pn2_voxel_grid's compaction passes
 VOXEL_MAX_ROWS = 1 << 29                 # PN2_VOXEL_MAX_ROWS: the largest max_rows of pn2_voxel_grid
@@ -277,6 +280,10 @@ def load():
     if not os.path.exists(LIB_PATH):
         raise Pn2Error("libpn2_hip.so not found at %s -- build it with `python -c \"import __graft_entry__ as g; "
                        "g.build()\"` (hipcc, gfx950). There is no fallback path." % LIB_PATH)
+    # torch first: its ROCm wheel carries a HIP runtime of its own under a file name (libamdhip64.so) that is not the SONAME this
+    # library asks for (libamdhip64.so.7).  Loaded after torch, the library binds to the runtime torch already mapped; loaded
+    # before it, the process ends up with TWO runtimes, and every launch on one of torch's streams fails with PN2_ELAUNCH.
+    import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
