@@ -10,7 +10,11 @@ from pointnet12_amd import loader, optim
 
 pytestmark = pytest.mark.gpu
 
-ADAM_TOL = 1e-6          # relative to max |param|; ATen fuses multiply-adds, the kernel does not (measured ~1e-7)
+# ATen parity ONLY: relative to max |param|, because ATen fuses multiply-adds and the kernel does not (measured ~1e-7).  A norm-relative
+# figure says nothing about small elements, eps or the weight-decay term where |g| << |p|: element-wise correctness of pn2_adam_step is
+# held in tests/test_adam_abi_gpu.py (bits of the oracle, and the fp64 rule of tests/adam_ref.py within its own error bound), and that
+# bound itself in tests/test_adam_ref_cpu.py.
+ADAM_TOL = 1e-6
 
 
 def bits(a):
@@ -129,15 +133,19 @@ def test_adam_golden(dev):
                g["adam/exp_avg_sq"]) <= ADAM_TOL
 
 
-@pytest.mark.parametrize("wd,sizes", [(0.0, [(7,), (3, 5), (1,)]), (1e-4, [(1000003,), (64, 9, 1, 1), (2,)])])
-def test_adam_matches_torch_and_oracle(dev, wd, sizes):
-    """Ragged sizes (total not a multiple of 4: the scalar tail), 8 steps, StepLR in the loop as semseg.py:113."""
+@pytest.mark.parametrize("wd,sizes,betas,eps", [(0.0, [(7,), (3, 5), (1,)], (0.9, 0.999), 1e-08),
+                                                (1e-4, [(1000003,), (64, 9, 1, 1), (2,)], (0.9, 0.999), 1e-08),
+                                                (1e-4, [(1027,), (64, 9, 1, 1), (2,)], (0.3, 0.5), 1e-3)],
+                         ids=["0.0-sizes0", "0.0001-sizes1", "betas0.3,0.5-eps0.001"])
+def test_adam_matches_torch_and_oracle(dev, wd, sizes, betas, eps):
+    """Ragged sizes (total not a multiple of 4: the scalar tail), 8 steps, StepLR in the loop as semseg.py:113.  betas = (0.3, 0.5):
+    the optimiser class reaches the lerp's `weight >= 0.5` form."""
     torch.manual_seed(11)
     init = [torch.randn(s) for s in sizes]
     ref_p = [torch.nn.Parameter(t.clone()) for t in init]
     my_p = [torch.nn.Parameter(t.clone().to(dev)) for t in init]
-    ref = torch.optim.Adam(ref_p, lr=2e-3, betas=(0.9, 0.999), eps=1e-08, weight_decay=wd)
-    mine = optim.Adam(my_p, lr=2e-3, betas=(0.9, 0.999), eps=1e-08, weight_decay=wd)
+    ref = torch.optim.Adam(ref_p, lr=2e-3, betas=betas, eps=eps, weight_decay=wd)
+    mine = optim.Adam(my_p, lr=2e-3, betas=betas, eps=eps, weight_decay=wd)
     s_ref = torch.optim.lr_scheduler.StepLR(ref, step_size=3, gamma=0.5)
     s_mine = torch.optim.lr_scheduler.StepLR(mine, step_size=3, gamma=0.5)
     o_p = flat(ref_p).copy()
@@ -153,7 +161,8 @@ def test_adam_matches_torch_and_oracle(dev, wd, sizes):
         assert mine.param_groups[0]["lr"] == lr
         ref.step()
         mine.step()
-        TR.adam_step(o_p, np.concatenate([gr.reshape(-1).numpy() for gr in grads]), o_m, o_v, t, lr=lr, weight_decay=wd)
+        TR.adam_step(o_p, np.concatenate([gr.reshape(-1).numpy() for gr in grads]), o_m, o_v, t, lr=lr, betas=betas,
+                     eps=eps, weight_decay=wd)
         s_ref.step()
         s_mine.step()
         assert rel(flat(my_p), flat(ref_p)) <= ADAM_TOL, t
