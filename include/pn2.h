@@ -684,7 +684,12 @@ int pn2_bn_bwd_reduce_noact_dense(const float *dDense, int ldd, const float *dPo
  *   sum (may be NULL) = (sum_b sum_n dist[b,n]) / B, added in a fixed order (fp64 partials per workgroup, then in index order).
  * dist, idx and sum are bit-identical from run to run; nothing of size N x M is written.  workspace:
  * pn2_chamfer_nn_workspace_bytes(B, N, M, D) bytes (host-only query, never 0 for a valid shape), 256-byte aligned, need not
- * be cleared.  B <= 65535, B*N < 2^31. */
+ * be cleared.  B <= 65535, B*N < 2^31.
+ * Non-finite coordinates (pinned by tests/test_chamfer_abi_gpu.py, observed on an MI355X): the search keeps a candidate only on
+ * `d2 < best`, best starting at +inf, and a d2 that is NaN or +inf never passes it.  So a candidate with a NaN or infinite
+ * coordinate is never chosen, and a query with one gets idx = 0 and dist = +inf, which makes sum +inf (torch.min would hand the
+ * NaN on).  Such a row changes no other query's dist, idx or dp1 bits; in pn2_chamfer_bwd a non-finite query's dp1 row is NaN in
+ * its non-finite components, and in dp2 it reaches candidate 0 of its own cloud only. */
 int64_t pn2_chamfer_nn_workspace_bytes(int B, int N, int M, int D);
 int pn2_chamfer_nn(const float *p1, const float *p2, int B, int N, int M, int D, float *dist, int64_t *idx, float *sum,
                    void *workspace, pn2_stream_t stream);

@@ -14,6 +14,9 @@ Differences from the reference, all deliberate:
     ``RuntimeError``, a CPU tensor ``Pn2Error``, ``D > 16`` ``Pn2Error`` -- there is no fallback path;
   * ties go to the lowest candidate index, decided on the fp32 squared distance in difference form (the reference's
     ``min`` over fp32 norms does the same on the data it was probed with);
+  * non-finite coordinates: a squared distance that is NaN or +inf never wins the search's strict ``<``, so a candidate
+    with a NaN or infinite coordinate is never chosen and a query with one gets index 0 and distance +inf -- the value
+    becomes +inf where the reference's ``min`` hands a NaN on; no other point's result changes (include/pn2.h);
   * ``nearest_neighbor`` and ``chamfer_symmetric`` are additions.
 """
 import torch

@@ -11,7 +11,8 @@
 //     ~3e-4 |p| in d for near-coincident points once the square root is taken.
 //   * strict `<` over candidates in ascending index: ties (on that fp32 d^2) go to the LOWEST index; the same rule joins the
 //     partial results when the candidates of a cloud are split over workgroups (ascending ranges, strict `<`).
-//   * one correctly rounded square root per query, after the search.
+//   * one correctly rounded square root per query, after the search: sqrtf, which hipcc rounds correctly by default; without
+//     OCML_BASIC_ROUNDED_OPERATIONS __fsqrt_rn is v_sqrt_f32 alone, which is one ulp off on some values.
 //   * the scalar is summed in a fixed order: fp64 per-workgroup partials (a fixed shuffle tree), then ONE workgroup adds the
 //     partials in index order -- dist, idx and the value are bit-identical from run to run.
 #include "pn2_common.h"
@@ -142,7 +143,7 @@ __global__ __launch_bounds__(kThreads) void chamfer_nn_kernel(const float *__res
         if (n >= N) continue;
         const size_t o = (size_t)b * N + n;
         if (splits == 1) {
-            const float dd = __fsqrt_rn(best[i]);
+            const float dd = sqrtf(best[i]);                              // (not __fsqrt_rn: that is the 1-ulp native root here)
             dist[o] = dd;
             idx[o] = arg[i];
             acc += (double)dd;
@@ -171,7 +172,7 @@ __global__ __launch_bounds__(kThreads) void chamfer_join_kernel(const float *__r
             const float d2 = part_d2[o * splits + s];
             if (d2 < best) { best = d2; arg = part_idx[o * splits + s]; }
         }
-        const float dd = __fsqrt_rn(best);
+        const float dd = sqrtf(best);
         dist[o] = dd;
         idx[o] = arg;
         acc = (double)dd;
