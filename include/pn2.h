@@ -1111,6 +1111,105 @@ int pn2_spfh(const float *points, int ldp, const float *normals, int ldn, int no
 int pn2_fpfh(const float *points, int ldp, const int64_t *idx, const uint8_t *spfh, int B, int M, int K, float max_d2,
              const int64_t *n_points, float *fpfh_out, int32_t *err, pn2_stream_t stream);
 
+/* ---- feature matching: the two nearest rows in feature space, mutual and ratio tests (csrc/feature_match.hip), added within ABI 15
+ * (purely additive: no version change) ----------
+ * pn2_feature_nn2 gives every query row its nearest and second-nearest candidate row (one launch); pn2_match_pairs filters one such
+ * search, optionally against the search with the roles swapped, into a compacted pair list (four launches).  Plain launches on the
+ * caller's stream; no allocation, no host synchronisation, no atomics, no thread waits for another thread's write; the bytes are
+ * the same from run to run.  tests/match_ref.py restates the rule in numpy.
+ *   query [B,N,ldq] fp32, cand [B,M,ldc] fp32; the feature is columns 0 .. D-1, 1 <= D <= PN2_MATCH_MAX_D, D <= ldq, D <= ldc (an
+ *         FPFH row: D = ld = 33).
+ *   n_query, n_cand  device int64 [B] or NULL (= N, M), clamped to [0,N] / [0,M], as in pn2_knn.
+ * DISTANCE, fp32, each operation rounded on its own, nothing fused, in ascending c:  s = 0;  for c = 0 .. D-1: t = q[c] - f[c],
+ *   s = s + t * t;  d2(i,j) = s.
+ * TAKES PART.  A row (query or candidate) takes part iff its D values are all finite and not all zero (a row that pn2_fpfh flagged
+ *   PN2_FPFH_ERR_EMPTY may hold zeros: left in, such rows would all match one another at distance 0).  A row that takes no part is
+ *   never a candidate; as a query it gets idx = (M, M), dist = (+inf, +inf).
+ * SELECT.  Among the candidates j < n_cand that take part, the two smallest by ascending (d2, j), every compare strict (pn2_knn's
+ *   tie rule: equal distances keep their index order).  A NaN or +inf d2 is never kept.  idx int64 [B,N,2] (M: none), dist fp32
+ *   [B,N,2] (+inf: none).  Rows at and beyond n_query are not written.
+ * PAIRS (pn2_match_pairs).  idx / dist as above; back int64 [B,M,2] or NULL: the idx of the search with the roles swapped (mutual
+ *   checking on).  Row i < n_query is KEPT iff, with j = idx[i,0]:  0 <= j < M;  back is NULL or back[j,0] == i;  and
+ *   ratio2 == +inf, or dist[i,1] == +inf (no second neighbour), or dist[i,0] <= ratio2 * dist[i,1] (one fp32 multiply).
+ *   The kept rows are written in ascending i: pair_src int64 [B,N] = i, pair_tgt int64 [B,N] = j, count int64 [B]; entries at and
+ *   beyond count are not written.  workspace: pn2_match_pairs_workspace_bytes(B, N) bytes, 16-byte aligned, may hold anything.
+ * PN2_EINVAL, nothing launched and nothing written: a null query / cand / idx / dist / pair list / count / workspace, B < 1 or
+ * B > 65535, N or M < 1 or > 2^31 - 256, D < 1 or above a pitch, a ratio2 that is negative or NaN, a misaligned pointer (floats 4,
+ * int64 8, the workspace 16 bytes).  D > PN2_MATCH_MAX_D: PN2_EUNSUPPORTED, nothing launched. */
+#define PN2_MATCH_MAX_D 64
+int pn2_feature_nn2(const float *query, int ldq, const float *cand, int ldc, int B, int N, int M, int D, const int64_t *n_query,
+                    const int64_t *n_cand, int64_t *idx, float *dist, pn2_stream_t stream);
+int64_t pn2_match_pairs_workspace_bytes(int B, int N);
+int pn2_match_pairs(const int64_t *idx, const float *dist, const int64_t *back, int B, int N, int M, float ratio2, const int64_t *n_query,
+                    int64_t *pair_src, int64_t *pair_tgt, int64_t *count, void *workspace, pn2_stream_t stream);
+
+/* ---- correspondence RANSAC: the rigid transform of a pair list, and its least-squares refit (csrc/corr_ransac.hip), added within
+ * ABI 15 (purely additive: no version change) ----------
+ * pn2_corr_ransac scores H three-pair hypotheses per cloud and selects one (three launches); pn2_corr_refit does ONE least-squares
+ * round on that transform's inliers (two launches).  Plain launches on the caller's stream; no allocation, no host synchronisation,
+ * no float atomics, no thread waits for another thread's write; the bytes are the same from run to run.
+ * tests/corr_ransac_ref.py restates the rule in numpy.  IEEE fp64 throughout, each operation rounded on its own, nothing fused.
+ *   src [B,N,lds], tgt [B,M,ldt] fp32, 3 <= ld <= 16, columns 0..2 = x, y, z, read where they lie.
+ *   pair_src, pair_tgt  int64 [B,N]: pair k of cloud b joins source row pair_src[b,k] and target row pair_tgt[b,k] (pn2_match_pairs'
+ *             output).   count  device int64 [B] or NULL (= N), clamped to [0,N]: n below.
+ *   T         fp64 [B,12] = [R | t] row major (T[4a + c] = R_ac, T[4a + 3] = t_a): pn2_icp_step's layout.
+ *   workspace pn2_corr_workspace_bytes(B, N, H) bytes of device memory, 16-byte aligned; it may hold anything before
+ *             pn2_corr_ransac; pn2_corr_refit uses a part of it whose place depends on (B, N) alone.
+ * HYPOTHESIS h < H: pair rows r_j = row(j), j = 0, 1, 2, by the SAMPLER of "plane RANSAC" above among n rows;
+ *   a_j = double(src[pair_src[r_j]]), b_j = double(tgt[pair_tgt[r_j]]).  INVALID if n < 3; two of the r_j, of the source indices
+ *   or of the target indices coincide; an index lies outside [0,N) / [0,M); one of the six points is not finite; for one of the
+ *   edges (0,1), (0,2), (1,2) the lengths lp = |a_j - a_i|, lq = |b_j - b_i| (|d| = sqrt((d_x d_x + d_y d_y) + d_z d_z)) do not
+ *   satisfy lp > 0, lq > 0 and min(lp, lq) >= edge_ratio * max(lp, lq);  a frame below has |w| = 0 or not finite;  or one of the
+ *   twelve results is not finite.  There is no retry: an invalid hypothesis is lost (twelve NaNs in hyp_T).
+ *   FRAME of a side (a_0, a_1, a_2):  e1 = (a_1 - a_0) / |a_1 - a_0|;  v = a_2 - a_0;  w = e1 x v componentwise (w_x = e1_y v_z -
+ *   e1_z v_y, w_y = e1_z v_x - e1_x v_z, w_z = e1_x v_y - e1_y v_x);  e3 = w / |w|;  e2 = e3 x e1 the same way;
+ *   c = ((a_0 + a_1) + a_2) / 3.0.   With (e1, e2, e3, c) of the source side and (f1, f2, f3, c') of the target side:
+ *   R_ac = (f1_a e1_c + f2_a e2_c) + f3_a e3_c;   t_a = c'_a - ((R_a0 c_x + R_a1 c_y) + R_a2 c_z).
+ * SCORE.  For pair k < n with p = double(src row), q = double(tgt row): e_a = (((R_a0 p_x + R_a1 p_y) + R_a2 p_z) + t_a) - q_a,
+ *   d2 = (e_x e_x + e_y e_y) + e_z e_z; the pair is an INLIER iff both indices are in range, both points are finite and
+ *   d2 <= threshold * threshold (the product rounded once).  An index out of range sets PN2_CORR_ERR_PAIR, a point that is not
+ *   finite PN2_CORR_ERR_NONFINITE.  hyp_count int32 [B,H] or NULL receives every hypothesis's inlier count, -1 for an invalid one;
+ *   hyp_T fp64 [B,H,12] or NULL its twelve doubles.
+ * SELECT.  The valid hypothesis with the largest count, the lowest h among equals: best_h int32 [B] (-1: none valid), best_count
+ *   int64 [B] (then 0), T = its twelve doubles bit for bit, status int32 [B] = 0.  No valid hypothesis, or best_count < 3: T = the
+ *   identity, status = PN2_CORR_NONE, *err |= PN2_CORR_ERR_NONE, and pn2_corr_refit writes nothing of that cloud.
+ * REFIT (pn2_corr_refit, one round; callers run it `refine` times).  Over the inliers of the current T, PN2_CORR_SUMS = 17 fp64
+ *   sums -> sums [B,17]: count; p_x, p_y, p_z; q_x, q_y, q_z; p_a q_b for (a, b) = (x,x), (x,y), (x,z), (y,x), ... (z,z) (each
+ *   product rounded, then added); d2.  The order of summation is a function of (B, N) alone and is not stated otherwise.
+ *   inliers int64 [B] = count;  rmse fp64 [B] = sqrt(sum d2 / count), 0 for count = 0: the root mean square distance of the inliers
+ *   UNDER THE T THE ROUND STARTED FROM.  With flags = PN2_CORR_EVAL_ONLY the round ends here.  Otherwise (Horn 1987), n = count:
+ *   S_ab = sum p_a q_b - (sum p_a * sum q_b) / n;
+ *   N00 = (S_xx + S_yy) + S_zz, N11 = (S_xx - S_yy) - S_zz, N22 = (S_yy - S_xx) - S_zz, N33 = (S_zz - S_xx) - S_yy,
+ *   N01 = S_yz - S_zy, N02 = S_zx - S_xz, N03 = S_xy - S_yx, N12 = S_xy + S_yx, N13 = S_zx + S_xz, N23 = S_yz + S_zy;
+ *   u = the eigenvector of N's largest eigenvalue by csrc/sym_eig4.h (cyclic Jacobi, pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3),
+ *   PN2_HORN_SWEEPS = 8 sweeps, the largest diagonal entry, the first among equals);  (w, x, y, z) = u / sqrt(((u_0 u_0 + u_1 u_1)
+ *   + u_2 u_2) + u_3 u_3), negated iff w < 0;
+ *   R_00 = ((w w + x x) - y y) - z z, R_01 = 2 (x y - w z), R_02 = 2 (x z + w y), R_10 = 2 (x y + w z), R_11 = ((w w - x x) + y y)
+ *   - z z, R_12 = 2 (y z - w x), R_20 = 2 (x z - w y), R_21 = 2 (y z + w x), R_22 = ((w w - x x) - y y) + z z;
+ *   t_a = (sum q_a) / n - ((R_a0 m_x + R_a1 m_y) + R_a2 m_z) with m = (sum p) / n.   (The quaternion route handles inliers that
+ *   lie in a plane, S of rank 2, and never returns a reflection.)   n < 3, or a result that is not finite: status |=
+ *   PN2_CORR_DEGENERATE and T stays.
+ * err: device int32, caller zeroes, may be NULL.
+ * PN2_EINVAL, nothing launched and nothing written: a null src / tgt / pair list / T / workspace / required output, B < 1 or
+ * B > 65535, N or M < 1 or > 2^31 - 256, H < 1 or H > 65536, a pitch outside 3..16, a threshold that is not finite and >= 0, an
+ * edge_ratio outside [0,1], unknown flags, a misaligned pointer (the workspace: 16 bytes); pn2_corr_workspace_bytes returns
+ * PN2_EINVAL for such B / N / H. */
+#define PN2_CORR_NONE 1            /* status bits */
+#define PN2_CORR_DEGENERATE 2
+#define PN2_CORR_ERR_PAIR 1        /* err bits */
+#define PN2_CORR_ERR_NONFINITE 2
+#define PN2_CORR_ERR_NONE 4
+#define PN2_CORR_EVAL_ONLY 1       /* pn2_corr_refit's flag */
+#define PN2_CORR_SUMS 17
+int64_t pn2_corr_workspace_bytes(int B, int N, int H);
+int pn2_corr_ransac(const float *src, int lds, const float *tgt, int ldt, int B, int N, int M, const int64_t *pair_src, const int64_t *pair_tgt,
+                    const int64_t *count, int H, uint64_t seed, double edge_ratio, double threshold, double *T, double *hyp_T,
+                    int32_t *hyp_count, int32_t *best_h, int64_t *best_count, int32_t *status, int32_t *err, void *workspace,
+                    pn2_stream_t stream);
+int pn2_corr_refit(const float *src, int lds, const float *tgt, int ldt, int B, int N, int M, const int64_t *pair_src, const int64_t *pair_tgt,
+                   const int64_t *count, double threshold, int flags, double *T, int64_t *inliers, double *rmse, double *sums,
+                   int32_t *status, void *workspace, pn2_stream_t stream);
+
 /* ---- voxel-grid downsampling (csrc/voxel.hip), added within ABI 15 (purely additive: no version change) ------------------------------
  * One row per occupied cell of a regular grid, for a batch of B clouds that lie back to back in device memory (the conventions
  * of pn2_scan_filter: device-side row_begin / row_count / out_begin, a host bound max_rows that sizes the grid of workgroups and

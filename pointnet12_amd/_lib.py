@@ -127,6 +127,12 @@ SIGNATURES = {
     "pn2_plane_classify": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i64, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pn2_spfh": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "pn2_fpfh": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
+    "pn2_feature_nn2": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "pn2_match_pairs_workspace_bytes": (_i64, [_i, _i]),
+    "pn2_match_pairs": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pn2_corr_workspace_bytes": (_i64, [_i, _i, _i]),
+    "pn2_corr_ransac": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, ctypes.c_uint64, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pn2_corr_refit": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pn2_voxel_grid_workspace_bytes": (_i64, [_i, _i64]),
     "pn2_voxel_grid": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pn2_segment_reduce_workspace_bytes": (_i64, [_i, _i64, _i]),
@@ -165,6 +171,11 @@ ICP_ERR_QUERY, ICP_ERR_SINGULAR, ICP_ERR_NONFINITE = 1, 2, 4         # its err b
 PLANE_NONE, PLANE_DEGENERATE, PLANE_SMALL = 1, 2, 4      # PN2_PLANE_* of include/pn2.h: the status bits of the plane entry points
 PLANE_ERR_NONFINITE, PLANE_ERR_NONE = 1, 2               # their err bits
 FPFH_ERR_EMPTY, FPFH_ERR_NONFINITE = 1, 2   # PN2_FPFH_ERR_* of include/pn2.h: the err bits of pn2_spfh / pn2_fpfh
+MATCH_MAX_D = 64         # PN2_MATCH_MAX_D: the widest feature of pn2_feature_nn2
+CORR_NONE, CORR_DEGENERATE = 1, 2        # PN2_CORR_* of include/pn2.h: the status bits of pn2_corr_ransac / pn2_corr_refit
+CORR_ERR_PAIR, CORR_ERR_NONFINITE, CORR_ERR_NONE = 1, 2, 4           # their err bits
+CORR_EVAL_ONLY = 1       # PN2_CORR_EVAL_ONLY: pn2_corr_refit's flag, sums / inliers / rmse only
+CORR_SUMS = 17           # PN2_CORR_SUMS: the words of pn2_corr_refit's sums
 PCA_ERR_FEW, PCA_ERR_NONFINITE = 1, 2     # PN2_PCA_ERR_* of include/pn2.h: the err bits of pn2_local_pca
 VOXEL_TILE = 1024        # PN2_VOXEL_TILE of include/pn2.h: rows per workgroup of pn2_voxel_grid's compaction passes
 VOXEL_MAX_ROWS = 1 << 29                 # PN2_VOXEL_MAX_ROWS: the largest max_rows of pn2_voxel_grid
@@ -233,7 +244,8 @@ class _Timed:
                                                    "pn2_scan_filter_workspace_bytes", "pn2_voxel_grid_workspace_bytes",
                                                    "pn2_segment_reduce_workspace_bytes", "pn2_voxel_components_workspace_bytes",
                                                    "pn2_panoptic_workspace_bytes", "pn2_lovasz_workspace_bytes", "pn2_lovasz_tile_rows",
-                                                   "pn2_grid_workspace_bytes", "pn2_icp_workspace_bytes", "pn2_plane_workspace_bytes"):
+                                                   "pn2_grid_workspace_bytes", "pn2_icp_workspace_bytes", "pn2_plane_workspace_bytes",
+                                                   "pn2_match_pairs_workspace_bytes", "pn2_corr_workspace_bytes"):
             return fn
 
         def timed(*args):

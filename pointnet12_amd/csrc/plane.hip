@@ -22,6 +22,7 @@
 // This file is built with -ffp-contract=off: every term is the separately rounded fp64 statement of the header.
 #include <cmath>
 #include "pn2_common.h"
+#include "ransac_sample.h"
 #include "sym_eig3.h"
 
 namespace {
@@ -33,24 +34,12 @@ constexpr int kRefitRows = 4;                                       // rows per 
 constexpr int kRowTile = kThreads * kRefitRows;                     // rows per workgroup there
 constexpr int kSums = 10;                                           // count, sum q (3), sum q q^T (xx, xy, xz, yy, yz, zz)
 constexpr int kChunks = 8;                                          // of the finish kernel
-constexpr unsigned long long kGolden = 0x9E3779B97F4A7C15ull;
 
 struct Axis {
     double x, y, z;
 };
 
 __device__ __forceinline__ int plane_count(const int64_t *n, int b, int full) { return n == nullptr ? full : pn2_clamped_rows(n, b, full); }
-
-// the header's sampler: row j of hypothesis h of cloud b among n rows
-__device__ __forceinline__ int64_t plane_sample(unsigned long long seed, int b, int h, int j, int n) {
-    unsigned long long x = seed * kGolden + (((unsigned long long)b << 40) | ((unsigned long long)h << 8) | (unsigned long long)j);
-    x ^= x >> 30;
-    x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 27;
-    x *= 0x94D049BB133111EBull;
-    x ^= x >> 31;
-    return (int64_t)(((x >> 32) * (unsigned long long)n) >> 32);
-}
 
 __device__ __forceinline__ bool plane_takes_part(const int32_t *assign, int64_t at) { return assign == nullptr || assign[at] < 0; }
 
@@ -77,7 +66,7 @@ __global__ __launch_bounds__(kThreads) void plane_hypothesis_kernel(const float 
     const int n = plane_count(n_points, b, N);
     const double nan = __builtin_nan("");
     double nx = nan, ny = nan, nz = nan, d = nan;
-    const int64_t r0 = plane_sample(seed, b, h, 0, n), r1 = plane_sample(seed, b, h, 1, n), r2 = plane_sample(seed, b, h, 2, n);
+    const int64_t r0 = ransac_sample(seed, b, h, 0, n), r1 = ransac_sample(seed, b, h, 1, n), r2 = ransac_sample(seed, b, h, 2, n);    // (ransac_sample.h)
     bool ok = n > 0 && r0 < n && r1 < n && r2 < n && r0 != r1 && r0 != r2 && r1 != r2;
     if (ok) {
         const int64_t base = (int64_t)b * N;

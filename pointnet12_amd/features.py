@@ -6,10 +6,17 @@ extension.  33 numbers per point, invariant to rigid motion, from what the packa
 (``normals.estimate_normals``) and "k nearest within r" lists (``neighbors.GridIndex.query_self`` or ``knn_point``).  The first
 kernel counts three angle bins per neighbour pair into an integer row (``spfh``, a public intermediate); the second adds to every
 row's own histogram the 1 / d^2 weighted mean of its neighbours' histograms.  The rule was written from the paper: it is
-UNVERIFIED AGAINST OPEN3D / PCL, whose binning differs in details (include/pn2.h names the one at ties).  OUT OF SCOPE: feature
-matching and mutual / ratio tests, correspondence RANSAC and global registration, wiring into ``registration.icp``, K above 32,
+UNVERIFIED AGAINST OPEN3D / PCL, whose binning differs in details (include/pn2.h names the one at ties).  OUT OF SCOPE: K above 32,
 PFH and SHOT, a gradient, query points other than the cloud's own.
+
+The descriptor's consumer is here too: ``match_features`` (``pn2_feature_nn2`` / ``pn2_match_pairs``, csrc/feature_match.hip; the
+rule is stated in include/pn2.h under "feature matching" and in numpy in tests/match_ref.py) gives every source row its two nearest
+target rows in feature space by an exact all-pairs search, and keeps the rows that pass a mutual and a ratio test as a compacted
+pair list -- what ``registration.ransac_correspondences`` and ``registration.register_global`` take.  OUT OF SCOPE there: features
+wider than 64 columns, approximate or tree search in feature space, a gradient.
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -202,3 +209,97 @@ def spfh_counts(spfh):
     """``spfh`` uint8 [..., 36] -> ``(counts int32 [..., 33], m int32 [...])``: the 3 x 11 bin counts and the number of pairs.
     Plain torch."""
     return spfh[..., :33].to(torch.int32), spfh[..., 33].to(torch.int32)
+
+
+Matches = collections.namedtuple("Matches", "pair_src pair_tgt count idx dist")
+
+
+def match_workspace_bytes(N, B=1):
+    """Bytes of ``pn2_match_pairs``' workspace for ``B`` clouds of up to ``N`` source rows (host-only call)."""
+    n = _lib.load().pn2_match_pairs_workspace_bytes(int(B), int(N))
+    if n < 0:
+        raise ValueError("match_features: B = %d clouds of N = %d rows are not supported" % (B, N))
+    return int(n)
+
+
+class MatchBuffers:
+    """Everything ``match_features`` writes, allocated once (``match_buffers``): ``idx`` int64 / ``dist`` float32 [B,N,2] (the forward
+    search), ``back_idx`` / ``back_dist`` [B,M,2] (the search with the roles swapped, with ``mutual``), ``pair_src`` / ``pair_tgt``
+    int64 [B,N], ``count`` int64 [B] and the workspace."""
+
+    def __init__(self, N, M, B, device, mutual=True):
+        self.N, self.M, self.B, self.mutual = int(N), int(M), int(B), bool(mutual)
+        i64 = dict(device=device, dtype=torch.int64)
+        self.idx = torch.full((self.B, self.N, 2), self.M, **i64)
+        self.device = self.idx.device
+        self.dist = torch.full((self.B, self.N, 2), float("inf"), device=device, dtype=torch.float32)
+        self.back_idx = torch.full((self.B, self.M, 2), self.N, **i64) if mutual else None
+        self.back_dist = torch.full((self.B, self.M, 2), float("inf"), device=device, dtype=torch.float32) if mutual else None
+        self.pair_src, self.pair_tgt = torch.full((self.B, self.N), -1, **i64), torch.full((self.B, self.N), -1, **i64)
+        self.count = torch.zeros(self.B, **i64)
+        self.workspace = torch.empty(match_workspace_bytes(self.N, self.B), device=device, dtype=torch.uint8)
+
+
+def match_buffers(N, M, B=1, device="cuda", mutual=True):
+    """Preallocates for ``B`` pairs of clouds with ``N`` source and ``M`` target rows.  With ``buffers=`` ``match_features`` allocates
+    nothing, reads nothing back and captures into a graph that stays valid when the features and the device-side counts change."""
+    return MatchBuffers(N, M, B, device, mutual)
+
+
+def _feature_rows(t, what):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _lib.Pn2Error("match_features: %s must live on the GPU: this package has no CPU path" % what)
+    if t.dtype != torch.float32 or t.dim() not in (2, 3) or t.shape[-1] < 1 or t.shape[-2] < 1:
+        raise RuntimeError("match_features: %s must be float32 [N, D] or [B, N, D]" % what)
+    t = t.contiguous()
+    return t[None] if t.dim() == 2 else t
+
+
+def match_features(fs, ft, mutual=True, ratio=0.9, n_source=None, n_target=None, buffers=None):
+    """Correspondences between two clouds from their descriptors: for every source row the nearest target row in feature space (an
+    exact all-pairs search in float32, equal distances resolved towards the lower index), kept iff it passes the tests.
+
+    ``fs`` [N,D] or [B,N,D], ``ft`` [M,D] or [B,M,D] float32 on the GPU, 1 <= D <= 64 (``compute_fpfh``'s [.,33] rows as they are).
+    A row takes part iff its values are all finite and not all zero (the row of an isolated point holds zeros).  ``mutual``: the
+    nearest source row of the matched target row must be the row itself (a second search with the roles swapped).  ``ratio`` (None:
+    off): the nearest distance must be at most ``ratio`` times the second nearest; the kernel compares the squared distances against
+    ``float32(ratio ** 2)``, and a row without a second neighbour passes.  ``n_source`` / ``n_target``: device int64 [B] (or host
+    integers), only that many leading rows count.
+
+    Returns ``Matches(pair_src, pair_tgt, count, idx, dist)`` of device tensors: int64 [B,N] source and target row of every kept
+    pair in ascending source row, int64 [B] how many (entries at and beyond it are not written: -1 when allocated here), and the
+    forward search itself: int64 [B,N,2] (``M``: none) and float32 [B,N,2] squared distances (+inf: none).  [N,D] features drop the
+    leading B.  ``buffers``: a ``MatchBuffers``.  The bytes are the same from run to run."""
+    flat = isinstance(fs, torch.Tensor) and fs.dim() == 2
+    fs, ft = _feature_rows(fs, "fs"), _feature_rows(ft, "ft")
+    B, N, D = fs.shape
+    M, dev = ft.shape[1], fs.device
+    if ft.shape[0] != B or ft.shape[2] != D or ft.device != dev:
+        raise ValueError("match_features: fs and ft disagree on B, D or the device")
+    if D > _lib.MATCH_MAX_D:
+        raise RuntimeError("match_features: D (%d) > %d is not supported (there is no fallback path)" % (D, _lib.MATCH_MAX_D))
+    if ratio is None:
+        ratio2 = float("inf")
+    else:
+        if not float(ratio) >= 0.0:
+            raise ValueError("match_features: ratio must not be negative")
+        ratio2 = float(np.float32(float(ratio) ** 2))
+    buf = buffers
+    if buf is None:
+        buf = MatchBuffers(N, M, B, dev, mutual)
+    elif buf.B != B or buf.N != N or buf.M != M or buf.device != dev or (mutual and not buf.mutual):
+        raise ValueError("match_features: the buffers were made for B = %d, N = %d, M = %d, mutual = %s on %s" %
+                         (buf.B, buf.N, buf.M, buf.mutual, buf.device))
+    n_source = _counts(n_source, B, dev, "match_features: n_source")
+    n_target = _counts(n_target, B, dev, "match_features: n_target")
+    lib, s = _lib.load(), _lib.stream()
+    _lib.check(lib.pn2_feature_nn2(_p(fs), D, _p(ft), D, B, N, M, D, _p(n_source), _p(n_target), _p(buf.idx), _p(buf.dist), s), "pn2_feature_nn2")
+    back = None
+    if mutual:
+        back = buf.back_idx
+        _lib.check(lib.pn2_feature_nn2(_p(ft), D, _p(fs), D, B, M, N, D, _p(n_target), _p(n_source), _p(back), _p(buf.back_dist), s),
+                   "pn2_feature_nn2")
+    _lib.check(lib.pn2_match_pairs(_p(buf.idx), _p(buf.dist), _p(back), B, N, M, ratio2, _p(n_source), _p(buf.pair_src), _p(buf.pair_tgt),
+                                   _p(buf.count), _p(buf.workspace), s), "pn2_match_pairs")
+    res = (buf.pair_src, buf.pair_tgt, buf.count, buf.idx, buf.dist)
+    return Matches(*[t[0] if flat else t for t in res])

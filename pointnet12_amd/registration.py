@@ -7,14 +7,22 @@ extension.  It is the joint consumer of ``neighbors.GridIndex`` ("the nearest ta
 kernel that writes one 29-word partial per 1024 source rows, and a per-cloud kernel that adds the partials in a fixed order, solves
 the 6 x 6 system and updates ``[R | t]`` in fp64.  The loop never reads anything back: a cloud that has converged (or turned out
 singular) is frozen on the device and its later steps return at once.  OUT OF SCOPE: robust weights, a normal-compatibility test,
-multi-resolution, GICP and coloured ICP, global registration, a gradient, pose graphs.
+multi-resolution, GICP and coloured ICP, a gradient, pose graphs.
+
+ICP only converges from a good ``init``; ``register_global`` produces one from two clouds with an unknown relative pose:
+``features.compute_fpfh`` on both, ``features.match_features``, then ``ransac_correspondences`` (``pn2_corr_ransac`` /
+``pn2_corr_refit``, csrc/corr_ransac.hip; the rule is stated in include/pn2.h under "correspondence RANSAC" and in numpy in
+tests/corr_ransac_ref.py): three-pair hypotheses named by an integer function of the seed, each a closed-form rigid transform,
+scored by its count of pairs within ``threshold`` in an all-pairs pass (one hypothesis per lane, the pairs broadcast from LDS), the
+best one refitted by Horn's quaternion method on its inliers.  Nothing is read back.  OUT OF SCOPE there: MSAC / LO-RANSAC scores,
+an adaptive stopping rule, scale estimation, a gradient, wiring into ``FrameSegmenter``.
 """
 import collections
 
 import numpy as np
 import torch
 
-from . import _lib, neighbors
+from . import _lib, features, neighbors
 from . import normals as _normals
 
 _p = _lib.ptr
@@ -234,3 +242,181 @@ def transform_points(points, transform, out=None):
         return res
     out[..., :3] = res
     return out
+
+
+CorrResult = collections.namedtuple("CorrResult", "transform count rmse best_h status")
+GlobalResult = collections.namedtuple("GlobalResult", "transform count rmse best_h status matches")
+GLOBAL_THRESHOLD = 0.3   # register_global's default inlier distance as a multiple of the FPFH radius (1.5 voxels against a radius of 5)
+
+
+def corr_workspace_bytes(N, B=1, iterations=1024):
+    """Bytes of ``pn2_corr_ransac`` / ``pn2_corr_refit``'s workspace for ``B`` pair lists of up to ``N`` pairs and ``iterations``
+    hypotheses (host-only call)."""
+    n = _lib.load().pn2_corr_workspace_bytes(int(B), int(N), int(iterations))
+    if n < 0:
+        raise ValueError("ransac_correspondences: B = %d lists of N = %d pairs with %d hypotheses are not supported" % (B, N, iterations))
+    return int(n)
+
+
+class CorrBuffers:
+    """Everything ``ransac_correspondences`` writes, allocated once (``corr_buffers``): ``T`` float64 [B,12], ``transform`` float64
+    [B,4,4], ``count`` / ``best_count`` int64 [B], ``rmse`` float64 [B], ``sums`` float64 [B,17], ``best_h`` / ``status`` int32 [B],
+    ``hyp_count`` int32 [B,iterations], the workspace, and ``error_flag`` (device int32, cleared at the start of every call; the
+    launches OR ``_lib.CORR_ERR_*`` into it)."""
+
+    def __init__(self, N, B, iterations, device):
+        self.N, self.B, self.H = int(N), int(B), int(iterations)
+        f64 = dict(device=device, dtype=torch.float64)
+        i32 = dict(device=device, dtype=torch.int32)
+        self.T = torch.zeros(self.B, 12, **f64)
+        self.device = self.T.device
+        self.transform = torch.zeros(self.B, 4, 4, **f64)
+        self.transform[:, 3, 3] = 1.0
+        self.rmse, self.sums = torch.zeros(self.B, **f64), torch.zeros(self.B, _lib.CORR_SUMS, **f64)
+        self.count = torch.zeros(self.B, device=device, dtype=torch.int64)
+        self.best_count = torch.zeros(self.B, device=device, dtype=torch.int64)
+        self.best_h, self.status = torch.zeros(self.B, **i32), torch.zeros(self.B, **i32)
+        self.hyp_count = torch.zeros(self.B, self.H, **i32)
+        self.workspace = torch.empty(corr_workspace_bytes(self.N, self.B, self.H), device=device, dtype=torch.uint8)
+        self.error_flag = torch.zeros(1, **i32)
+
+    def check(self, none_ok=True):
+        """Reads ``error_flag`` back: ``ValueError`` for a pair whose rows are out of range or not finite and, unless ``none_ok``
+        (``status`` says which clouds), for a cloud in which no transform was found."""
+        flag = int(self.error_flag.item())
+        if flag & _lib.CORR_ERR_PAIR:
+            raise ValueError("ransac_correspondences: a pair names a row outside its cloud; it was never an inlier")
+        if flag & _lib.CORR_ERR_NONFINITE:
+            raise ValueError("ransac_correspondences: a paired point is not finite; the pair was never an inlier")
+        if flag & _lib.CORR_ERR_NONE and not none_ok:
+            raise ValueError("ransac_correspondences: a cloud has no valid hypothesis, or its best one has fewer than 3 inliers")
+
+
+def corr_buffers(N, B=1, iterations=1024, device="cuda"):
+    """Preallocates for ``B`` pair lists of up to ``N`` pairs (the source clouds' rows) and ``iterations`` hypotheses.  With
+    ``buffers=`` ``ransac_correspondences`` allocates nothing and reads nothing back, and captures into a graph that stays valid when
+    the points, the pairs and the device-side count change."""
+    return CorrBuffers(N, B, iterations, device)
+
+
+def ransac_correspondences(source, target, matches, threshold, iterations=1024, seed=0, edge_ratio=0.9, refine=2, buffers=None):
+    """The rigid transform that takes the source rows of a pair list onto their target rows, in the presence of wrong pairs:
+    ``iterations`` three-pair hypotheses named by an integer function of ``seed``, each scored by its count of pairs that land within
+    ``threshold`` of their target row, the best one (the lowest index among equals) refitted ``refine`` times by least squares on its
+    inliers (Horn's quaternion method: inliers that lie in a plane are handled, a reflection is never returned).
+
+    ``source`` [N,ld] or [B,N,ld], ``target`` [M,ld] or [B,M,ld] float32 on the GPU, 3 <= ld <= 16.  ``matches``:
+    ``features.match_features``' result, or any ``(pair_src, pair_tgt, count)`` of device int64 tensors [B,N], [B,N], [B] (``count``
+    may be None: all N).  A hypothesis is dropped unless its three source rows and its three target rows are distinct and every edge
+    of the source triangle is as long as the matching target edge to within ``edge_ratio`` (``min >= edge_ratio * max``; 0: off).
+
+    Returns ``CorrResult(transform, count, rmse, best_h, status)`` of device tensors: float64 [B,4,4]; int64 [B] the pairs within
+    ``threshold`` under the result and float64 [B] the root mean square of their distances (one closing evaluation); int32 [B] the
+    winning hypothesis (-1: none was valid); int32 ``_lib.CORR_NONE`` / ``_lib.CORR_DEGENERATE`` bits.  A cloud with ``CORR_NONE``
+    gets the identity, count 0 and rmse 0.  [N,ld] clouds drop the leading B."""
+    what = "ransac_correspondences"
+    flat, src, tgt = _pairs(source, target, what)
+    B, N, _ = src.shape
+    M, dev = tgt.shape[1], src.device
+    H = int(iterations)
+    threshold, edge_ratio = float(threshold), float(edge_ratio)
+    if not (np.isfinite(threshold) and threshold >= 0.0) or not 0.0 <= edge_ratio <= 1.0:
+        raise ValueError("%s: threshold must be finite and not negative, edge_ratio in [0, 1]" % what)
+    if not 1 <= H <= 65536 or int(refine) < 0:
+        raise ValueError("%s: iterations must be 1 .. 65536 and refine not negative" % what)
+    pair_src, pair_tgt, count = matches[0], matches[1], matches[2]
+    for t in (pair_src, pair_tgt):
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.int64 or t.numel() != B * N or not t.is_contiguous():
+            raise ValueError("%s: the pair lists must be contiguous int64 tensors [B, N] = [%d, %d] on the clouds' device" % (what, B, N))
+    count = neighbors._counts(count, B, dev, what + ": count")
+    buf = buffers
+    if buf is None:
+        buf = CorrBuffers(N, B, H, dev)
+    else:
+        if buf.B != B or buf.N != N or buf.H != H or buf.device != dev:
+            raise ValueError("%s: the buffers were made for B = %d, N = %d, iterations = %d on %s" % (what, buf.B, buf.N, buf.H, buf.device))
+        buf.error_flag.zero_()
+    buf.rmse.zero_()
+    buf.count.zero_()
+    lib, s = _lib.load(), _lib.stream()
+    clouds = (_p(src), src.shape[2], _p(tgt), tgt.shape[2], B, N, M, _p(pair_src), _p(pair_tgt), _p(count))
+    _lib.check(lib.pn2_corr_ransac(*clouds, H, int(seed) & (2 ** 64 - 1), edge_ratio, threshold, _p(buf.T), None, _p(buf.hyp_count), _p(buf.best_h),
+                                   _p(buf.best_count), _p(buf.status), _p(buf.error_flag), _p(buf.workspace), s), "pn2_corr_ransac")
+    for flags in [0] * int(refine) + [_lib.CORR_EVAL_ONLY]:
+        _lib.check(lib.pn2_corr_refit(*clouds, threshold, flags, _p(buf.T), _p(buf.count), _p(buf.rmse), _p(buf.sums), _p(buf.status),
+                                      _p(buf.workspace), s), "pn2_corr_refit")
+    buf.transform[:, :3, :].copy_(buf.T.view(B, 3, 4))
+    res = (buf.transform, buf.count, buf.rmse, buf.best_h, buf.status)
+    return CorrResult(*[t[0] if flat else t for t in res])
+
+
+class GlobalBuffers:
+    """Everything ``register_global`` writes, allocated once (``global_buffers``): ``source_fpfh`` / ``target_fpfh``
+    (``features.FpfhBuffers``), ``matches`` (``features.MatchBuffers``) and ``corr`` (``CorrBuffers``, whose ``error_flag`` is
+    ``error_flag`` here)."""
+
+    def __init__(self, N, M, B, k, iterations, device, search="grid", mutual=True):
+        self.N, self.M, self.B, self.k, self.H, self.search = int(N), int(M), int(B), int(k), int(iterations), search
+        self.source_fpfh = features.FpfhBuffers(N, B, k, device, search)
+        self.target_fpfh = features.FpfhBuffers(M, B, k, device, search)
+        self.matches = features.MatchBuffers(N, M, B, device, mutual)
+        self.corr = CorrBuffers(N, B, iterations, device)
+        self.device, self.error_flag = self.corr.device, self.corr.error_flag
+
+    def check(self, none_ok=True):
+        """Reads the three error flags back: ``FpfhBuffers.check`` of both clouds, then ``CorrBuffers.check``."""
+        self.source_fpfh.check()
+        self.target_fpfh.check()
+        self.corr.check(none_ok)
+
+
+def global_buffers(N, M, B=1, k=32, iterations=1024, device="cuda", search="grid", mutual=True):
+    """Preallocates ``register_global`` for ``B`` pairs of ``N`` source and ``M`` target rows.  With ``buffers=`` the call allocates
+    nothing, reads nothing back and captures into a graph that stays valid when the points and the device-side counts change."""
+    return GlobalBuffers(N, M, B, k, iterations, device, search, mutual)
+
+
+def register_global(source, target, radius, threshold=None, k=32, normals=None, search="grid", viewpoint="origin", mutual=True, ratio=0.9,
+                    iterations=1024, seed=0, edge_ratio=0.9, refine=2, n_source=None, n_target=None, buffers=None):
+    """Registers ``source`` to ``target`` WITHOUT an initial guess: ``features.compute_fpfh(cloud, radius, k)`` on both clouds,
+    ``features.match_features(mutual=mutual, ratio=ratio)`` on the descriptors, ``ransac_correspondences(threshold, iterations, seed,
+    edge_ratio, refine)`` on the pairs.  The result is meant as ``icp(init=...)``: RANSAC's answer is right to about ``threshold``,
+    ICP finishes the job.
+
+    ``source`` [N,ld] or [B,N,ld], ``target`` [M,ld] or [B,M,ld] float32 on the GPU.  ``threshold`` defaults to ``0.3 * radius``
+    (``GLOBAL_THRESHOLD``: the usual 1.5 voxels against a descriptor radius of 5 voxels).  ``normals``: a pair ``(source_normals,
+    target_normals)`` of float32 tensors with the unit normals in columns 0..2; without it ``compute_fpfh`` estimates them, oriented
+    towards ``viewpoint`` (``estimate_normals``' argument, or a pair ``(source_viewpoint, target_viewpoint)``) -- THE DESCRIPTOR
+    DEPENDS ON THE SIGN OF THE NORMALS, the default ``"origin"`` suits two scans that are each in their own sensor's frame.  ``search`` is ``compute_fpfh``'s.  ``n_source`` / ``n_target``: device int64 [B] (or host integers).
+
+    Returns ``GlobalResult(transform, count, rmse, best_h, status, matches)``: ``ransac_correspondences``' five and the ``Matches``.
+    ``buffers``: a ``GlobalBuffers``; ``buffers.check()`` reads the error flags back."""
+    what = "register_global"
+    flat, src, tgt = _pairs(source, target, what)
+    B, N, _ = src.shape
+    M, dev = tgt.shape[1], src.device
+    if not float(radius) > 0:
+        raise ValueError("register_global: radius must be positive")
+    threshold = GLOBAL_THRESHOLD * float(radius) if threshold is None else float(threshold)
+    buf = buffers
+    if buf is not None and (buf.B != B or buf.N != N or buf.M != M or buf.device != dev or buf.k < int(k) or buf.H != int(iterations) or
+                            buf.search != search):
+        raise ValueError("register_global: the buffers were made for B = %d, N = %d, M = %d, k >= %d, iterations = %d, search = \"%s\" on %s" %
+                         (buf.B, buf.N, buf.M, buf.k, buf.H, buf.search, buf.device))
+    ns, nt = (None, None) if normals is None else normals
+    if normals is not None and flat:
+        ns, nt = ns[None], nt[None]
+    vs, vt = viewpoint if isinstance(viewpoint, (tuple, list)) and len(viewpoint) == 2 else (viewpoint, viewpoint)
+    n_source = neighbors._counts(n_source, B, dev, what + ": n_source")
+    n_target = neighbors._counts(n_target, B, dev, what + ": n_target")
+    fs = features.compute_fpfh(src, radius, k=k, normals=ns, viewpoint=vs, n_points=n_source, search=search,
+                               buffers=None if buf is None else buf.source_fpfh)
+    ft = features.compute_fpfh(tgt, radius, k=k, normals=nt, viewpoint=vt, n_points=n_target, search=search,
+                               buffers=None if buf is None else buf.target_fpfh)
+    m = features.match_features(fs, ft, mutual=mutual, ratio=ratio, n_source=n_source, n_target=n_target,
+                                buffers=None if buf is None else buf.matches)
+    r = ransac_correspondences(src, tgt, m, threshold, iterations=iterations, seed=seed, edge_ratio=edge_ratio, refine=refine,
+                               buffers=None if buf is None else buf.corr)
+    if flat:
+        return GlobalResult(r.transform[0], r.count[0], r.rmse[0], r.best_h[0], r.status[0], features.Matches(*[t[0] for t in m]))
+    return GlobalResult(*r, m)
