@@ -1369,6 +1369,59 @@ int pn2_voxel_components(const float *pts, int ld, const int64_t *row_begin, con
                          int32_t *comp_points, int32_t *comp_voxels, int32_t *comp_label, int64_t *comp_count, int *err, void *workspace,
                          pn2_stream_t stream);
 
+/* ---- segment boxes: an oriented bounding box per segment, an L-shape fit swept by angle (csrc/boxes.hip), added within ABI 15
+ * (purely additive: no version change) ------------------------------------------------------------------------------------------------
+ * Length, width, height and heading of every segment of an `inverse`-style map: pn2_voxel_components' row_component / comp_count
+ * (an instance's box), pn2_voxel_grid's inverse / out_count, or any other.  The reference has no such function.  tests/box_ref.py
+ * restates the rule in numpy.  Every output is an integer, a minimum or a maximum (or one fixed chain of float32 operations on
+ * those), so the bytes depend neither on the order of the rows nor on which thread saw which row.
+ * SEGMENTS are pn2_segment_mean's, unchanged: seg int32 per row, a NEGATIVE seg takes no part; a seg at or beyond the device-side
+ *   out_count[b] (clamped to max_rows) takes no part and sets PN2_BOX_ERR_RANGE; row_begin / row_count / max_rows / out_begin /
+ *   out_count mean what they mean there, every count is read on the device and clamped to [0, max_rows].
+ * COLUMNS.  pts is float32 of pitch ld; three DISTINCT column indices cx, cy, cz < ld name the two ground-plane coordinates and the
+ *   height ((0, 1, 2): KITTI's z-up).
+ * TAKING PART.  A row of a segment takes part iff its three values are finite and |x|, |y| <= 2^60.  Any other row of a segment takes
+ *   no part and sets PN2_BOX_ERR_NONFINITE (a stated choice: a box with one NaN row left out is more use than a NaN box; the
+ *   magnitude cut removes every overflow from the arithmetic below).  Rows with a negative or out-of-range seg are not looked at.
+ * ANGLE TABLE.  angles: float32 [A, 4] on the device, (c_a, s_a, yaw_a, 0), 1 <= A <= PN2_BOX_MAX_ANGLES.  The kernels do no
+ *   trigonometry: the caller fills the table (pointnet12_amd/boxes.py: theta_a = a * (pi / 2) / A in fp64, c = float32(cos theta),
+ *   s = float32(sin theta), yaw = float32(theta)).
+ * PROJECTION, per row and angle, float32, every operation rounded on its own:  u = (c*x) + (s*y),  v = (c*y) - (s*x).
+ * EXTENT.  u0, u1, v0, v1: the minimum and maximum of u and of v over the segment's rows IN THE TOTAL ORDER OF THE ORDER-PRESERVING
+ *   uint32 KEY (bits | 0x80000000 for a clear sign bit, ~bits otherwise: -0.0 < +0.0).  The same order gives z0, z1 of the height column
+ *   and the raw box lo[3], hi[3] (of cx, cy, cz).  lu = u1 - u0, lv = v1 - v0, area = lu * lv.
+ * SCORE (the closeness criterion of Zhang et al., "Efficient L-shape fitting for vehicle detection using laser scanners", IV 2017,
+ *   quantised).  d0 float32, finite; d0 <= 0 means AREA ONLY: the score of every angle is 0.  Otherwise, per row and angle:
+ *     e = fminf(fminf(u - u0, u1 - u), fminf(v - v0, v1 - v));  d = fmaxf(e, d0);  q = d0 / d (one IEEE float32 division);
+ *     t = (int32)(q * 1048576.0f) (an exact product, truncated: 0 <= t <= 2^20);  score_a = sum of t in int64 (at most 2^29 rows: exact).
+ * SELECTION.  The angle with the largest score wins, among equal scores the smaller area (float32 <), among equal areas the LOWEST a.
+ * OUTPUTS, per segment s of cloud b at row out_begin[b] + s (center, size, lo, hi: three floats per row):
+ *   angle  int32, -1 for a segment without rows;      yaw = yaw_a;      size = (lu, lv, z1 - z0);
+ *   center: cu = 0.5f * (u0 + u1), cv = 0.5f * (v0 + v1), x = (c*cu) - (s*cv), y = (s*cu) + (c*cv), z = 0.5f * (z0 + z1);
+ *   lo, hi; n int32: the rows that took part; score int64.
+ *   A segment without rows writes +0.0 / -1 / 0.  Output rows at or beyond out_count[b] are not written.  angle, lo, hi, n and score
+ *   may each be NULL.
+ * Six plain launches on the caller's stream sized by max_rows (csrc/boxes.hip: rows bucketed by segment through an integer cursor,
+ * then one angle per lane); no allocation, no host synchronisation, no float atomics, no thread waits for another thread's write.
+ * A segment with at least split_rows rows (0: the default, 4096; otherwise 64 .. PN2_VOXEL_MAX_ROWS) is swept by a workgroup of 16 waves
+ * instead of one wave; THE BYTES ARE THE SAME whichever serves it, and from run to run.
+ * err (device int, caller zeroes, may be NULL) receives PN2_BOX_ERR_RANGE and PN2_BOX_ERR_NONFINITE; the bits are disjoint from
+ * PN2_VOXEL_ERR_*, PN2_SEGMENT_ERR_*, PN2_CLUSTER_ERR_* and PN2_PANOPTIC_ERR_*: one word serves a downsample -> cluster -> boxes chain.
+ * workspace: pn2_segment_boxes_workspace_bytes(B, max_rows) bytes of device memory (16 per row and 4 per cloud, rounded), 16-byte
+ * aligned; it may hold anything on entry.
+ * PN2_EINVAL without a launch: a null pts / seg / row_begin / row_count / out_begin / out_count / angles / center / size / yaw /
+ * workspace, A outside 1..256, columns that are not distinct or not below ld, B < 1 or B > 65535, max_rows < 0 or >
+ * PN2_VOXEL_MAX_ROWS, a split_rows other than 0 or 64 .. PN2_VOXEL_MAX_ROWS, a d0 that is not finite, a pointer that is not 4-byte
+ * (score: 8-byte; angles, workspace: 16-byte) aligned; pn2_segment_boxes_workspace_bytes returns PN2_EINVAL for such B / max_rows. */
+#define PN2_BOX_MAX_ANGLES 256
+#define PN2_BOX_ERR_RANGE 1024
+#define PN2_BOX_ERR_NONFINITE 2048
+int64_t pn2_segment_boxes_workspace_bytes(int B, int64_t max_rows);
+int pn2_segment_boxes(const float *pts, int ld, int cx, int cy, int cz, const int32_t *seg, const int64_t *row_begin, const int64_t *row_count,
+                      int B, int64_t max_rows, const int64_t *out_begin, const int64_t *out_count, const float *angles, int A, float d0,
+                      int split_rows, float *center, float *size, float *yaw, int32_t *angle, float *lo, float *hi, int32_t *n,
+                      int64_t *score, int *err, void *workspace, pn2_stream_t stream);
+
 /* ---- camera colour lookup for points (csrc/image.hip), added within ABI 15 (purely additive: no version change) -------------------
  * pn2_sample_image writes the colour of the pixel under each projected point: the per-point loop of
  * data_utils/ColorGenerator_Loader.py:63-65 (`pts_color[i] = frame_HSV[row, col]` inside the frame) and the divisions of :68-69, for

@@ -139,6 +139,9 @@ SIGNATURES = {
     "pn2_segment_mean": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "pn2_segment_mean_bwd": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "pn2_segment_mode": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "pn2_segment_boxes_workspace_bytes": (_i64, [_i, _i64]),
+    "pn2_segment_boxes": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                               _vp, _vp, _vp]),
     "pn2_voxel_components_workspace_bytes": (_i64, [_i, _i64]),
     "pn2_voxel_components": (_i, [_vp, _i, _vp, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp,
                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -184,6 +187,9 @@ SEGMENT_MAX_COLS = 16    # PN2_SEGMENT_MAX_COLS: the widest pn2_segment_mean / p
 SEGMENT_ERR_RANGE, SEGMENT_ERR_NONFINITE = 4, 8      # PN2_SEGMENT_ERR_* (disjoint from VOXEL_ERR_*: they share VoxelGrid.error_flag)
 CLUSTER_ERR_INDEX, CLUSTER_ERR_CELL, CLUSTER_ERR_CAP, CLUSTER_ERR_ROWS = 16, 32, 64, 128     # PN2_CLUSTER_ERR_* (disjoint from both)
 PANOPTIC_ERR_CLASS, PANOPTIC_ERR_ROWS = 256, 512     # PN2_PANOPTIC_ERR_* (disjoint from all of the above)
+BOX_ERR_RANGE, BOX_ERR_NONFINITE = 1024, 2048        # PN2_BOX_ERR_* (disjoint from all of the above: a downsample -> cluster -> boxes chain shares one word)
+BOX_MAX_ANGLES = 256     # PN2_BOX_MAX_ANGLES: the longest angle table of pn2_segment_boxes
+BOX_SPLIT_ROWS = 4096    # pn2_segment_boxes' split_rows = 0: the rows from which a workgroup sweeps a segment instead of a wave
 
 
 class BnLazy(ctypes.Structure):
@@ -245,7 +251,7 @@ class _Timed:
                                                    "pn2_segment_reduce_workspace_bytes", "pn2_voxel_components_workspace_bytes",
                                                    "pn2_panoptic_workspace_bytes", "pn2_lovasz_workspace_bytes", "pn2_lovasz_tile_rows",
                                                    "pn2_grid_workspace_bytes", "pn2_icp_workspace_bytes", "pn2_plane_workspace_bytes",
-                                                   "pn2_match_pairs_workspace_bytes", "pn2_corr_workspace_bytes"):
+                                                   "pn2_match_pairs_workspace_bytes", "pn2_corr_workspace_bytes", "pn2_segment_boxes_workspace_bytes"):
             return fn
 
         def timed(*args):

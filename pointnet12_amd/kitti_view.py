@@ -56,6 +56,7 @@ Differences from the reference, all deliberate:
 """
 import ctypes
 import json
+import math
 
 import numpy as np
 import torch
@@ -683,13 +684,18 @@ def render_points(pts_3d, labels, colors, camera, point_size=2, background=(0, 0
 class InstanceSpec:
     """How ``FrameSegmenter.label_scan(instances=)`` makes instances: cells ``voxel_size`` METRES wide (a scalar), ``things`` -- the
     predicted classes that get instance ids (for SemanticKITTI's shifted training classes ``range(8)``: car .. motorcyclist) --,
-    ``connectivity`` 6 / 18 / 26 and ``min_points``, the fewest rows of an instance (smaller components get no id)."""
+    ``connectivity`` 6 / 18 / 26 and ``min_points``, the fewest rows of an instance (smaller components get no id).  ``boxes=True``: an
+    oriented box per instance as well (``boxes.instance_boxes`` with a table of ``box_angles`` angles and the closeness floor ``box_d0``
+    in metres)."""
 
-    def __init__(self, voxel_size, things, connectivity=26, min_points=1):
+    def __init__(self, voxel_size, things, connectivity=26, min_points=1, boxes=False, box_angles=64, box_d0=0.05):
         self.voxel_size, self.things = float(voxel_size), sorted(set(int(t) for t in things))
         self.connectivity, self.min_points = int(connectivity), int(min_points)
         if not self.things or self.things[0] < 0 or connectivity not in (6, 18, 26) or self.min_points < 1 or not self.voxel_size > 0:
             raise ValueError("InstanceSpec: voxel_size > 0, at least one class >= 0 in things, connectivity 6 / 18 / 26, min_points >= 1")
+        self.boxes, self.box_angles, self.box_d0 = bool(boxes), int(box_angles), float(box_d0)
+        if not 1 <= self.box_angles <= _lib.BOX_MAX_ANGLES or not math.isfinite(self.box_d0):
+            raise ValueError("InstanceSpec: 1 <= box_angles <= %d, box_d0 finite" % _lib.BOX_MAX_ANGLES)
         self._member = {}
 
     def member(self, device):
@@ -977,7 +983,9 @@ class FrameSegmenter:
         ``scan_labels``: ``id + 1``, 0 for the rows the filter dropped and for rows without an instance (a class outside ``things``, a
         row that disagrees with its cell's majority, a component below ``min_points``); ``"instance_count"`` (int64 ``[1]`` on the
         device); ``"kept_classes"`` (int32: the kept rows' predicted classes, the first ``count`` entries mean something) and
-        ``"kept_instances"`` (int32: their ids, -1 for none -- an ``inverse``-style map for ``voxel.segment_mean``).  Ids are numbered by
+        ``"kept_instances"`` (int32: their ids, -1 for none -- an ``inverse``-style map for ``voxel.segment_mean``).  With
+        ``instances.boxes`` also ``"instance_boxes"``: a ``boxes.Boxes`` over the kept rows in metres, instance ``id`` at row ``id``
+        (the first ``instance_count`` rows mean something; its error bits go to the instance grid's ``error_flag``).  Ids are numbered by
         each instance's lowest kept row.  With a device generator nothing is read back.  ``kitti.write_labels(fn, scan_labels,
         scan_instances)`` writes both halves of the ``.label`` words.  ``instances=None`` leaves this call exactly as it was.
 
@@ -1038,3 +1046,12 @@ class FrameSegmenter:
         scan.scatter_(0, torch.where(live, out["index"].long().clamp_(0, rows - 1), rows), torch.where(live, comps.row_component + 1, 0))
         out.update({"scan_instances": scan[:M], "instance_count": comps.count, "kept_classes": classes,
                     "kept_instances": comps.row_component})
+        if spec.boxes:
+            from . import boxes as BX
+            buf = work.get("boxes")
+            if buf is None or buf.angles != spec.box_angles:
+                buf = work["boxes"] = BX.buffers(rows, 1, rows, spec.box_angles, dev)
+            # (the error bits join the grid's word, which downsample cleared: one word for the chain)
+            out["instance_boxes"] = BX.segment_boxes(pts, comps.row_component, comps.count, angles=spec.box_angles, d0=spec.box_d0,
+                                                     row_begin=held["begin"], row_count=out["count"], max_rows=rows, buffers=buf,
+                                                     error_flag=grid.error_flag)

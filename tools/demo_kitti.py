@@ -2,7 +2,7 @@
 """One frame of the reference's KITTI demo (``python pcdvis.py``) on the HIP library: scan -> labels -> pixels -> two images,
 three with ``--ego``.
 
-    python tools/demo_kitti.py [--out DIR] [--npoints 25000] [--seed 0] [--merge] [--time] [--raw [--labels-out FILE [--instances SIZE]] [--normals K[:RADIUS]] [--ground THRESHOLD]] [--ego CAMERA.json [--render-option FILE.json]] [--image FILE]
+    python tools/demo_kitti.py [--out DIR] [--npoints 25000] [--seed 0] [--merge] [--time] [--raw [--labels-out FILE [--instances SIZE [--boxes-out FILE]]]] [--normals K[:RADIUS]] [--ground THRESHOLD]] [--ego CAMERA.json [--render-option FILE.json]] [--image FILE]
     python tools/demo_kitti.py --root $KITTI_ROOT --part 01 --index 0 --calib DIR --config semantic-kitti.yaml [--checkpoint CKPT]
 
 Without ``--root`` the scan is synthetic (``synthetic.kitti_cloud``, un-normalised back to metres), the calibration is the one
@@ -32,6 +32,9 @@ raw scan takes the majority label of its 5 nearest drawn rows within 1 m, mapped
 metres and the cells of the "thing" classes (training classes 0 .. 7: car .. motorcyclist) are clustered per class under 26
 connectivity (``kitti_view.InstanceSpec``, ``voxel.VoxelGrid.components``, ``pn2_voxel_components``); a row's instance is ``id + 1``, 0
 for none, and the low halves are what they are without the option, byte for byte.
+``--boxes-out FILE`` (with ``--instances``) writes one text line per instance, ``x y z l w h yaw class n``: the oriented box of
+``boxes.instance_boxes`` (``pn2_segment_boxes``; metres and radians, the longer side first, yaw in [0, pi)), the instance's majority
+training class and its rows.
 ``--voxel SIZE`` (with ``--raw``) downsamples the kept rows to one row per occupied cell of SIZE metres before the choice
 (``voxel.VoxelGrid``, ``pn2_voxel_grid``), which is then drawn from the voxel count.  ``--voxel-reduce mean`` shows each cell's mean row
 (centroid and mean remission, ``pn2_segment_mean``) instead of its first, ``--voxel-labels mode`` takes the cell's majority label.
@@ -231,6 +234,7 @@ def main():
                     help="with --labels-out: Euclidean clustering of the thing classes on a grid of SIZE metres; instance ids in the high halves")
     ap.add_argument("--normals", metavar="K[:RADIUS]", help="with --raw: also write normals.png, the drawn rows' surface normals as colours")
     ap.add_argument("--ground", type=float, metavar="THRESHOLD", help="with --raw: also write ground.png, the drawn rows on / off the RANSAC ground plane")
+    ap.add_argument("--boxes-out", metavar="FILE", help="with --instances: one line per instance, x y z l w h yaw class n (boxes.instance_boxes)")
     ap.add_argument("--search", choices=("brute", "grid"), default="brute",
                     help="the neighbour search of --labels-out and --normals: pn2_knn's brute force, or the uniform grid of neighbors.GridIndex "
                          "(--normals then needs a RADIUS)")
@@ -282,6 +286,8 @@ def main():
         ap.error("--labels-out needs --raw and does not go with --merge (merged classes have no raw id)")
     if args.instances is not None and not args.labels_out:
         ap.error("--instances needs --labels-out")
+    if args.boxes_out and args.instances is None:
+        ap.error("--boxes-out needs --instances")
     if args.voxel is None and (args.voxel_reduce != "first" or args.voxel_labels != "first"):
         ap.error("--voxel-reduce / --voxel-labels need --voxel")
     if args.voxel is not None and not args.raw:
@@ -307,12 +313,24 @@ def main():
         if args.labels_out:
             out = seg.label_scan(scan, words, scan_filter=scan_filter, rng=gen, lut=kitti.inverse_label_lut(cfg["learning_map_inv"]),
                                  background=frame, voxel=grid, image=camera_image, search=args.search,
-                                 instances=None if args.instances is None else V.InstanceSpec(args.instances, range(8)))
+                                 instances=None if args.instances is None else V.InstanceSpec(args.instances, range(8),
+                                                                                                boxes=bool(args.boxes_out)))
             kitti.write_labels(args.labels_out, out["scan_labels"], out.get("scan_instances"))
             print("labelled %d of %d rows; wrote %s" % (int((out["scan_labels"] != 0).sum()), len(scan), args.labels_out))
             if args.instances is not None:
                 print("%d instances of the thing classes on %d rows (cells of %g m)"
                       % (int(out["instance_count"].item()), int((out["scan_instances"] != 0).sum()), args.instances))
+            if args.boxes_out:
+                from pointnet12_amd import boxes, voxel as VX
+                S = int(out["instance_count"].item())
+                b = boxes.canonical(out["instance_boxes"])
+                classes = VX.segment_mode(out["kept_classes"], out["kept_instances"], out["instance_count"], row_begin=seg._raw_state["begin"],
+                                          row_count=out["count"])
+                table = torch.cat([b.center[:S], b.size[:S], b.yaw[:S, None]], 1).cpu().numpy()
+                with open(args.boxes_out, "w") as f:
+                    for row, c, n in zip(table, classes[:S].cpu().tolist(), b.n[:S].cpu().tolist()):
+                        f.write("%.3f %.3f %.3f %.3f %.3f %.3f %.4f %d %d\n" % (*row, c, n))
+                print("wrote %d boxes to %s" % (S, args.boxes_out))
         else:
             out = seg.frame_raw(scan, words, scan_filter=scan_filter, rng=gen, background=frame, voxel=grid, image=camera_image)
         print("raw scan of %d rows, %d kept by the device filter; filter error flag %d"
