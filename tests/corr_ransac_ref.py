@@ -146,9 +146,14 @@ def inliers(src_b, tgt_b, ps, pt, n, T, threshold):
 
 def refit_sums(p, q, dd):
     """The seventeen sums over inlier rows p, q [m,3] with their d2 -> (sums [17], abs_sums [17])."""
-    cols = [np.ones(len(p))] + [p[:, a] for a in range(3)] + [q[:, a] for a in range(3)] + [p[:, a] * q[:, c] for a in range(3) for c in range(3)] + [dd]
-    Tm = np.stack(cols, 1) if len(p) else np.zeros((0, SUMS))
+    Tm = refit_terms(p, q, dd)
     return Tm.sum(0), np.abs(Tm).sum(0)
+
+
+def refit_terms(p, q, dd):
+    """-> [m,17]: the seventeen terms of every inlier pair, in row order -- what ``refit_sums`` adds up."""
+    cols = [np.ones(len(p))] + [p[:, a] for a in range(3)] + [q[:, a] for a in range(3)] + [p[:, a] * q[:, c] for a in range(3) for c in range(3)] + [dd]
+    return np.stack(cols, 1) if len(p) else np.zeros((0, SUMS))
 
 
 def horn_matrix(S):

@@ -15,6 +15,15 @@ def default_cell(max_d2):
     return float(np.sqrt(np.float64(np.float32(max_d2))) * (1.0 + 2.0 ** -20))
 
 
+def disc_cloud(rng, B, M, ld=4):
+    """[B, M, ld] float32: a uniform disc of radius 12 (r = 12 sqrt(u), a random angle), z in [-1.5, 1.5); the columns from 3 on are
+    not coordinates."""
+    r, a = 12.0 * np.sqrt(rng.random((B, M))), 2 * np.pi * rng.random((B, M))
+    pts = rng.random((B, M, ld)).astype(np.float32)
+    pts[..., 0], pts[..., 1], pts[..., 2] = r * np.cos(a), r * np.sin(a), 3 * rng.random((B, M)) - 1.5
+    return pts
+
+
 def cells(p, origin, cell):
     """p [..., 3] float32 -> (q int64 [..., 3], valid bool [...]): q = floor(((double)p - origin) / cell), valid iff -2^20 <= q < 2^20
     on all three axes (NaN and inf fail).  q is 0 where the row is invalid."""

@@ -101,6 +101,22 @@ def update(T, x):
     return np.array(out), th, math.sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2])
 
 
+def step_terms(p, tgt_b, normals_b, j, metric):
+    """p [n,3] fp64 (the transformed source), j int64 [n] (the K = 1 answers, M: nobody) -> (t [m,28], rows int64 [m], part bool [n]):
+    the terms a step adds up, the source row each of them comes from (POINT: three terms per row, axis by axis) and the rows that
+    take part (PLANE: matched to a target whose normal is finite and not zero)."""
+    M = len(tgt_b)
+    part = j < M
+    jj = np.where(part, j, 0)
+    e = p - tgt_b[jj, :3].astype(np.float64)
+    if metric == PLANE:
+        nv = normals_b[jj, :3].astype(np.float64)
+        part = part & np.isfinite(nv).all(-1) & ~(nv == 0).all(-1)
+        return terms(p[part], e[part], nv[part]), np.flatnonzero(part), part
+    t = np.concatenate([terms(p[part], e[part], np.broadcast_to(AXES[a], (int(part.sum()), 3))) for a in range(3)])
+    return t, np.tile(np.flatnonzero(part), 3), part
+
+
 def icp_step(src, tgt, normals, T, status, iters, max_d2, origin, cell, metric, flags=0, tol_rot=0.0, tol_trans=0.0, n_src=None, n_tgt=None):
     """One pn2_icp_step on numpy inputs: src [B,N,ld], tgt [B,M,ld] float32, normals [B,M,>=3] float32 (None for POINT), T [B,12]
     fp64, status / iters int32 [B] -- none of them written to.  Returns a dict: T, x [B,6], status, iters, sums [B,28], abs_sums
@@ -128,15 +144,7 @@ def icp_step(src, tgt, normals, T, status, iters, max_d2, origin, cell, metric, 
             if g["err_query"]:
                 out["err"] |= ERR_QUERY
         out["corr"][b, :n] = j
-        part = j < M
-        jj = np.where(part, j, 0)
-        e = p - tgt[b, jj, :3].astype(np.float64)
-        if metric == PLANE:
-            nv = np.asarray(normals, np.float32)[b, jj, :3].astype(np.float64)
-            part = part & np.isfinite(nv).all(-1) & ~(nv == 0).all(-1)
-            t = terms(p[part], e[part], nv[part])
-        else:
-            t = np.concatenate([terms(p[part], e[part], np.broadcast_to(AXES[a], (int(part.sum()), 3))) for a in range(3)])
+        t, _, part = step_terms(p, tgt[b], None if metric == POINT else np.asarray(normals, np.float32)[b], j, metric)
         out["sums"][b], out["abs_sums"][b], out["count"][b] = t.sum(0), np.abs(t).sum(0), part.sum()
         if ev:
             continue

@@ -135,13 +135,18 @@ def inliers(pts_b, n, assign_b, plane, threshold):
 
 def refit_sums(pts_b, inl, plane):
     """-> (sums [10], abs_sums [10]): count, sum q, sum q q^T (xx, xy, xz, yy, yz, zz) over the inliers, q = double(p) - (-d) n."""
+    T = refit_terms(pts_b, inl, plane)
+    return T.sum(0), np.abs(T).sum(0)
+
+
+def refit_terms(pts_b, inl, plane):
+    """-> [m,10]: the ten terms of every inlier, in row order -- what ``refit_sums`` adds up."""
     P = np.asarray(plane, np.float64)
     s = -P[3] * P[:3]
     q = pts_b[inl, :3].astype(np.float64) - s
     cols = [np.ones(len(q)), q[:, 0], q[:, 1], q[:, 2], q[:, 0] * q[:, 0], q[:, 0] * q[:, 1], q[:, 0] * q[:, 2], q[:, 1] * q[:, 1],
             q[:, 1] * q[:, 2], q[:, 2] * q[:, 2]]
-    T = np.stack(cols, 1) if len(q) else np.zeros((0, 10))
-    return T.sum(0), np.abs(T).sum(0)
+    return np.stack(cols, 1) if len(q) else np.zeros((0, 10))
 
 
 def sym_eig3(C6):

@@ -36,12 +36,14 @@ def bits(a):
 _case = {}
 
 
-def case():
-    """B = 4 lists of 600 pairs between 600 source rows (ld 4) and 650 target rows (ld 3), host arrays made once, read-only.
+def case(N=N, M=M, B=B):
+    """B = 4 lists of 600 pairs between 600 source rows (ld 4) and 650 target rows (ld 3), host arrays made once, read-only (other
+    sizes: the same construction, B >= 4).
     Clouds 0, 1, 3: pairs 0, 2, 4, ... are true under a planted transform (the target row is float32(R p + t)), the odd ones random.
     Cloud 1's source rows lie in ONE PLANE.  Cloud 2: every pair random (all outliers).  Cloud 3 also holds a NaN source row, an inf
     target row, a target row that forty pairs share, and two pairs whose index is out of range."""
-    if not _case:
+    key = (N, M, B)
+    if key not in _case:
         rng = np.random.default_rng(42)
         src = np.zeros((B, N, 4), np.float32)
         src[..., :3] = rng.uniform(-2, 2, (B, N, 3))
@@ -67,20 +69,55 @@ def case():
         pt[3, 7], ps[3, 9] = M, -1
         for a in (src, tgt, ps, pt):
             a.setflags(write=False)
-        _case.update(src=src, tgt=tgt, ps=ps.astype(np.int64), pt=pt.astype(np.int64), truth=np.stack(truth))
-    return _case
+        _case[key] = dict(src=src, tgt=tgt, ps=ps.astype(np.int64), pt=pt.astype(np.int64), truth=np.stack(truth))
+    return _case[key]
+
+
+def sized_case(N, M=5000, B=3):
+    """B = 3 lists of N pairs between N source rows (ld 4) and 5 000 target rows (ld 3), made once, read-only.  Pairs 0, 4, 8, ... are
+    true under a planted transform and have a target row of their own; the others are random.  The last cloud holds a NaN source row,
+    an inf target row and two pairs whose index is out of range -- none of them on a true pair."""
+    key = ("sized", N, M, B)
+    if key not in _case:
+        rng = np.random.default_rng(N)
+        true = np.arange(0, N, 4)
+        assert len(true) < M
+        src = np.zeros((B, N, 4), np.float32)
+        src[..., :3] = rng.uniform(-2, 2, (B, N, 3))
+        src[..., 3] = rng.random((B, N))
+        tgt = rng.uniform(-3, 3, (B, M, 3)).astype(np.float32)
+        ps = np.stack([rng.permutation(N) for _ in range(B)])
+        pt = rng.integers(0, M, (B, N))
+        truth = []
+        for b in range(B):
+            R, t = C.rotation(rng.normal(size=3), rng.uniform(20, 170)), rng.normal(size=3)
+            truth.append(np.concatenate([R, t[:, None]], 1).reshape(12))
+            rows = rng.permutation(M)
+            pt[b, true] = rows[:len(true)]
+            tgt[b, rows[:len(true)]] = (src[b, ps[b, true], :3].astype(np.float64) @ R.T + t).astype(np.float32)
+            if b == B - 1:
+                pt[b, 21] = rows[-1]                                 # (a row that no true pair names)
+                tgt[b, rows[-1], 2] = np.inf
+        src[B - 1, ps[B - 1, 10], 1] = np.nan
+        pt[B - 1, 7], ps[B - 1, 9] = M, -1
+        for a in (src, tgt, ps, pt):
+            a.setflags(write=False)
+        _case[key] = dict(src=src, tgt=tgt, ps=ps.astype(np.int64), pt=pt.astype(np.int64), truth=np.stack(truth))
+    return _case[key]
 
 
 class Run:
     """The case on the device with every output prefilled, and the two entry points as methods that return the code."""
 
-    def __init__(self, dev, H, count=None, edge_ratio=0.9, seed=0, threshold=THR):
-        c = case()
+    def __init__(self, dev, H, count=None, edge_ratio=0.9, seed=0, threshold=THR, c=None, fill=0xA5):
+        c = case() if c is None else c
         lib = _lib.load()
-        self.H, self.count_np, self.edge_ratio, self.seed, self.threshold = H, count, edge_ratio, seed, threshold
+        self.c, self.H, self.count_np, self.edge_ratio, self.seed, self.threshold = c, H, count, edge_ratio, seed, threshold
+        (self.B, self.N), self.M = c["ps"].shape, c["tgt"].shape[1]
+        B, N = self.B, self.N
         self.src, self.tgt, self.ps, self.pt = (cu(c[k], dev) for k in ("src", "tgt", "ps", "pt"))
         self.count = None if count is None else cu(np.int64(count), dev)
-        self.work = torch.full((lib.pn2_corr_workspace_bytes(B, N, H),), 0xA5, device=dev, dtype=torch.uint8)           # (it may hold anything)
+        self.work = torch.full((lib.pn2_corr_workspace_bytes(B, N, H),), fill, device=dev, dtype=torch.uint8)           # (it may hold anything)
         f = lambda shape, v, dt: torch.full(shape, v, device=dev, dtype=dt)
         self.out = dict(T=f((B, 12), F64_FILL, torch.float64), hyp=f((B, H, 12), F64_FILL, torch.float64), hyp_count=f((B, H), I32_FILL, torch.int32),
                         best_h=f((B,), I32_FILL, torch.int32), best_count=f((B,), I64_FILL, torch.int64), status=f((B,), I32_FILL, torch.int32),
@@ -89,7 +126,7 @@ class Run:
 
     def clouds(self):
         p = _lib.ptr
-        return (p(self.src), 4, p(self.tgt), 3, B, N, M, p(self.ps), p(self.pt), p(self.count))
+        return (p(self.src), 4, p(self.tgt), 3, self.B, self.N, self.M, p(self.ps), p(self.pt), p(self.count))
 
     def ransac(self):
         p, o = _lib.ptr, self.out
@@ -106,10 +143,10 @@ class Run:
         return {k: v.cpu().numpy() for k, v in self.out.items()}
 
     def counts(self):
-        return np.full(B, N, np.int64) if self.count_np is None else np.clip(np.int64(self.count_np), 0, N)
+        return np.full(self.B, self.N, np.int64) if self.count_np is None else np.clip(np.int64(self.count_np), 0, self.N)
 
     def reference(self):
-        c = case()
+        c = self.c
         return C.ransac(c["src"], c["tgt"], c["ps"], c["pt"], self.threshold, self.H, self.seed, self.edge_ratio, self.count_np)
 
 
@@ -150,9 +187,9 @@ def test_ransac_equals_the_reference(dev, H, edge_ratio):
 
 
 def check_refit(r, got, T_in, status_in):
-    c = case()
+    c = r.c
     ns = r.counts()
-    for b in range(B):
+    for b in range(r.B):
         if status_in[b] & C.NONE:
             assert (got["sums"][b] == F64_FILL).all() and got["rmse"][b] == F64_FILL and got["inliers"][b] == I64_FILL
             assert np.array_equal(bits(got["T"][b]), bits(T_in[b]))
@@ -201,6 +238,58 @@ def test_refit_rounds(dev):
         assert all(np.array_equal(bits(v), bits(last[k])) for k, v in r.host().items())          # two runs, the same bytes
         if count is not None:
             assert got["status"][2] & C.NONE
+    print("worst sums %.3f of the bound, worst solve %.3f of the tolerance" % (worst["sums"], worst["solve"]))
+
+
+# Past one tile: 2 refit tiles (1 025 pairs), 9 and 17 (the finish kernel's thread (k, c) adds word k of tiles c, c + 8, c + 16, ...), with
+# B = 3 so that ``partial``'s pitch is exercised with more than one tile.  Counts: cloud 1 ends exactly on a tile boundary with whole
+# tiles of the launch beyond it, cloud 2 ends inside a tile.  The sampler's seeds are chosen on the reference alone so that an
+# all-inlier triple is among the 257 hypotheses of every cloud (a quarter of the pairs is true: one triple in 64).
+SEAM_CASES = {1025: ((1025, 1024, 600), 0), 8193: ((8193, 8192, 5000), 0), 16385: ((16385, 8192, 9000), 0)}        # N: counts, seed
+SEAM_H = 257
+
+
+def true_pairs(counts):
+    return (np.int64(counts) + 3) // 4                               # pairs 0, 4, 8, ... below each count
+
+
+def run_seam(dev, N):
+    """RANSAC, two refit rounds and a closing evaluation of ``sized_case(N)`` on a workspace of 0xFF bytes, every stage checked
+    -> the outputs after each stage."""
+    counts, seed = SEAM_CASES[N]
+    r = Run(dev, SEAM_H, list(counts), seed=seed, c=sized_case(N), fill=0xFF)
+    assert r.ransac() == 0
+    got = r.host()
+    ref = r.reference()
+    assert np.array_equal(ref["best_count"], true_pairs(counts)) and (ref["status"] == 0).all()       # (the input's condition)
+    assert ref["err"] == C.ERR_PAIR | C.ERR_NONFINITE
+    check_ransac(got, ref)
+    stages = [got]
+    for _ in range(2):
+        T_in, status_in = got["T"].copy(), got["status"].copy()
+        assert r.refit() == 0
+        got = r.host()
+        check_refit(r, got, T_in, status_in)
+        stages.append(got)
+    assert (got["status"] == 0).all() and np.array_equal(got["inliers"], true_pairs(counts))
+    assert np.abs(got["T"] - r.c["truth"]).max() <= 1e-5            # the refitted transform is the planted one
+    T_in = got["T"].copy()
+    assert r.refit(_lib.CORR_EVAL_ONLY) == 0
+    last = r.host()
+    assert np.array_equal(bits(last["T"]), bits(T_in)) and np.array_equal(last["status"], got["status"])
+    for b in range(r.B):
+        ev = C.refit(r.c["src"][b], r.c["tgt"][b], r.c["ps"][b], r.c["pt"][b], int(counts[b]), T_in[b], r.threshold)
+        assert last["inliers"][b] == last["sums"][b, 0] == ev["count"]
+        assert (np.abs(last["sums"][b] - ev["sums"]) <= ev["count"] * 2.0 ** -52 * ev["abs_sums"]).all()
+        assert abs(last["rmse"][b] - C.rmse_of(last["sums"][b])) <= 2.0 ** -50 * C.rmse_of(last["sums"][b])
+    return stages + [last]
+
+
+@pytest.mark.parametrize("N", sorted(SEAM_CASES))
+def test_ransac_and_refit_past_one_tile(dev, N):
+    first, second = run_seam(dev, N), run_seam(dev, N)
+    for a, b in zip(first, second):
+        assert all(np.array_equal(bits(a[k]), bits(b[k])) for k in a)          # two runs, the same bytes
     print("worst sums %.3f of the bound, worst solve %.3f of the tolerance" % (worst["sums"], worst["solve"]))
 
 

@@ -25,7 +25,8 @@ def triple(v):
     return (ctypes.c_double * 3)(*np.broadcast_to(np.asarray(v, np.float64), (3,)))
 
 
-def grid_search(dev, cand, query, K, max_d2, origin=0.0, cell=None, n_query=None, n_cand=None, flags=0, want=("dist", "count", "err")):
+def grid_search(dev, cand, query, K, max_d2, origin=0.0, cell=None, n_query=None, n_cand=None, flags=0, want=("dist", "count", "err"),
+                fill=0xA5):
     """pn2_grid_build then pn2_grid_knn at the C ABI on numpy inputs -> dict of numpy outputs (idx, dist, count as the device
     left them, prefilled with the patterns above) and the two err words."""
     lib = _lib.load()
@@ -38,7 +39,7 @@ def grid_search(dev, cand, query, K, max_d2, origin=0.0, cell=None, n_query=None
     dq = None if query is None else cu(np.asarray(query, np.float32), dev)
     nq = None if n_query is None else cu(np.asarray(n_query, np.int64), dev)
     nc = None if n_cand is None else cu(np.asarray(n_cand, np.int64), dev)
-    ws = torch.full((lib.pn2_grid_workspace_bytes(B, M),), 0xA5, device=dev, dtype=torch.uint8)          # (it may hold anything)
+    ws = torch.full((lib.pn2_grid_workspace_bytes(B, M),), fill, device=dev, dtype=torch.uint8)          # (it may hold anything)
     idx = torch.full((B, N, K), IDX_FILL, device=dev, dtype=torch.int64)
     dist = torch.full((B, N, K), DIST_FILL, device=dev, dtype=torch.float32) if "dist" in want else None
     count = torch.full((B, N), COUNT_FILL, device=dev, dtype=torch.int32) if "count" in want else None
@@ -218,6 +219,61 @@ def test_self_search_both_visit_orders_and_two_runs_are_byte_identical(dev):
         for k in ("idx", "dist", "count"):
             assert np.array_equal(got[k].view(np.uint8), runs[0][k].view(np.uint8))
     assert (runs[0]["idx"][0, 17] == M).all() and runs[0]["count"][0, 17] == 0
+
+
+# pn2_grid_build scans the populations of the table's tiles (1 024 slots each; the table has the power of two at or above 2 M slots) 64
+# at a time with a carry.  The largest M elsewhere in the suite gives 8 tiles.  Here: 16 and 64 tiles (one step), 128 (two steps: the
+# carry is used) and 256 (four steps: a carry that is assigned and not added to would show); tests/test_tile_seams_cpu.py restates the
+# capacity rule and the tile counts.  The workspace holds 0xFF bytes: a slot, a start or a record that is read and was not written
+# is -1 or NaN.
+DISC_SIZES = [(257, 8192), (257, 32768), (257, 32769), (129, 65537)]             # (N, M)
+DISC_RADIUS = 0.3
+_disc_cache = {}
+
+
+def disc_case(N, M):
+    """(query, cand, n_cand, max_d2, the reference at K = 32) on R.disc_cloud: B = 2, ld = 4, the queries N of each cloud's candidates
+    moved by 0.01, the second cloud indexing two thirds of its rows.  Computed once, shared, never written to."""
+    if (N, M) not in _disc_cache:
+        rng = np.random.default_rng(M)
+        cand = R.disc_cloud(rng, 2, M)
+        query = np.stack([cand[b, rng.choice(M, N, replace=False)] for b in range(2)]) + np.float32(0.01)
+        n_cand = np.int64([M, M - M // 3])
+        m = np.float32(DISC_RADIUS ** 2)
+        ref = R.grid_knn(query, cand, 32, m, 0.0, R.default_cell(m), n_cand=n_cand)
+        for v in (query, cand, n_cand) + tuple(v for v in ref.values() if isinstance(v, np.ndarray)):
+            v.setflags(write=False)
+        _disc_cache[(N, M)] = (query, cand, n_cand, m, ref)
+    return _disc_cache[(N, M)]
+
+
+@pytest.mark.parametrize("N,M", DISC_SIZES)
+def test_disc_clouds_over_16_to_256_slot_tiles(dev, N, M):
+    query, cand, n_cand, m, ref = disc_case(N, M)
+    assert ref["err_build"] == 0 and (ref["count"][0] >= 1).all() and ref["count"].max() > 2          # (the input: no query is alone)
+    for K in (1, 8, 32):
+        assert_equals_reference(grid_search(dev, cand, query, K, m, n_cand=n_cand, fill=0xFF), ref, K)
+
+
+def test_self_search_over_128_slot_tiles_in_both_visit_orders(dev):
+    """M = 32 769: every row below the count is written and nothing beyond it, and every 127th row equals the reference of those rows
+    given as explicit queries."""
+    _, cand, n_cand, m, _ = disc_case(257, 32769)
+    M, K = cand.shape[1], 8
+    rows = np.arange(0, M, 127)
+    ref = R.grid_knn(cand[:, rows], cand, K, m, 0.0, R.default_cell(m), n_cand=n_cand)
+    for flags in (0, _lib.GRID_VISIT_SORTED):
+        got = grid_search(dev, cand, None, K, m, n_cand=n_cand, flags=flags, fill=0xFF)
+        assert got["err_build"] == 0 and got["err_query"] == 0
+        for b in range(2):
+            n = int(n_cand[b])
+            assert (got["idx"][b, :n] != IDX_FILL).all() and (got["dist"][b, :n] != np.float32(DIST_FILL)).all() and (got["count"][b, :n] != COUNT_FILL).all()
+            assert (got["idx"][b, n:] == IDX_FILL).all() and (got["dist"][b, n:] == np.float32(DIST_FILL)).all() and (got["count"][b, n:] == COUNT_FILL).all()
+            below = rows < n
+            assert np.array_equal(got["idx"][b, rows[below]], ref["idx"][b, below])
+            assert np.array_equal(got["dist"][b, rows[below]].view(np.uint32), ref["dist"][b, below].view(np.uint32))
+            assert np.array_equal(got["count"][b, rows[below]], ref["count"][b, below])
+            assert (got["idx"][b, rows[below], 0] == rows[below]).all()            # a row's nearest neighbour is the row itself
 
 
 def test_device_counts_leave_the_rows_beyond_untouched(dev):

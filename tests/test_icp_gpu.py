@@ -29,7 +29,7 @@ def triple(v):
 class Pair:
     """Target clouds on the device with their grid built (pn2_grid_build at the C ABI), and the source clouds."""
 
-    def __init__(self, dev, src, tgt, normals, max_d2, n_src=None):
+    def __init__(self, dev, src, tgt, normals, max_d2, n_src=None, fill=0xA5):
         lib = _lib.load()
         self.dev, self.src_np, self.tgt_np, self.nrm_np, self.max_d2, self.n_src_np = dev, src, tgt, normals, np.float32(max_d2), n_src
         self.B, self.N, self.lds = src.shape
@@ -39,8 +39,8 @@ class Pair:
         self.src, self.tgt = cu(src, dev), cu(tgt, dev)
         self.nrm = None if normals is None else cu(normals, dev)
         self.n_src = None if n_src is None else cu(np.asarray(n_src, np.int64), dev)
-        self.grid = torch.full((lib.pn2_grid_workspace_bytes(self.B, self.M),), 0xA5, device=dev, dtype=torch.uint8)
-        self.work = torch.full((lib.pn2_icp_workspace_bytes(self.B, self.N),), 0xA5, device=dev, dtype=torch.uint8)      # (it may hold anything)
+        self.grid = torch.full((lib.pn2_grid_workspace_bytes(self.B, self.M),), fill, device=dev, dtype=torch.uint8)
+        self.work = torch.full((lib.pn2_icp_workspace_bytes(self.B, self.N),), fill, device=dev, dtype=torch.uint8)      # (it may hold anything)
         _lib.check(lib.pn2_grid_build(_lib.ptr(self.tgt), self.ldt, self.B, self.M, None, ctypes.addressof(self.o), ctypes.addressof(self.c),
                                       None, _lib.ptr(self.grid), _lib.stream()), "pn2_grid_build")
 
@@ -88,13 +88,14 @@ def perturbed_planted():
 _cases = {}
 
 
-def lattice_case(N, ld):
-    """B = 3 lattice clouds (ties exist), M = 1000 targets, radius 0.15 (a little above one lattice step of 1/8, so some rows have
+def lattice_case(N, ld, M=1000, seed=None):
+    """B = 3 lattice clouds (ties exist), M targets, drawn from ``seed`` (100 N + ld unless given), radius 0.15 (a little above one lattice step of 1/8, so some rows have
     nobody in the ball), cloud 0 from the identity, cloud 1 from the perturbed planted transform with one row fewer, cloud 2 with
     count 0.  Planted: source rows far from every target, a NaN source row, zero and NaN normals.  Host arrays, read-only, once."""
-    if (N, ld) not in _cases:
-        rng = np.random.default_rng(100 * N + ld)
-        B, M = 3, 1000
+    key = (N, ld, M, seed)
+    if key not in _cases:
+        rng = np.random.default_rng(100 * N + ld if seed is None else seed)
+        B = 3
         src, tgt = np.zeros((B, N, ld), np.float32), np.zeros((B, M, ld), np.float32)
         src[..., :3], tgt[..., :3] = lattice(rng, B, N), lattice(rng, B, M)
         src[..., 3:], tgt[..., 3:] = rng.random((B, N, ld - 3)), rng.random((B, M, ld - 3))          # (not coordinates)
@@ -112,8 +113,8 @@ def lattice_case(N, ld):
         T = np.stack([IDENTITY, perturbed_planted(), IDENTITY])
         for a in (src, tgt, normals, n_src, T):
             a.setflags(write=False)
-        _cases[(N, ld)] = (src, tgt, normals, n_src, T)
-    return _cases[(N, ld)]
+        _cases[key] = (src, tgt, normals, n_src, T)
+    return _cases[key]
 
 
 def assert_step_matches(got, ref, T_in, metric):
@@ -163,6 +164,59 @@ def test_single_steps_equal_the_reference(dev, N, ld):
             matched = ref["corr"][0][ref["corr"][0] < 1000]
             assert (normals[0, matched, 0] == 0).any() and np.isnan(normals[0, matched, 2]).any()     # rows that name j and take no part
             assert got["count"][0] < len(matched)
+
+
+# Past the first trip of the finish kernel's loop over tiles (thread (k, c) adds word k of tiles c, c + 8, c + 16, ...): 8 tiles (one per
+# chunk), 9 (chunk 0 takes two trips, the last tile holds one row) and 17 (three trips).  The device-side counts: cloud 1 ends exactly
+# on a tile boundary with whole tiles of the launch beyond it, cloud 2 ends inside a tile.  The same counts serve the plane and the
+# correspondence tests; tests/test_tile_seams_cpu.py shows on the reference that a tile lost from these cases cannot pass.
+SEAM_COUNTS = {8192: (8192, 4096, 5000), 8193: (8193, 8192, 5000), 16385: (16385, 8192, 9000)}
+SEAM_M = 300                                                       # (the reference costs N x M)
+SEAM_SEEDS = {8192: 1, 8193: 1, 16385: 4}                         # chosen on the reference: see ``seam_case``
+
+
+def seam_case(N):
+    """``lattice_case(N, 3)`` with 300 targets, the counts above, and a seed for which (on the reference alone) no cloud is singular
+    and the LAST row of cloud 0 -- at N = 1024 t + 1 a tile of its own -- takes part under both metrics."""
+    src, tgt, normals, _, T = lattice_case(N, 3, SEAM_M, SEAM_SEEDS[N])
+    return src, tgt, normals, np.int64(SEAM_COUNTS[N]), T
+
+
+@pytest.mark.parametrize("N", sorted(SEAM_COUNTS))
+def test_single_steps_past_the_first_trip_over_the_tiles(dev, N):
+    """The workspace holds 0xFF bytes (NaN as a double): a partial that is read and was not written poisons every sum."""
+    src, tgt, normals, n_src, T = seam_case(N)
+    pair = Pair(dev, src, tgt, normals, 0.15 ** 2, n_src, fill=0xFF)
+    for metric in (I.PLANE, I.POINT):
+        st = pair.state(T)
+        assert pair.step(st, metric) == 0
+        got, ref = host(st), pair.reference(T, metric)
+        assert (ref["status"] == 0).all() and (ref["count"] > n_src // 4).all() and ref["corr"][0, N - 1] < SEAM_M      # (the input's conditions)
+        assert_step_matches(got, ref, T, metric)
+        for b in range(3):
+            assert (got["corr"][b, :n_src[b]] != I64_FILL).all() and (got["corr"][b, n_src[b]:] == I64_FILL).all()
+
+
+def test_k1_walk_over_a_table_of_128_tiles(dev):
+    """257 source rows against 32 769 targets on a disc: the target's slot table has 131 072 slots, 128 tiles of 1 024, so the scan of
+    the tile populations carries across 64 tiles once, and the K = 1 walk reads cell starts that the carry produced."""
+    rng = np.random.default_rng(32769)
+    B, N, M = 2, 257, 32769
+    tgt = R.disc_cloud(rng, B, M)
+    src = np.stack([tgt[b, rng.choice(M, N, replace=False), :3] for b in range(B)]) + np.float32(0.01)
+    v = rng.standard_normal((B, M, 3))
+    normals = (v / np.linalg.norm(v, axis=-1, keepdims=True)).astype(np.float32)
+    D = I.rotation((3, -1, 2), 0.002)                              # (0.024 at the rim of the disc: well inside the ball of 0.3)
+    T = np.stack([IDENTITY, np.concatenate([D, np.array([[0.004], [0.003], [-0.002]])], 1).reshape(12)])
+    n_src = np.int64([N, 200])
+    pair = Pair(dev, src, tgt, normals, 0.3 ** 2, n_src, fill=0xFF)
+    for metric in (I.PLANE, I.POINT):
+        st = pair.state(T)
+        assert pair.step(st, metric) == 0
+        got, ref = host(st), pair.reference(T, metric)
+        assert (ref["status"] == 0).all() and ref["err"] == 0 and np.array_equal(ref["count"], n_src)       # every row finds somebody
+        assert_step_matches(got, ref, T, metric)
+        assert (got["corr"][1, 200:] == I64_FILL).all()
 
 
 def test_frozen_eval_only_and_refusals(dev):

@@ -41,7 +41,7 @@ def bits(a):
 class Cloud:
     """Clouds on the device with every output prefilled, and the three entry points as methods that return the code."""
 
-    def __init__(self, dev, pts, H, n_points=None, assign=None, axis=(0, 0, 1), cos_max=0.0, threshold=THR, seed=0):
+    def __init__(self, dev, pts, H, n_points=None, assign=None, axis=(0, 0, 1), cos_max=0.0, threshold=THR, seed=0, fill=0xA5):
         lib = _lib.load()
         self.dev, self.pts_np, self.H, self.n_np, self.axis_np, self.cos_max, self.threshold, self.seed = dev, pts, H, n_points, axis, cos_max, threshold, seed
         self.B, self.N, self.ld = pts.shape
@@ -49,7 +49,7 @@ class Cloud:
         self.pts = cu(pts, dev)
         self.n_points = None if n_points is None else cu(np.asarray(n_points, np.int64), dev)
         self.assign = None if assign is None else cu(assign, dev)
-        self.work = torch.full((lib.pn2_plane_workspace_bytes(self.B, self.N, H),), 0xA5, device=dev, dtype=torch.uint8)       # (it may hold anything)
+        self.work = torch.full((lib.pn2_plane_workspace_bytes(self.B, self.N, H),), fill, device=dev, dtype=torch.uint8)       # (it may hold anything)
         B, N = self.B, self.N
         f = lambda shape, v, dt: torch.full(shape, v, device=dev, dtype=dt)
         self.out = dict(plane=f((B, 4), F64_FILL, torch.float64), hyp_count=f((B, H), I32_FILL, torch.int32), best_h=f((B,), I32_FILL, torch.int32),
@@ -95,12 +95,14 @@ class Cloud:
 _cases = {}
 
 
-def lattice_case(N, ld):
+def lattice_case(N, ld, seed=None):
     """B = 3 lattice clouds (coordinates multiples of 1/8: exactly representable, so ties are real) with the device-side counts
-    (N, 2, 0).  About half the rows lie on the lattice plane z = -1/4; every seventh row repeats row 0 (degenerate triples); from
-    N = 63 on a NaN row, an inf row and rows that take no part (assign >= 0).  Host arrays, read-only, made once."""
-    if (N, ld) not in _cases:
-        rng = np.random.default_rng(1000 * N + ld)
+    (N, 2, 0), drawn from ``seed`` (1000 N + ld unless given).  About half the rows lie on the lattice plane z = -1/4; every seventh
+    row repeats row 0 (degenerate triples); from N = 63 on a NaN row, an inf row and rows that take no part (assign >= 0).  Host
+    arrays, read-only, made once."""
+    key = (N, ld, seed)
+    if key not in _cases:
+        rng = np.random.default_rng(1000 * N + ld if seed is None else seed)
         B = 3
         pts = np.zeros((B, N, ld), np.float32)
         pts[..., :3] = rng.integers(-8, 8, (B, N, 3)) / 8
@@ -114,8 +116,8 @@ def lattice_case(N, ld):
             assign[0, 5] = assign[0, 9] = -1                        # the rows that are not finite take part: the error bit
             assign.setflags(write=False)
         pts.setflags(write=False)
-        _cases[(N, ld)] = (pts, np.int64([N, 2, 0]), assign)
-    return _cases[(N, ld)]
+        _cases[key] = (pts, np.int64([N, 2, 0]), assign)
+    return _cases[key]
 
 
 def check_refit_round(c, got, plane_in, status_in):
@@ -228,6 +230,32 @@ def test_pipeline_equals_the_reference(dev, N, ld):
             assert got["status"][0] == 0 and (ref["hyp_count"][0] == -1).any()        # the repeated rows made degenerate triples
         if N >= 1023 and H >= 256:                                  # (0.09 of the hypotheses lie in the planted plane: 256 of them do not all miss it)
             assert np.array_equal(got["plane"][0], [0, 0, 1.0, 0.25]) and got["count"][0] > N // 3         # the planted plane, exactly
+    print("worst ratios to the bounds so far: %r" % worst)
+
+
+# Past the first trip of the two loops over row tiles: the finish kernel's (thread (k, c) adds word k of tiles c, c + 8, c + 16, ...) at
+# 9 and 17 tiles, the write kernel's (k += 256 over the tile counts) at 257 tiles, N = 262 145 being the smallest such N.  Counts: a
+# cloud that ends exactly on a tile boundary with whole tiles of the launch beyond it, and (9, 17 tiles) one that ends inside a tile.
+# Both seeds are chosen on the reference alone: the sampler's so that plane_ref.fit_plane gives status 0 for every cloud, the cloud's so
+# that the LAST row of cloud 0 -- a tile of its own at N = 1024 t + 1 -- is an inlier, else that tile's partial and count would be zero
+# and the last trip of either loop invisible (tests/test_tile_seams_cpu.py asserts it).
+SEAM_CASES = {8193: ((8193, 8192, 5000), 65, 2, 0), 16385: ((16385, 8192, 9000), 65, 4, 0), 262145: ((262145, 262144), 64, 5, 0)}  # N: counts, H, seeds
+
+
+def seam_case(N):
+    """-> (pts, counts, assign, H, seed): ``lattice_case(N, 3)``'s clouds (the first two at 262 145 rows) with the counts above."""
+    counts, H, cloud_seed, seed = SEAM_CASES[N]
+    pts, _, assign = lattice_case(N, 3, cloud_seed)
+    return pts[:len(counts)], np.int64(counts), assign[:len(counts)], H, seed
+
+
+@pytest.mark.parametrize("N", sorted(SEAM_CASES))
+def test_pipeline_past_the_first_trip_over_the_tiles(dev, N):
+    """The workspace holds 0xFF bytes (NaN as a double, -1 as an integer): a word that is read and was not written poisons the result."""
+    pts, counts, assign, H, seed = seam_case(N)
+    c = Cloud(dev, pts, H, counts, assign, seed=seed, fill=0xFF)
+    got, ref = run_pipeline(c)
+    assert (ref["status"] == 0).all() and (ref["count"] > counts // 4).all() and ref["inlier"][0, N - 1]       # (the input's conditions)
     print("worst ratios to the bounds so far: %r" % worst)
 
 

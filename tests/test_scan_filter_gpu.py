@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 
 T = _lib.SCAN_TILE
 POISON_F, POISON_I = 0x5A5A5A5A, -777
-SIZES = [1, 63, 64, 65, T - 1, T, T + 1, 3 * T + 17, 131071]
+SIZES = [1, 63, 64, 65, T - 1, T, T + 1, 3 * T + 17, 131071, 128 * T + 1]     # (129 tiles: the scan's carry takes a third step)
 
 
 def lmap_g9():

@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 
 T = _lib.VOXEL_TILE
 POISON_F, POISON_I = 0x5A5A5A5A, -777
-SIZES = [1, 63, 64, 65, T - 1, T, T + 1, 3 * T + 17, 131071]
+SIZES = [1, 63, 64, 65, T - 1, T, T + 1, 3 * T + 17, 131071, 128 * T + 1]     # (129 tiles: the scan's carry takes a third step)
 ALL_OUTPUTS = ("points", "labels", "index", "inverse", "n_points")
 
 
