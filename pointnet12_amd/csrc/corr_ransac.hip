@@ -9,32 +9,28 @@
 //                           ONE HYPOTHESIS PER LANE with its twelve doubles in registers; the tile is staged once through LDS as six
 //                           doubles a pair (p_x = NaN for a pair that is out of range or not finite: its d2 is NaN and fails the
 //                           compare) and broadcast-read; an integer count per lane, no cross-lane reduction.
-//   corr_select_kernel      plane_select_kernel's 64-bit key: the largest count, the lowest h among equals.
-//   corr_accumulate_kernel  icp.hip's tile scheme on seventeen words: one pair per lane, kRefitRows pairs one after another, a
-//   corr_finish_kernel      butterfly over the wave, the waves in wave order, one partial per tile; then thread (k, c) adds word k
-//                           of the tiles c, c + 8, ..., one lane adds the chunks in order and solves by Horn's quaternion method
-//                           (sym_eig4.h: cyclic Jacobi on the symmetric 4 x 4, a fixed number of sweeps).
-//   The order of every floating-point sum is a function of (B, N) alone.  No float atomics (the only atomics are the ORs into err),
+//   corr_select_kernel      the largest count, the lowest h among equals (ransac_select.h); the best hypothesis is T, the identity
+//                           without one.
+//   corr_accumulate_kernel  the tiled sum of tile_sum.h on seventeen words, a pair where it says row: one partial per tile; then one
+//   corr_finish_kernel      lane holds the totals and solves by Horn's quaternion method (sym_eig4.h: cyclic Jacobi on the
+//                           symmetric 4 x 4, a fixed number of sweeps).
+//   The order of every floating-point sum is a function of (B, N) alone (tile_sum.h).  No float atomics (the only atomics are the ORs into err),
 //   no thread waits for another thread's write, nothing is allocated, plain launches.
 //
 // This file is built with -ffp-contract=off: every term is the separately rounded fp64 statement of the header.
 #include <cmath>
 #include "pn2_common.h"
 #include "ransac_sample.h"
+#include "ransac_select.h"
+#include "rigid.h"
 #include "sym_eig4.h"
+#include "tile_sum.h"
 
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kSumThreads;                               // every kernel here
 constexpr int kWaves = kThreads / PN2_WAVE;
-constexpr int kScoreTile = 512;                                     // pairs per scoring workgroup (24 KiB of LDS)
-constexpr int kRefitRows = 4;                                       // pairs per lane of the accumulate kernel
-constexpr int kRowTile = kThreads * kRefitRows;                     // pairs per workgroup there
 constexpr int kSums = PN2_CORR_SUMS;                                // count, sum p (3), sum q (3), sum p q^T (9, p major), sum d2
-constexpr int kChunks = 8;                                          // of the finish kernel
-static_assert(kSums <= 32, "the finish kernel gives a word to each of 32 threads");
-
-__device__ __forceinline__ int corr_count(const int64_t *n, int b, int full) { return n == nullptr ? full : pn2_clamped_rows(n, b, full); }
 
 __device__ __forceinline__ double corr_len(const double (&a)[3], const double (&b)[3]) {
     const double x = b[0] - a[0], y = b[1] - a[1], z = b[2] - a[2];
@@ -75,11 +71,11 @@ __device__ __forceinline__ bool corr_load(const float *__restrict__ p, double (&
     return std::isfinite(a[0]) && std::isfinite(a[1]) && std::isfinite(a[2]);
 }
 
-// d2 of a pair under T = [R | t]: e = (R p + t) - q, the transform as registration.transform_points states it
+// d2 of a pair under T = [R | t]: e = (R p + t) - q
 __device__ __forceinline__ double corr_d2(const double (&T)[12], double px, double py, double pz, double qx, double qy, double qz) {
-    const double ex = (((T[0] * px + T[1] * py) + T[2] * pz) + T[3]) - qx;
-    const double ey = (((T[4] * px + T[5] * py) + T[6] * pz) + T[7]) - qy;
-    const double ez = (((T[8] * px + T[9] * py) + T[10] * pz) + T[11]) - qz;
+    const double ex = pn2_rigid_apply<0>(T, px, py, pz) - qx;
+    const double ey = pn2_rigid_apply<1>(T, px, py, pz) - qy;
+    const double ez = pn2_rigid_apply<2>(T, px, py, pz) - qz;
     return (ex * ex + ey * ey) + ez * ez;
 }
 
@@ -89,7 +85,7 @@ __global__ __launch_bounds__(kThreads) void corr_hypothesis_kernel(const float *
                                                                    double edge_ratio, double *__restrict__ hyp) {
     const int b = blockIdx.y, h = blockIdx.x * kThreads + threadIdx.x;
     if (h >= H) return;
-    const int n = corr_count(count, b, N);
+    const int n = pn2_rows_or_all(count, b, N);
     double T[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) T[k] = __builtin_nan("");
@@ -157,7 +153,7 @@ __global__ __launch_bounds__(kThreads) void corr_score_kernel(const float *__res
                                                               int tiles, int32_t *__restrict__ tile_count, int32_t *__restrict__ err) {
     __shared__ double s_p[3][kScoreTile], s_q[3][kScoreTile];
     const int b = blockIdx.z, tile = blockIdx.x, t = threadIdx.x;
-    const int n = corr_count(count, b, N);
+    const int n = pn2_rows_or_all(count, b, N);
     const int first = tile * kScoreTile;
     if (first >= n) return;                                         // (uniform over the workgroup; the select kernel does not read this tile)
     const int cnt = min(kScoreTile, n - first);
@@ -191,33 +187,14 @@ __global__ __launch_bounds__(kThreads) void corr_select_kernel(int N, const int6
                                                                int64_t *__restrict__ best_count, int32_t *__restrict__ status,
                                                                int32_t *__restrict__ err) {
     __shared__ unsigned long long s_key[kWaves];
-    const int b = blockIdx.x, t = threadIdx.x;
-    const int n = corr_count(count, b, N);
-    const int live = (int)(((int64_t)n + kScoreTile - 1) / kScoreTile);         // the tiles the scoring pass wrote
-    // key: (count + 1) in the high word, ~h in the low one: the largest count, the lowest h among equals; 0 = no valid hypothesis
-    unsigned long long key = 0;
-    for (int h = t; h < H; h += kThreads) {
-        const double r = hyp[((int64_t)b * H + h) * 12];
-        const bool valid = r == r;
-        int64_t c = 0;
-        for (int tile = 0; tile < live; ++tile) c += tile_count[((int64_t)b * tiles + tile) * H + h];
-        if (hyp_count != nullptr) hyp_count[(int64_t)b * H + h] = valid ? (int32_t)c : -1;
-        const unsigned long long k = ((unsigned long long)(c + 1) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)h);
-        if (valid && k > key) key = k;
-    }
-    key = pn2_wave_max_u64(key);
-    if ((t & (PN2_WAVE - 1)) == 0) s_key[t >> 6] = key;
-    __syncthreads();
-    if (t != 0) return;
-    for (int k = 1; k < kWaves; ++k) key = s_key[k] > key ? s_key[k] : key;
-    const bool any = key != 0;
-    const int h = any ? (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull)) : -1;
-    const int64_t c = any ? (int64_t)(key >> 32) - 1 : 0;
-    best_h[b] = h;
-    best_count[b] = c;
-    const bool none = !any || c < 3;
+    const int b = blockIdx.x;
+    RansacBest best;
+    if (!ransac_select(b, pn2_rows_or_all(count, b, N), H, hyp, 12, tiles, tile_count, hyp_count, s_key, best)) return;
+    best_h[b] = best.h;
+    best_count[b] = best.count;
+    const bool none = !best.any || best.count < 3;
 #pragma unroll
-    for (int k = 0; k < 12; ++k) T[(int64_t)b * 12 + k] = none ? ((k & 3) == (k >> 2) ? 1.0 : 0.0) : hyp[((int64_t)b * H + h) * 12 + k];
+    for (int k = 0; k < 12; ++k) T[(int64_t)b * 12 + k] = none ? ((k & 3) == (k >> 2) ? 1.0 : 0.0) : hyp[((int64_t)b * H + best.h) * 12 + k];
     status[b] = none ? PN2_CORR_NONE : 0;
     if (none && err != nullptr) atomicOr(err, PN2_CORR_ERR_NONE);
 }
@@ -226,20 +203,20 @@ __global__ __launch_bounds__(kThreads) void corr_accumulate_kernel(const float *
                                                                    int M, const int64_t *__restrict__ pair_src, const int64_t *__restrict__ pair_tgt,
                                                                    const int64_t *__restrict__ count, double thr2, const double *__restrict__ Tin,
                                                                    const int32_t *__restrict__ status, double *__restrict__ partial) {
-    __shared__ double s_wave[kWaves][kSums];
-    const int b = blockIdx.y, tile = blockIdx.x, t = threadIdx.x;
+    __shared__ double s_wave[kSumWaves][kSums];
+    const int b = blockIdx.y, tile = blockIdx.x;
     if ((status[b] & PN2_CORR_NONE) != 0) return;                   // (uniform over the workgroup)
-    const int n = corr_count(count, b, N);
+    const int n = pn2_rows_or_all(count, b, N);
     double acc[kSums];
 #pragma unroll
     for (int k = 0; k < kSums; ++k) acc[k] = 0.0;
-    if ((int64_t)tile * kRowTile < n) {
+    if ((int64_t)tile * kSumTile < n) {
         double T[12];
 #pragma unroll
         for (int k = 0; k < 12; ++k) T[k] = Tin[(int64_t)b * 12 + k];
 #pragma nounroll
-        for (int r = 0; r < kRefitRows; ++r) {
-            const int64_t i = (int64_t)tile * kRowTile + (int64_t)r * kThreads + t;
+        for (int r = 0; r < kSumRows; ++r) {
+            const int64_t i = pn2_tile_row(tile, r);
             if (i >= n) continue;
             const int64_t at = (int64_t)b * N + i;
             double p[3], q[3];
@@ -257,42 +234,19 @@ __global__ __launch_bounds__(kThreads) void corr_accumulate_kernel(const float *
             acc[16] = acc[16] + d2;
         }
     }
-    const int lane = t & (PN2_WAVE - 1), wave = t >> 6;
-#pragma unroll
-    for (int k = 0; k < kSums; ++k) {
-        const double v = pn2_wave_sum_f64(acc[k]);
-        if (lane == 0) s_wave[wave][k] = v;
-    }
-    __syncthreads();
-    if (t < kSums) {
-        double v = s_wave[0][t];
-        for (int k = 1; k < kWaves; ++k) v = v + s_wave[k][t];
-        partial[((int64_t)b * gridDim.x + tile) * kSums + t] = v;
-    }
+    pn2_tile_partial(acc, s_wave, partial + ((int64_t)b * gridDim.x + tile) * kSums);
 }
 
 __global__ __launch_bounds__(kThreads) void corr_finish_kernel(int tiles, int flags, const double *__restrict__ partial, double *__restrict__ T,
                                                                int64_t *__restrict__ inliers, double *__restrict__ rmse, double *__restrict__ sums,
                                                                int32_t *__restrict__ status) {
-    __shared__ double s_chunk[kChunks][32];
-    const int b = blockIdx.x, t = threadIdx.x;
+    __shared__ double s_chunk[kSumChunks][32];
+    const int b = blockIdx.x;
     if ((status[b] & PN2_CORR_NONE) != 0) return;
-    const int k = t & 31, c = t >> 5;
-    double v = 0.0;
-    if (k < kSums)
-        for (int tile = c; tile < tiles; tile += kChunks) v = v + partial[((int64_t)b * tiles + tile) * kSums + k];
-    s_chunk[c][k] = v;
-    __syncthreads();
-    if (t != 0) return;
     double S[kSums];
+    if (!pn2_tile_total(partial + (int64_t)b * tiles * kSums, tiles, s_chunk, S)) return;
 #pragma unroll
-    for (int q = 0; q < kSums; ++q) {
-        double s = s_chunk[0][q];
-#pragma unroll
-        for (int h = 1; h < kChunks; ++h) s = s + s_chunk[h][q];
-        S[q] = s;
-        sums[(int64_t)b * kSums + q] = s;
-    }
+    for (int q = 0; q < kSums; ++q) sums[(int64_t)b * kSums + q] = S[q];
     const double n = S[0];
     inliers[b] = (int64_t)n;
     rmse[b] = n > 0.0 ? sqrt(S[16] / n) : 0.0;
@@ -345,8 +299,6 @@ __global__ __launch_bounds__(kThreads) void corr_finish_kernel(int tiles, int fl
     for (int e = 0; e < 12; ++e) T[(int64_t)b * 12 + e] = R[e];
 }
 
-bool corr_shape_ok(int B, int64_t N) { return B >= 1 && B <= 65535 && N >= 1 && N <= 0x7FFFFF00; }
-
 struct CorrWork {
     double *partial, *hyp;          // [B,row tiles,17]; [B,H,12]
     int32_t *score;                 // [B,score tiles,H]
@@ -359,7 +311,7 @@ CorrWork corr_carve(int B, int64_t N, int H, void *base) {
     CorrWork w;
     int64_t at = 0;
     w.partial = reinterpret_cast<double *>(p + at);
-    at += pn2_round16((int64_t)B * pn2_cdiv(N, kRowTile) * kSums * (int64_t)sizeof(double));
+    at += pn2_round16((int64_t)B * pn2_cdiv(N, kSumTile) * kSums * (int64_t)sizeof(double));
     w.hyp = reinterpret_cast<double *>(p + at);
     at += pn2_round16((int64_t)B * H * 12 * (int64_t)sizeof(double));
     w.score = reinterpret_cast<int32_t *>(p + at);
@@ -370,7 +322,7 @@ CorrWork corr_carve(int B, int64_t N, int H, void *base) {
 
 bool corr_clouds_ok(const float *src, int lds, const float *tgt, int ldt, int B, int N, int M, const int64_t *pair_src, const int64_t *pair_tgt,
                     const int64_t *count, double threshold) {
-    return src && tgt && pair_src && pair_tgt && corr_shape_ok(B, N) && corr_shape_ok(B, M) && lds >= 3 && lds <= 16 && ldt >= 3 && ldt <= 16 &&
+    return src && tgt && pair_src && pair_tgt && pn2_cloud_shape_ok(B, N) && pn2_cloud_shape_ok(B, M) && lds >= 3 && lds <= 16 && ldt >= 3 && ldt <= 16 &&
            std::isfinite(threshold) && threshold >= 0.0 && pn2_aligned(src, 4) && pn2_aligned(tgt, 4) && pn2_aligned(pair_src, 8) &&
            pn2_aligned(pair_tgt, 8) && pn2_aligned(count, 8);
 }
@@ -380,7 +332,7 @@ bool corr_clouds_ok(const float *src, int lds, const float *tgt, int ldt, int B,
 extern "C" {
 
 int64_t pn2_corr_workspace_bytes(int B, int N, int H) {
-    if (!corr_shape_ok(B, N) || H < 1 || H > 65536) return PN2_EINVAL;
+    if (!pn2_cloud_shape_ok(B, N) || H < 1 || H > 65536) return PN2_EINVAL;
     return corr_carve(B, N, H, nullptr).bytes;
 }
 
@@ -412,7 +364,7 @@ int pn2_corr_refit(const float *src, int lds, const float *tgt, int ldt, int B, 
     PN2_CHECK_ARG(pn2_aligned(T, 8) && pn2_aligned(inliers, 8) && pn2_aligned(rmse, 8) && pn2_aligned(sums, 8) && pn2_aligned(status, 4) &&
                   pn2_aligned(workspace, 16));
     const CorrWork w = corr_carve(B, N, 1, workspace);
-    const int tiles = (int)pn2_cdiv(N, kRowTile);
+    const int tiles = (int)pn2_cdiv(N, kSumTile);
     const hipStream_t s = pn2_s(stream);
     hipLaunchKernelGGL(corr_accumulate_kernel, dim3((unsigned)tiles, (unsigned)B), dim3(kThreads), 0, s, src, lds, tgt, ldt, N, M, pair_src, pair_tgt,
                        count, threshold * threshold, T, status, w.partial);

@@ -26,8 +26,6 @@ constexpr int kSlices = 8;                                          // waves per
 constexpr int kThreads = kQueries * kSlices;
 constexpr int kTileFloats = 8192;                                   // 32 KiB of LDS: 128 rows at W = 64, 227 at W = 36
 
-__device__ __forceinline__ int match_count(const int64_t *n, int b, int full) { return n == nullptr ? full : pn2_clamped_rows(n, b, full); }
-
 template <int W>
 __global__ __launch_bounds__(kThreads) void feature_nn2_kernel(const float *__restrict__ query, int ldq, const float *__restrict__ cand, int ldc,
                                                                int N, int M, int D, const int64_t *__restrict__ n_query,
@@ -39,7 +37,7 @@ __global__ __launch_bounds__(kThreads) void feature_nn2_kernel(const float *__re
     __shared__ float s_d[kSlices][2][kQueries];
     __shared__ int s_j[kSlices][2][kQueries];
     const int b = blockIdx.y, t = threadIdx.x, lane = t & (PN2_WAVE - 1), slice = t / PN2_WAVE;
-    const int nq = match_count(n_query, b, N), mc = match_count(n_cand, b, M);
+    const int nq = pn2_rows_or_all(n_query, b, N), mc = pn2_rows_or_all(n_cand, b, M);
     if ((int64_t)blockIdx.x * kQueries >= nq) return;               // (uniform over the workgroup)
     const int i = blockIdx.x * kQueries + lane;
     const bool live = i < nq;
@@ -129,7 +127,7 @@ __global__ __launch_bounds__(kThreads) void feature_nn2_kernel(const float *__re
 
 __global__ __launch_bounds__(256) void match_rows_kernel(const int64_t *__restrict__ n_query, int B, int N, int64_t *__restrict__ rows) {
     const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b < B) rows[b] = match_count(n_query, b, N);
+    if (b < B) rows[b] = pn2_rows_or_all(n_query, b, N);
 }
 
 __global__ __launch_bounds__(kCompactThreads) void match_flag_kernel(const int64_t *__restrict__ idx, const float *__restrict__ dist,
@@ -168,8 +166,6 @@ __global__ __launch_bounds__(kCompactThreads) void match_write_kernel(const int6
     });
 }
 
-bool match_shape_ok(int B, int64_t N) { return B >= 1 && B <= 65535 && N >= 1 && N <= 0x7FFFFF00; }
-
 struct MatchWork {
     int64_t *rows;                  // [B]
     void *compact;
@@ -194,7 +190,7 @@ extern "C" {
 int pn2_feature_nn2(const float *query, int ldq, const float *cand, int ldc, int B, int N, int M, int D, const int64_t *n_query,
                     const int64_t *n_cand, int64_t *idx, float *dist, pn2_stream_t stream) {
     PN2_CHECK_ARG(query && cand && idx && dist);
-    PN2_CHECK_ARG(match_shape_ok(B, N) && match_shape_ok(B, M) && D >= 1 && D <= ldq && D <= ldc);
+    PN2_CHECK_ARG(pn2_cloud_shape_ok(B, N) && pn2_cloud_shape_ok(B, M) && D >= 1 && D <= ldq && D <= ldc);
     PN2_CHECK_ARG(pn2_aligned(query, 4) && pn2_aligned(cand, 4) && pn2_aligned(n_query, 8) && pn2_aligned(n_cand, 8) && pn2_aligned(idx, 8) &&
                   pn2_aligned(dist, 4));
     if (D > PN2_MATCH_MAX_D) return PN2_EUNSUPPORTED;
@@ -207,14 +203,14 @@ int pn2_feature_nn2(const float *query, int ldq, const float *cand, int ldc, int
 }
 
 int64_t pn2_match_pairs_workspace_bytes(int B, int N) {
-    if (!match_shape_ok(B, N)) return PN2_EINVAL;
+    if (!pn2_cloud_shape_ok(B, N)) return PN2_EINVAL;
     return match_carve(B, N, nullptr).bytes;
 }
 
 int pn2_match_pairs(const int64_t *idx, const float *dist, const int64_t *back, int B, int N, int M, float ratio2, const int64_t *n_query,
                     int64_t *pair_src, int64_t *pair_tgt, int64_t *count, void *workspace, pn2_stream_t stream) {
     PN2_CHECK_ARG(idx && dist && pair_src && pair_tgt && count && workspace);
-    PN2_CHECK_ARG(match_shape_ok(B, N) && match_shape_ok(B, M) && ratio2 >= 0.f);                  // (a NaN ratio2 fails the compare)
+    PN2_CHECK_ARG(pn2_cloud_shape_ok(B, N) && pn2_cloud_shape_ok(B, M) && ratio2 >= 0.f);                  // (a NaN ratio2 fails the compare)
     PN2_CHECK_ARG(pn2_aligned(idx, 8) && pn2_aligned(dist, 4) && pn2_aligned(back, 8) && pn2_aligned(n_query, 8) && pn2_aligned(pair_src, 8) &&
                   pn2_aligned(pair_tgt, 8) && pn2_aligned(count, 8) && pn2_aligned(workspace, 16));
     const MatchWork w = match_carve(B, N, workspace);

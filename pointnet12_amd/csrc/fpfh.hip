@@ -37,7 +37,7 @@ __global__ __launch_bounds__(FPFH_THREADS) void spfh_kernel(const float *__restr
     const int b = blockIdx.y;
     const int lane = threadIdx.x;
     const int i = blockIdx.x * FPFH_THREADS + lane;
-    const int n = n_points == nullptr ? M : pn2_clamped_rows(n_points, b, M);
+    const int n = pn2_rows_or_all(n_points, b, M);
     if (i >= n) return;                                           // (no barrier below)
     const size_t row = (size_t)b * M + i;
     const int64_t *ri = idx + row * K;
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(FPFH_THREADS) void fpfh_kernel(const float *__restr
                                                             int32_t *__restrict__ err) {
     const int b = blockIdx.y;
     const int i = blockIdx.x * FPFH_THREADS + threadIdx.x;
-    const int n = n_points == nullptr ? M : pn2_clamped_rows(n_points, b, M);
+    const int n = pn2_rows_or_all(n_points, b, M);
     if (i >= n) return;
     const size_t row = (size_t)b * M + i;
     const int64_t *ri = idx + row * K;

@@ -34,7 +34,7 @@ __global__ __launch_bounds__(kThreads) void grid_clear_kernel(const int64_t *__r
         reinterpret_cast<uint4 *>(w.table + (int64_t)b * w.cap)[i] = pn2_slot_empty(0u, 0u);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         Head h;
-        h.count = grid_count(n_cand, b, M);
+        h.count = pn2_rows_or_all(n_cand, b, M);
         h.indexed = h.tail = h.unused = 0;
         w.head[b] = h;
     }
@@ -44,7 +44,7 @@ __global__ __launch_bounds__(kThreads) void grid_count_kernel(const float *__res
                                                               Grid grid, Work w, int32_t *__restrict__ err) {
     const int b = blockIdx.y;
     const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (i >= grid_count(n_cand, b, M)) return;
+    if (i >= pn2_rows_or_all(n_cand, b, M)) return;
     const float *p = cand + ((int64_t)b * M + i) * ldc;
     unsigned long long key;
     int slot = -1;
@@ -136,7 +136,7 @@ __global__ __launch_bounds__(kThreads) void grid_knn_kernel(const float *__restr
         if (sorted) row = __float_as_int(r.w);
         if (row < 0 || row >= M) return;
     } else {
-        if (i >= grid_count(n_query, b, N)) return;
+        if (i >= pn2_rows_or_all(n_query, b, N)) return;
         const float *q = query + ((int64_t)b * N + i) * ldq;
         qx = q[0]; qy = q[1]; qz = q[2];
     }

@@ -70,10 +70,6 @@ Work carve(const Carve &ws, void *workspace) {
     return w;
 }
 
-__device__ __forceinline__ int grid_count(const int64_t *__restrict__ n, int b, int full) {
-    return n == nullptr ? full : pn2_clamped_rows(n, b, full);          // (no count: every row)
-}
-
 bool grid_shape_ok(int B, int64_t M) { return pn2_slot_shape_ok(B, M) && M >= 1; }
 
 // One lane's walk over the 27 cells around the query (qx, qy, qz) of cloud b: every indexed candidate of those cells with

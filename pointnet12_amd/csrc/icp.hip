@@ -1,34 +1,31 @@
 // Rigid scan registration: pn2_icp_step does ONE Gauss-Newton iteration of point-to-plane or point-to-point ICP for B clouds against
 // targets that pn2_grid_build has binned.  The rule is in include/pn2.h under "ICP step" and in numpy in tests/icp_ref.py.
 //
-//   icp_accumulate_kernel  one workgroup per tile of kIcpTile source rows, one row per lane, kIcpRows rows per lane one after another:
-//                          the row through T in fp64, rounded to fp32, the K = 1 walk over the 27 cells (grid_walk.h: the walk and
-//                          the arithmetic of pn2_grid_knn), the residual and its Jacobian in fp64, the 28 products added to 28
-//                          accumulators in registers.  Then a butterfly over the wave (pn2_wave_sum_f64), the four waves through LDS
-//                          in wave order, ONE partial of kIcpWords doubles per tile with ordinary vector stores.  Neither the
+//   icp_accumulate_kernel  one workgroup per tile of source rows, one row per lane (the tiled sum of tile_sum.h on kIcpWords words):
+//                          the row through T in fp64 (rigid.h), rounded to fp32, the K = 1 walk over the 27 cells (grid_walk.h: the
+//                          walk and the arithmetic of pn2_grid_knn), the residual and its Jacobian in fp64, the 28 products added
+//                          to 28 accumulators in registers, the row counted in a 29th; ONE partial per tile.  Neither the
 //                          transformed cloud nor a distance per row goes to memory.  A tile at or beyond the cloud's count writes
 //                          zeros (the workspace arrives holding anything); the tiles of a frozen cloud return at once.
-//   icp_finish_kernel      one workgroup per cloud: word k of the partials of tiles c, c + 8, c + 16 ... is added by thread (k, c) in
-//                          ascending tile order, the eight chunks by ONE lane in chunk order; that lane then does the 6 x 6 Cholesky
-//                          solve, the rotation update and the status on scalars.
-//   The order of every sum is a function of (B, N) alone -- which lane holds which row, the butterfly, the wave order, the chunk
-//   assignment -- and of nothing the hardware decides: the bytes are the same from run to run.  No float atomics (the only atomics
-//   are the ORs into err), no thread waits for another thread's write, nothing is allocated, two plain launches.
+//   icp_finish_kernel      one workgroup per cloud: the total of the partials; ONE lane then does the 6 x 6 Cholesky solve, the
+//                          rotation update and the status on scalars.
+//   The order of every sum is a function of (B, N) alone: tile_sum.h states it.  No float atomics (the only atomics are the ORs
+//   into err), no thread waits for another thread's write, nothing is allocated, two plain launches.
 //
 // This file is built with -ffp-contract=off: every term is the separately rounded fp64 statement of the header.
 #include <cmath>
 #include "grid_walk.h"
+#include "rigid.h"
+#include "tile_sum.h"
 
 namespace {
 
-constexpr int kIcpRows = 4;                                         // rows per lane
-constexpr int kIcpTile = kThreads * kIcpRows;                       // rows per workgroup
+static_assert(kThreads == kSumThreads, "the walk's workgroup is the tiled sum's");
 constexpr int kIcpSums = 28;                                        // A's upper triangle (21), b (6), E
 constexpr int kIcpWords = kIcpSums + 1;                             // ... and the count, as a double (an integer below 2^31: exact)
-constexpr int kChunks = 8;                                          // of the finish kernel: thread (k, c) adds word k of the tiles c, c + 8, ...
 
 // the 28 products of one residual: J_k J_l for k <= l row-major, J_k r, r r -- each one multiplication and one addition
-__device__ __forceinline__ void icp_add_terms(double (&acc)[kIcpSums], const double (&J)[6], double r) {
+__device__ __forceinline__ void icp_add_terms(double (&acc)[kIcpWords], const double (&J)[6], double r) {
     int at = 0;
 #pragma unroll
     for (int k = 0; k < 6; ++k)
@@ -43,7 +40,7 @@ __device__ __forceinline__ void icp_add_terms(double (&acc)[kIcpSums], const dou
 }
 
 // one residual along n at the transformed point p with e = p - q
-__device__ __forceinline__ void icp_residual(double (&acc)[kIcpSums], double px, double py, double pz, double ex, double ey, double ez,
+__device__ __forceinline__ void icp_residual(double (&acc)[kIcpWords], double px, double py, double pz, double ex, double ey, double ez,
                                              double nx, double ny, double nz) {
     const double r = (nx * ex + ny * ey) + nz * ez;
     const double J[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz};
@@ -57,27 +54,25 @@ __global__ __launch_bounds__(kThreads) void icp_accumulate_kernel(const float *_
                                                                   int eval, const double *__restrict__ T, const int32_t *__restrict__ status,
                                                                   int64_t *__restrict__ corr, int32_t *__restrict__ err,
                                                                   double *__restrict__ partial) {
-    __shared__ double s_wave[kWaves][kIcpWords];
-    const int b = blockIdx.y, tile = blockIdx.x, t = threadIdx.x;
+    __shared__ double s_wave[kSumWaves][kIcpWords];
+    const int b = blockIdx.y, tile = blockIdx.x;
     if (!eval && (status[b] & (PN2_ICP_CONVERGED | PN2_ICP_SINGULAR)) != 0) return;        // frozen: not walked (uniform over the workgroup)
-    const int n = grid_count(n_src, b, N);
-    double acc[kIcpSums];
+    const int n = pn2_rows_or_all(n_src, b, N);
+    double acc[kIcpWords];
 #pragma unroll
     for (int k = 0; k < kIcpSums; ++k) acc[k] = 0.0;
     int rows = 0;
-    if ((int64_t)tile * kIcpTile < n) {
+    if ((int64_t)tile * kSumTile < n) {
         double R[12];
 #pragma unroll
         for (int k = 0; k < 12; ++k) R[k] = T[(int64_t)b * 12 + k];
 #pragma nounroll
-        for (int r = 0; r < kIcpRows; ++r) {
-            const int64_t i = (int64_t)tile * kIcpTile + (int64_t)r * kThreads + t;
+        for (int r = 0; r < kSumRows; ++r) {
+            const int64_t i = pn2_tile_row(tile, r);
             if (i >= n) continue;
             const float *s = src + ((int64_t)b * N + i) * lds;
             const double sx = (double)s[0], sy = (double)s[1], sz = (double)s[2];
-            const double px = ((R[0] * sx + R[1] * sy) + R[2] * sz) + R[3];
-            const double py = ((R[4] * sx + R[5] * sy) + R[6] * sz) + R[7];
-            const double pz = ((R[8] * sx + R[9] * sy) + R[10] * sz) + R[11];
+            const double px = pn2_rigid_apply<0>(R, sx, sy, sz), py = pn2_rigid_apply<1>(R, sx, sy, sz), pz = pn2_rigid_apply<2>(R, sx, sy, sz);
             float bd[1] = {INFINITY};
             int bi[1] = {M};
             int took = 0;
@@ -102,21 +97,8 @@ __global__ __launch_bounds__(kThreads) void icp_accumulate_kernel(const float *_
             ++rows;
         }
     }
-    // the wave, the four waves in wave order, one partial per tile
-    const int lane = t & (PN2_WAVE - 1), wave = t >> 6;
-#pragma unroll
-    for (int k = 0; k < kIcpSums; ++k) {
-        const double v = pn2_wave_sum_f64(acc[k]);
-        if (lane == 0) s_wave[wave][k] = v;
-    }
-    const double c = pn2_wave_sum_f64((double)rows);
-    if (lane == 0) s_wave[wave][kIcpSums] = c;
-    __syncthreads();
-    if (t < kIcpWords) {
-        double v = s_wave[0][t];
-        for (int k = 1; k < kWaves; ++k) v = v + s_wave[k][t];
-        partial[((int64_t)b * gridDim.x + tile) * kIcpWords + t] = v;
-    }
+    acc[kIcpSums] = (double)rows;
+    pn2_tile_partial(acc, s_wave, partial + ((int64_t)b * gridDim.x + tile) * kIcpWords);
 }
 
 constexpr int icp_upper(int k, int l) { return k * 6 - k * (k - 1) / 2 + (l - k); }        // A_kl, k <= l, in the 21 words
@@ -124,7 +106,7 @@ constexpr int icp_lower(int i, int j) { return i * (i + 1) / 2 + j; }           
 static_assert(icp_upper(5, 5) == 20 && icp_upper(1, 1) == 6 && icp_lower(5, 5) == 20, "two triangles of 21 words");
 
 // A x = -b by Cholesky in index order; false: a pivot at or below 2^-40 of its diagonal entry, or not finite
-__device__ __forceinline__ bool icp_solve(const double (&S)[kIcpSums], double (&x)[6]) {
+__device__ __forceinline__ bool icp_solve(const double (&S)[kIcpWords], double (&x)[6]) {
     double L[21];
     bool ok = true;
 #pragma unroll
@@ -167,29 +149,14 @@ __global__ __launch_bounds__(kThreads) void icp_finish_kernel(int tiles, int met
                                                               double *__restrict__ sums, int64_t *__restrict__ count,
                                                               double *__restrict__ xout, int32_t *__restrict__ status,
                                                               int32_t *__restrict__ iters, int32_t *__restrict__ err) {
-    __shared__ double s_chunk[kChunks][32];
-    const int b = blockIdx.x, t = threadIdx.x;
+    __shared__ double s_chunk[kSumChunks][32];
+    const int b = blockIdx.x;
     if (!eval && (status[b] & (PN2_ICP_CONVERGED | PN2_ICP_SINGULAR)) != 0) return;        // frozen: nothing is touched
-    const int k = t & 31, c = t >> 5;
-    double v = 0.0;
-    if (k < kIcpWords)
-        for (int tile = c; tile < tiles; tile += kChunks) v = v + partial[((int64_t)b * tiles + tile) * kIcpWords + k];
-    s_chunk[c][k] = v;
-    __syncthreads();
-    if (t != 0) return;
-    double S[kIcpSums];
+    double S[kIcpWords];
+    if (!pn2_tile_total(partial + (int64_t)b * tiles * kIcpWords, tiles, s_chunk, S)) return;
 #pragma unroll
-    for (int q = 0; q < kIcpSums; ++q) {
-        double s = s_chunk[0][q];
-#pragma unroll
-        for (int h = 1; h < kChunks; ++h) s = s + s_chunk[h][q];
-        S[q] = s;
-        sums[(int64_t)b * kIcpSums + q] = s;
-    }
-    double cn = s_chunk[0][kIcpSums];
-#pragma unroll
-    for (int h = 1; h < kChunks; ++h) cn = cn + s_chunk[h][kIcpSums];
-    const int64_t n = (int64_t)cn;
+    for (int q = 0; q < kIcpSums; ++q) sums[(int64_t)b * kIcpSums + q] = S[q];
+    const int64_t n = (int64_t)S[kIcpSums];
     count[b] = n;
     if (eval) return;
 
@@ -240,14 +207,12 @@ __global__ __launch_bounds__(kThreads) void icp_finish_kernel(int tiles, int met
     if (th <= tol_rot && step <= tol_trans) status[b] = status[b] | PN2_ICP_CONVERGED;
 }
 
-bool icp_shape_ok(int B, int64_t N) { return B >= 1 && B <= 65535 && N >= 1 && N <= 0x7FFFFF00; }
-
 }  // namespace
 
 extern "C" {
 
 int64_t pn2_icp_workspace_bytes(int B, int N) {
-    return icp_shape_ok(B, N) ? pn2_round16((int64_t)B * pn2_cdiv(N, kIcpTile) * kIcpWords * (int64_t)sizeof(double)) : PN2_EINVAL;
+    return pn2_cloud_shape_ok(B, N) ? pn2_round16((int64_t)B * pn2_cdiv(N, kSumTile) * kIcpWords * (int64_t)sizeof(double)) : PN2_EINVAL;
 }
 
 int pn2_icp_step(const float *src, int lds, int B, int N, const int64_t *n_src, const float *tgt, int ldt, int M, const float *tgt_normal,
@@ -258,7 +223,7 @@ int pn2_icp_step(const float *src, int lds, int B, int N, const int64_t *n_src, 
     PN2_CHECK_ARG((flags & ~PN2_ICP_EVAL_ONLY) == 0 && (metric == PN2_ICP_POINT || metric == PN2_ICP_PLANE));
     const int eval = (flags & PN2_ICP_EVAL_ONLY) != 0;
     PN2_CHECK_ARG(eval || (x && status && iters));
-    PN2_CHECK_ARG(icp_shape_ok(B, N) && grid_shape_ok(B, M));
+    PN2_CHECK_ARG(pn2_cloud_shape_ok(B, N) && grid_shape_ok(B, M));
     PN2_CHECK_ARG(lds >= 3 && lds <= 16 && ldt >= 3 && ldt <= 16);
     PN2_CHECK_ARG(metric == PN2_ICP_POINT || (tgt_normal != nullptr && ldn >= 3 && ldn <= 16));
     PN2_CHECK_ARG(std::isfinite(tol_rot) && std::isfinite(tol_trans) && tol_rot >= 0.0 && tol_trans >= 0.0);
@@ -268,7 +233,7 @@ int pn2_icp_step(const float *src, int lds, int B, int N, const int64_t *n_src, 
     Grid grid;
     PN2_CHECK_ARG(pn2_grid_from(origin, cell, grid));
     const Work w = carve(Carve(B, M), const_cast<void *>(grid_workspace));         // (only read)
-    const int tiles = (int)pn2_cdiv(N, kIcpTile);
+    const int tiles = (int)pn2_cdiv(N, kSumTile);
     double *partial = static_cast<double *>(workspace);
     const hipStream_t s = pn2_s(stream);
     const dim3 by_tile((unsigned)tiles, (unsigned)B);

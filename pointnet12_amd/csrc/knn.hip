@@ -10,10 +10,6 @@ namespace {
 constexpr int KNN_TILE = 1024;
 constexpr int KNN_THREADS = 256;
 
-__device__ __forceinline__ int knn_count(const int64_t *__restrict__ n, int b, int full) {
-    return n == nullptr ? full : pn2_clamped_rows(n, b, full);         // (no count: every row)
-}
-
 // ---------------------------------------------------------------------------------------------
 // One query per lane; the candidates are staged through LDS as (x, y, z, |p|^2) tiles and broadcast-read, as
 // three_nn_kernel does.  Each lane keeps its CAP best (d2, index) pairs in registers, ascending; a candidate is tested
@@ -29,7 +25,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_kernel(const float *__restric
                                                           float *__restrict__ dist) {
     __shared__ float4 tile[KNN_TILE];
     const int b = blockIdx.y;
-    const int nq_b = knn_count(n_query, b, N), mc = knn_count(n_cand, b, M);
+    const int nq_b = pn2_rows_or_all(n_query, b, N), mc = pn2_rows_or_all(n_cand, b, M);
     if ((int)(blockIdx.x * KNN_THREADS) >= nq_b) return;                  // (block-uniform: no barrier is skipped by a part of it)
     const int n = blockIdx.x * KNN_THREADS + threadIdx.x;
     const bool live = n < nq_b;
@@ -105,7 +101,7 @@ __global__ __launch_bounds__(256) void knn_vote_kernel(const int64_t *__restrict
                                                        int64_t out_stride, int32_t *__restrict__ out, int32_t *__restrict__ err) {
     const int b = blockIdx.y;
     const int n = blockIdx.x * 256 + threadIdx.x;
-    if (n >= knn_count(n_query, b, N)) return;
+    if (n >= pn2_rows_or_all(n_query, b, N)) return;
     const size_t o = ((size_t)b * N + n) * K;
     const int64_t *labels = cand_label + (size_t)b * M;
     int64_t lab[CAP];

@@ -73,7 +73,7 @@ __global__ __launch_bounds__(PCA_THREADS) void local_pca_kernel(const float *__r
                                                                 int32_t *__restrict__ count, int32_t *__restrict__ err) {
     const int b = blockIdx.y;
     const int n = blockIdx.x * PCA_THREADS + threadIdx.x;
-    if (n >= (n_query == nullptr ? N : pn2_clamped_rows(n_query, b, N))) return;
+    if (n >= pn2_rows_or_all(n_query, b, N)) return;
     const size_t row = (size_t)b * N + n;
     const int64_t *ri = idx + row * K;
     const float *rd = DIST ? dist + row * K : nullptr;

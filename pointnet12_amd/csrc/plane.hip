@@ -8,38 +8,33 @@
 //                            for a row that takes no part or is not finite: its residual is NaN and fails the compare) and every
 //                            lane reads the same address, a broadcast.  The lane's count is an integer in a register: there is no
 //                            cross-lane reduction at all.  One int32 per (tile, hypothesis) goes to the workspace.
-//   plane_select_kernel      one workgroup per cloud: thread t adds the tile counts of hypotheses t, t + 256, ... in tile order, keeps
-//                            the largest (count, lowest h) as one 64-bit key, the 256 keys meet through a wave maximum and LDS.
-//   plane_accumulate_kernel  icp.hip's tile scheme on ten words: one row per lane, kRefitRows rows one after another, a butterfly
-//   plane_finish_kernel      over the wave, the waves in wave order, one partial per tile; then thread (k, c) adds word k of the
-//                            tiles c, c + 8, ..., one lane adds the chunks in order, takes pn2_sym_eig3 and writes the plane.
-//   plane_count_kernel       the inliers of the final plane: a ballot and a popcount per wave, one int32 per tile.
+//   plane_select_kernel      one workgroup per cloud: the largest count, the lowest h among equals (ransac_select.h); the best
+//                            hypothesis is the plane, zeros without one.
+//   plane_accumulate_kernel  the tiled sum of tile_sum.h on ten words: one partial per tile; then one lane holds the totals, takes
+//   plane_finish_kernel      pn2_sym_eig3 and writes the plane.
+//   plane_count_kernel       the inliers of the final plane over the same tiles: a ballot and a popcount per wave, one int32 per tile.
 //   plane_write_kernel       every workgroup adds those tile counts itself (integers: any order), decides min_inliers from the sum
 //                            and writes dist and assign for its tile; tile 0 writes count and the status bit.
-//   The order of every floating-point sum is a function of (B, N) alone.  No float atomics (the only atomics are the ORs into err),
+//   The order of every floating-point sum is a function of (B, N) alone (tile_sum.h).  No float atomics (the only atomics are the ORs into err),
 //   no thread waits for another thread's write, nothing is allocated, plain launches.
 //
 // This file is built with -ffp-contract=off: every term is the separately rounded fp64 statement of the header.
 #include <cmath>
 #include "pn2_common.h"
 #include "ransac_sample.h"
+#include "ransac_select.h"
 #include "sym_eig3.h"
+#include "tile_sum.h"
 
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kSumThreads;                               // every kernel here; the count and write kernels walk tile_sum.h's tiles too
 constexpr int kWaves = kThreads / PN2_WAVE;
-constexpr int kScoreTile = 512;                                     // rows per scoring workgroup (12 KiB of LDS)
-constexpr int kRefitRows = 4;                                       // rows per lane of the accumulate / count / write kernels
-constexpr int kRowTile = kThreads * kRefitRows;                     // rows per workgroup there
 constexpr int kSums = 10;                                           // count, sum q (3), sum q q^T (xx, xy, xz, yy, yz, zz)
-constexpr int kChunks = 8;                                          // of the finish kernel
 
 struct Axis {
     double x, y, z;
 };
-
-__device__ __forceinline__ int plane_count(const int64_t *n, int b, int full) { return n == nullptr ? full : pn2_clamped_rows(n, b, full); }
 
 __device__ __forceinline__ bool plane_takes_part(const int32_t *assign, int64_t at) { return assign == nullptr || assign[at] < 0; }
 
@@ -63,7 +58,7 @@ __global__ __launch_bounds__(kThreads) void plane_hypothesis_kernel(const float 
                                                                     double cos_max, double *__restrict__ hyp) {
     const int b = blockIdx.y, h = blockIdx.x * kThreads + threadIdx.x;
     if (h >= H) return;
-    const int n = plane_count(n_points, b, N);
+    const int n = pn2_rows_or_all(n_points, b, N);
     const double nan = __builtin_nan("");
     double nx = nan, ny = nan, nz = nan, d = nan;
     const int64_t r0 = ransac_sample(seed, b, h, 0, n), r1 = ransac_sample(seed, b, h, 1, n), r2 = ransac_sample(seed, b, h, 2, n);    // (ransac_sample.h)
@@ -109,7 +104,7 @@ __global__ __launch_bounds__(kThreads) void plane_score_kernel(const float *__re
                                                                int32_t *__restrict__ err) {
     __shared__ double s_x[kScoreTile], s_y[kScoreTile], s_z[kScoreTile];
     const int b = blockIdx.z, tile = blockIdx.x, t = threadIdx.x;
-    const int n = plane_count(n_points, b, N);
+    const int n = pn2_rows_or_all(n_points, b, N);
     const int first = tile * kScoreTile;
     if (first >= n) return;                                         // (uniform over the workgroup; the select kernel does not read this tile)
     const int cnt = min(kScoreTile, n - first);
@@ -146,33 +141,14 @@ __global__ __launch_bounds__(kThreads) void plane_select_kernel(int N, const int
                                                                 int64_t *__restrict__ best_count, int32_t *__restrict__ status,
                                                                 int32_t *__restrict__ err) {
     __shared__ unsigned long long s_key[kWaves];
-    const int b = blockIdx.x, t = threadIdx.x;
-    const int n = plane_count(n_points, b, N);
-    const int live = (int)(((int64_t)n + kScoreTile - 1) / kScoreTile);         // the tiles the scoring pass wrote
-    // key: (count + 1) in the high word, ~h in the low one: the largest count, the lowest h among equals; 0 = no valid hypothesis
-    unsigned long long key = 0;
-    for (int h = t; h < H; h += kThreads) {
-        const double nx = hyp[((int64_t)b * H + h) * 4];
-        const bool valid = nx == nx;
-        int64_t c = 0;
-        for (int tile = 0; tile < live; ++tile) c += tile_count[((int64_t)b * tiles + tile) * H + h];
-        if (hyp_count != nullptr) hyp_count[(int64_t)b * H + h] = valid ? (int32_t)c : -1;
-        const unsigned long long k = ((unsigned long long)(c + 1) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)h);
-        if (valid && k > key) key = k;
-    }
-    key = pn2_wave_max_u64(key);
-    if ((t & (PN2_WAVE - 1)) == 0) s_key[t >> 6] = key;
-    __syncthreads();
-    if (t != 0) return;
-    for (int k = 1; k < kWaves; ++k) key = s_key[k] > key ? s_key[k] : key;
-    const bool any = key != 0;
-    const int h = any ? (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull)) : -1;
-    const int64_t c = any ? (int64_t)(key >> 32) - 1 : 0;
-    best_h[b] = h;
-    best_count[b] = c;
-    const bool none = !any || c < 3;
+    const int b = blockIdx.x;
+    RansacBest best;
+    if (!ransac_select(b, pn2_rows_or_all(n_points, b, N), H, hyp, 4, tiles, tile_count, hyp_count, s_key, best)) return;
+    best_h[b] = best.h;
+    best_count[b] = best.count;
+    const bool none = !best.any || best.count < 3;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) plane[(int64_t)b * 4 + k] = none ? 0.0 : hyp[((int64_t)b * H + h) * 4 + k];
+    for (int k = 0; k < 4; ++k) plane[(int64_t)b * 4 + k] = none ? 0.0 : hyp[((int64_t)b * H + best.h) * 4 + k];
     status[b] = none ? PN2_PLANE_NONE : 0;
     if (none && err != nullptr) atomicOr(err, PN2_PLANE_ERR_NONE);
 }
@@ -190,21 +166,21 @@ __global__ __launch_bounds__(kThreads) void plane_accumulate_kernel(const float 
                                                                     const int32_t *__restrict__ assign, double threshold,
                                                                     const double *__restrict__ plane, const int32_t *__restrict__ status,
                                                                     double *__restrict__ partial) {
-    __shared__ double s_wave[kWaves][kSums];
-    const int b = blockIdx.y, tile = blockIdx.x, t = threadIdx.x;
+    __shared__ double s_wave[kSumWaves][kSums];
+    const int b = blockIdx.y, tile = blockIdx.x;
     if ((status[b] & PN2_PLANE_NONE) != 0) return;                  // (uniform over the workgroup)
-    const int n = plane_count(n_points, b, N);
+    const int n = pn2_rows_or_all(n_points, b, N);
     double acc[kSums];
 #pragma unroll
     for (int k = 0; k < kSums; ++k) acc[k] = 0.0;
-    if ((int64_t)tile * kRowTile < n) {
+    if ((int64_t)tile * kSumTile < n) {
         double P[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) P[k] = plane[(int64_t)b * 4 + k];
         const double sx = -P[3] * P[0], sy = -P[3] * P[1], sz = -P[3] * P[2];
 #pragma nounroll
-        for (int r = 0; r < kRefitRows; ++r) {
-            const int64_t i = (int64_t)tile * kRowTile + (int64_t)r * kThreads + t;
+        for (int r = 0; r < kSumRows; ++r) {
+            const int64_t i = pn2_tile_row(tile, r);
             if (i >= n) continue;
             const int64_t at = (int64_t)b * N + i;
             double x, y, z;
@@ -223,41 +199,18 @@ __global__ __launch_bounds__(kThreads) void plane_accumulate_kernel(const float 
             acc[9] = acc[9] + qz * qz;
         }
     }
-    const int lane = t & (PN2_WAVE - 1), wave = t >> 6;
-#pragma unroll
-    for (int k = 0; k < kSums; ++k) {
-        const double v = pn2_wave_sum_f64(acc[k]);
-        if (lane == 0) s_wave[wave][k] = v;
-    }
-    __syncthreads();
-    if (t < kSums) {
-        double v = s_wave[0][t];
-        for (int k = 1; k < kWaves; ++k) v = v + s_wave[k][t];
-        partial[((int64_t)b * gridDim.x + tile) * kSums + t] = v;
-    }
+    pn2_tile_partial(acc, s_wave, partial + ((int64_t)b * gridDim.x + tile) * kSums);
 }
 
 __global__ __launch_bounds__(kThreads) void plane_finish_kernel(int tiles, Axis axis, const double *__restrict__ partial, double *__restrict__ plane,
                                                                 double *__restrict__ rmse, double *__restrict__ sums, int32_t *__restrict__ status) {
-    __shared__ double s_chunk[kChunks][32];
-    const int b = blockIdx.x, t = threadIdx.x;
+    __shared__ double s_chunk[kSumChunks][32];
+    const int b = blockIdx.x;
     if ((status[b] & PN2_PLANE_NONE) != 0) return;
-    const int k = t & 31, c = t >> 5;
-    double v = 0.0;
-    if (k < kSums)
-        for (int tile = c; tile < tiles; tile += kChunks) v = v + partial[((int64_t)b * tiles + tile) * kSums + k];
-    s_chunk[c][k] = v;
-    __syncthreads();
-    if (t != 0) return;
     double S[kSums];
+    if (!pn2_tile_total(partial + (int64_t)b * tiles * kSums, tiles, s_chunk, S)) return;
 #pragma unroll
-    for (int q = 0; q < kSums; ++q) {
-        double s = s_chunk[0][q];
-#pragma unroll
-        for (int h = 1; h < kChunks; ++h) s = s + s_chunk[h][q];
-        S[q] = s;
-        sums[(int64_t)b * kSums + q] = s;
-    }
+    for (int q = 0; q < kSums; ++q) sums[(int64_t)b * kSums + q] = S[q];
     const double count = S[0];
     const double nx0 = plane[(int64_t)b * 4], ny0 = plane[(int64_t)b * 4 + 1], nz0 = plane[(int64_t)b * 4 + 2], d0 = plane[(int64_t)b * 4 + 3];
     const double sx = -d0 * nx0, sy = -d0 * ny0, sz = -d0 * nz0;
@@ -284,15 +237,15 @@ __global__ __launch_bounds__(kThreads) void plane_count_kernel(const float *__re
     __shared__ int s_wave[kWaves];
     const int b = blockIdx.y, tile = blockIdx.x, t = threadIdx.x;
     if ((status[b] & PN2_PLANE_NONE) != 0) return;
-    const int n = plane_count(n_points, b, N);
+    const int n = pn2_rows_or_all(n_points, b, N);
     int count = 0;
-    if ((int64_t)tile * kRowTile < n) {
+    if ((int64_t)tile * kSumTile < n) {
         double P[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) P[k] = plane[(int64_t)b * 4 + k];
 #pragma nounroll
-        for (int r = 0; r < kRefitRows; ++r) {
-            const int64_t i = (int64_t)tile * kRowTile + (int64_t)r * kThreads + t;
+        for (int r = 0; r < kSumRows; ++r) {
+            const int64_t i = pn2_tile_row(tile, r);
             bool in = false;
             if (i < n) {
                 const int64_t at = (int64_t)b * N + i;
@@ -333,13 +286,13 @@ __global__ __launch_bounds__(kThreads) void plane_write_kernel(const float *__re
         count[b] = c;
         if (!mark) status[b] = status[b] | PN2_PLANE_SMALL;         // (only this thread writes status[b]; the others read the NONE bit, which it keeps)
     }
-    const int n = plane_count(n_points, b, N);
+    const int n = pn2_rows_or_all(n_points, b, N);
     double P[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) P[k] = plane[(int64_t)b * 4 + k];
 #pragma nounroll
-    for (int r = 0; r < kRefitRows; ++r) {
-        const int64_t i = (int64_t)tile * kRowTile + (int64_t)r * kThreads + t;
+    for (int r = 0; r < kSumRows; ++r) {
+        const int64_t i = pn2_tile_row(tile, r);
         if (i >= n) continue;
         const int64_t at = (int64_t)b * N + i;
         double x, y, z;
@@ -348,8 +301,6 @@ __global__ __launch_bounds__(kThreads) void plane_write_kernel(const float *__re
         if (assign != nullptr && mark && fabs(res) <= threshold && assign[at] < 0) assign[at] = plane_id;
     }
 }
-
-bool plane_shape_ok(int B, int64_t N) { return B >= 1 && B <= 65535 && N >= 1 && N <= 0x7FFFFF00; }
 
 bool plane_axis(const double *axis, Axis &a) {
     if (axis == nullptr || !(std::isfinite(axis[0]) && std::isfinite(axis[1]) && std::isfinite(axis[2]))) return false;
@@ -373,9 +324,9 @@ PlaneWork plane_carve(int B, int64_t N, int H, void *base) {
     PlaneWork w;
     int64_t at = 0;
     w.partial = reinterpret_cast<double *>(p + at);
-    at += pn2_round16((int64_t)B * pn2_cdiv(N, kRowTile) * kSums * (int64_t)sizeof(double));
+    at += pn2_round16((int64_t)B * pn2_cdiv(N, kSumTile) * kSums * (int64_t)sizeof(double));
     w.rows = reinterpret_cast<int32_t *>(p + at);
-    at += pn2_round16((int64_t)B * pn2_cdiv(N, kRowTile) * (int64_t)sizeof(int32_t));
+    at += pn2_round16((int64_t)B * pn2_cdiv(N, kSumTile) * (int64_t)sizeof(int32_t));
     w.hyp = reinterpret_cast<double *>(p + at);
     at += pn2_round16((int64_t)B * H * 4 * (int64_t)sizeof(double));
     w.score = reinterpret_cast<int32_t *>(p + at);
@@ -389,7 +340,7 @@ PlaneWork plane_carve(int B, int64_t N, int H, void *base) {
 extern "C" {
 
 int64_t pn2_plane_workspace_bytes(int B, int N, int H) {
-    if (!plane_shape_ok(B, N) || H < 1 || H > 65536) return PN2_EINVAL;
+    if (!pn2_cloud_shape_ok(B, N) || H < 1 || H > 65536) return PN2_EINVAL;
     return plane_carve(B, N, H, nullptr).bytes;
 }
 
@@ -397,7 +348,7 @@ int pn2_plane_ransac(const float *pts, int ld, int B, int N, const int64_t *n_po
                      const double *axis, double cos_max, double threshold, double *plane, int32_t *hyp_count, int32_t *best_h,
                      int64_t *best_count, int32_t *status, int32_t *err, void *workspace, pn2_stream_t stream) {
     PN2_CHECK_ARG(pts && plane && best_h && best_count && status && workspace);
-    PN2_CHECK_ARG(plane_shape_ok(B, N) && H >= 1 && H <= 65536 && ld >= 3 && ld <= 16);
+    PN2_CHECK_ARG(pn2_cloud_shape_ok(B, N) && H >= 1 && H <= 65536 && ld >= 3 && ld <= 16);
     PN2_CHECK_ARG(std::isfinite(threshold) && threshold >= 0.0 && std::isfinite(cos_max));
     Axis a;
     PN2_CHECK_ARG(plane_axis(axis, a));
@@ -419,14 +370,14 @@ int pn2_plane_ransac(const float *pts, int ld, int B, int N, const int64_t *n_po
 int pn2_plane_refit(const float *pts, int ld, int B, int N, const int64_t *n_points, const int32_t *assign, const double *axis,
                     double threshold, double *plane, double *rmse, double *sums, int32_t *status, void *workspace, pn2_stream_t stream) {
     PN2_CHECK_ARG(pts && plane && rmse && sums && status && workspace);
-    PN2_CHECK_ARG(plane_shape_ok(B, N) && ld >= 3 && ld <= 16);
+    PN2_CHECK_ARG(pn2_cloud_shape_ok(B, N) && ld >= 3 && ld <= 16);
     PN2_CHECK_ARG(std::isfinite(threshold) && threshold >= 0.0);
     Axis a;
     PN2_CHECK_ARG(plane_axis(axis, a));
     PN2_CHECK_ARG(pn2_aligned(pts, 4) && pn2_aligned(assign, 4) && pn2_aligned(n_points, 8) && pn2_aligned(plane, 8) && pn2_aligned(rmse, 8));
     PN2_CHECK_ARG(pn2_aligned(sums, 8) && pn2_aligned(status, 4) && pn2_aligned(workspace, 16));
     const PlaneWork w = plane_carve(B, N, 1, workspace);
-    const int tiles = (int)pn2_cdiv(N, kRowTile);
+    const int tiles = (int)pn2_cdiv(N, kSumTile);
     const hipStream_t s = pn2_s(stream);
     hipLaunchKernelGGL(plane_accumulate_kernel, dim3((unsigned)tiles, (unsigned)B), dim3(kThreads), 0, s, pts, ld, N, n_points, assign, threshold,
                        plane, status, w.partial);
@@ -438,12 +389,12 @@ int pn2_plane_classify(const float *pts, int ld, int B, int N, const int64_t *n_
                        double threshold, const double *plane, int32_t *status, float *dist, int64_t *count, void *workspace,
                        pn2_stream_t stream) {
     PN2_CHECK_ARG(pts && plane && status && count && workspace);
-    PN2_CHECK_ARG(plane_shape_ok(B, N) && ld >= 3 && ld <= 16);
+    PN2_CHECK_ARG(pn2_cloud_shape_ok(B, N) && ld >= 3 && ld <= 16);
     PN2_CHECK_ARG(std::isfinite(threshold) && threshold >= 0.0 && plane_id >= 0);
     PN2_CHECK_ARG(pn2_aligned(pts, 4) && pn2_aligned(assign, 4) && pn2_aligned(n_points, 8) && pn2_aligned(plane, 8) && pn2_aligned(status, 4));
     PN2_CHECK_ARG(pn2_aligned(dist, 4) && pn2_aligned(count, 8) && pn2_aligned(workspace, 16));
     const PlaneWork w = plane_carve(B, N, 1, workspace);
-    const int tiles = (int)pn2_cdiv(N, kRowTile);
+    const int tiles = (int)pn2_cdiv(N, kSumTile);
     const hipStream_t s = pn2_s(stream);
     const dim3 by_tile((unsigned)tiles, (unsigned)B);
     hipLaunchKernelGGL(plane_count_kernel, by_tile, dim3(kThreads), 0, s, pts, ld, N, n_points, assign, threshold, plane, status, w.rows);

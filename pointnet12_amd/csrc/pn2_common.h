@@ -42,6 +42,14 @@ __device__ __forceinline__ int pn2_clamped_rows(const int64_t *count, int b, int
     return n < 0 ? 0 : (n > max_rows ? max_rows : (int)n);
 }
 
+// the same where the count array is optional: without one, every row
+__device__ __forceinline__ int pn2_rows_or_all(const int64_t *count, int b, int full) {
+    return count == nullptr ? full : pn2_clamped_rows(count, b, full);
+}
+
+// B clouds of N rows each: what a grid of (tiles, B) workgroups and an int row index can hold
+static inline bool pn2_cloud_shape_ok(int B, int64_t N) { return B >= 1 && B <= 65535 && N >= 1 && N <= 0x7FFFFF00; }
+
 // ----------------------------------------------------------------------------- library options
 // Dispatch / tuning switches of the library.  They are set EXPLICITLY through pn2_set_option() (include/pn2.h): the library
 // never reads the process environment, so an external caller's results depend on its arguments and on the options it set,
