@@ -153,6 +153,11 @@ SIGNATURES = {
     "pn2_lovasz_bwd": (_i, [_vp, _i, _i64, _vp, _i64, _i, _i, _vp, _vp, _vp]),
 }
 
+# The launch entry points: they return a status and take the stream handle as their last (pointer) argument.  Everything else
+# is a host-only call (sizes, capability questions, options); pn2_get_option has the same shape and launches nothing.
+LAUNCHES = frozenset(name for name, (res, args) in SIGNATURES.items()
+                     if res is _i and args and args[-1] is _vp and name != "pn2_get_option")
+HOST_ONLY = frozenset(SIGNATURES) - LAUNCHES
 
 ABI_VERSION = 15
 PN2_EUNSUPPORTED = -3            # include/pn2.h
@@ -242,16 +247,7 @@ class _Timed:
 
     def __getattr__(self, name):
         fn = getattr(_raw, name)
-        if not name.startswith("pn2_") or name in ("pn2_version", "pn2_error_string", "pn2_set_option", "pn2_get_option", "pn2_option_name", "pn2_fps_workspace_bytes",
-                                                   "pn2_nll_loss_workspace_bytes", "pn2_cross_entropy_workspace_bytes", "pn2_res_supported", "pn2_bwd_res_supported", "pn2_conv1x1_wgrad_workspace_bytes",
-                                                   "pn2_conv1x1_wgrad_cf_scratch_bytes", "pn2_conv1x1_bwd_cf_supported", "pn2_conv1x1_bwd_first_supported", "pn2_conv1x1_bwd_cf_scratch_bytes", "pn2_last_kernel", "pn2_clear_last_kernel",
-                                                   "pn2_ball_query_workspace_bytes", "pn2_point_transform_workspace_bytes",
-                                                   "pn2_group_colsum_workspace_bytes", "pn2_chamfer_nn_workspace_bytes",
-                                                   "pn2_scan_filter_workspace_bytes", "pn2_voxel_grid_workspace_bytes",
-                                                   "pn2_segment_reduce_workspace_bytes", "pn2_voxel_components_workspace_bytes",
-                                                   "pn2_panoptic_workspace_bytes", "pn2_lovasz_workspace_bytes", "pn2_lovasz_tile_rows",
-                                                   "pn2_grid_workspace_bytes", "pn2_icp_workspace_bytes", "pn2_plane_workspace_bytes",
-                                                   "pn2_match_pairs_workspace_bytes", "pn2_corr_workspace_bytes", "pn2_segment_boxes_workspace_bytes"):
+        if name not in LAUNCHES:
             return fn
 
         def timed(*args):
@@ -351,6 +347,14 @@ def forward_env_options(lib):
 def check(rc, what):
     if rc != 0:
         raise Pn2Error("%s failed: %s (%d)" % (what, load().pn2_error_string(rc).decode(), rc))
+
+
+def workspace_bytes(entry, args, error, message):
+    """``entry(*args)`` for a ``pn2_*_workspace_bytes`` entry point (host-only calls); a refused shape raises ``error(message)``."""
+    n = int(getattr(load(), entry)(*args))
+    if n < 0:
+        raise error(message)
+    return n
 
 
 def ptr(t):

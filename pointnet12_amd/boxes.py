@@ -54,9 +54,8 @@ class BoxBuffers:
     that is given these buffers; ``check()`` reads it back).  Rows no call writes hold zeros (``angle``: -1)."""
 
     def __init__(self, rows, B, max_rows, angles, device):
-        nbytes = _lib.load().pn2_segment_boxes_workspace_bytes(int(B), int(max_rows))
-        if nbytes < 0:
-            raise _lib.Pn2Error("BoxBuffers: B = %d, max_rows = %d are not supported" % (B, max_rows))
+        nbytes = _lib.workspace_bytes("pn2_segment_boxes_workspace_bytes", (int(B), int(max_rows)), _lib.Pn2Error,
+                                      "BoxBuffers: B = %d, max_rows = %d are not supported" % (B, max_rows))
         self.rows, self.B, self.max_rows, self.angles = int(rows), int(B), int(max_rows), int(angles)
         f = lambda *shape: torch.zeros(*shape, device=device, dtype=torch.float32)
         self.center, self.size, self.lo, self.hi, self.yaw = f(self.rows, 3), f(self.rows, 3), f(self.rows, 3), f(self.rows, 3), f(self.rows)

@@ -56,6 +56,14 @@ struct Cols {
 struct Work {                                                       // the workspace: B * max_rows ints each, then B ints
     int *cnt, *cursor, *bucket, *list, *listed;
 };
+// (the struct goes to the kernels by value: the size comes back through `bytes`)
+Work boxes_work(int B, int64_t max_rows, void *base, int64_t *bytes = nullptr) {
+    Pn2Arena a(base);
+    const int64_t n = (int64_t)B * max_rows;
+    const Work w{a.take<int>(n), a.take<int>(n), a.take<int>(n), a.take<int>(n), a.take<int>(B)};
+    if (bytes != nullptr) *bytes = a.bytes();
+    return w;
+}
 
 struct Out {
     float *center, *size, *yaw, *lo, *hi;
@@ -379,8 +387,9 @@ inline bool shape_ok(int B, int64_t max_rows) { return B >= 1 && B <= 65535 && m
 extern "C" {
 
 int64_t pn2_segment_boxes_workspace_bytes(int B, int64_t max_rows) {
-    if (!shape_ok(B, max_rows)) return PN2_EINVAL;
-    return 4 * pn2_round16((int64_t)B * max_rows * 4) + pn2_round16((int64_t)B * 4);
+    int64_t bytes = PN2_EINVAL;
+    if (shape_ok(B, max_rows)) boxes_work(B, max_rows, nullptr, &bytes);
+    return bytes;
 }
 
 int pn2_segment_boxes(const float *pts, int ld, int cx, int cy, int cz, const int32_t *seg, const int64_t *row_begin, const int64_t *row_count,
@@ -396,14 +405,7 @@ int pn2_segment_boxes(const float *pts, int ld, int cx, int cy, int cz, const in
                   pn2_aligned(yaw, 4) && pn2_aligned(angle, 4) && pn2_aligned(lo, 4) && pn2_aligned(hi, 4) && pn2_aligned(n, 4) &&
                   pn2_aligned(score, 8) && pn2_aligned(err, 4) && pn2_aligned(workspace, 16));
     const int split = split_rows == 0 ? kSplitDefault : split_rows;
-    const int64_t words = pn2_round16((int64_t)B * max_rows * 4);
-    unsigned char *at = static_cast<unsigned char *>(workspace);
-    Work w;
-    w.cnt = reinterpret_cast<int *>(at);
-    w.cursor = reinterpret_cast<int *>(at + words);
-    w.bucket = reinterpret_cast<int *>(at + 2 * words);
-    w.list = reinterpret_cast<int *>(at + 3 * words);
-    w.listed = reinterpret_cast<int *>(at + 4 * words);
+    const Work w = boxes_work(B, max_rows, workspace);
     const Cols col{ld, cx, cy, cz};
     const Out out{center, size, yaw, lo, hi, angle, n, reinterpret_cast<long long *>(score)};
     const float4 *table = reinterpret_cast<const float4 *>(angles);

@@ -56,7 +56,19 @@ Plan make_plan(int B, int N, int M) {
     return p;
 }
 
-inline int64_t partial_bytes(const Plan &p) { return (p.partials * 8 + 255) & ~(int64_t)255; }
+// The workspace: the fp64 partials (rounded to 256 bytes); with split candidates each query's best pair per range, the distances
+// then the indices back to back.
+struct Work {
+    double *partials;
+    float *part_d2;
+    int *part_idx;
+    int64_t bytes;
+};
+Work chamfer_work(const Plan &p, int B, int N, void *base) {
+    Pn2Arena a(base);
+    const int64_t pairs = p.splits > 1 ? (int64_t)B * N * p.splits : 0;        // (nothing taken, both null, without a join)
+    return {a.take<double>(p.partials, 256), pairs ? a.take<float>(pairs, 4) : nullptr, pairs ? a.take<int>(pairs, 4) : nullptr, a.bytes()};
+}
 
 // Sum of `v` over the workgroup in a fixed shape (xor-shuffle tree, then the four waves in order); valid in thread 0.
 __device__ __forceinline__ double block_sum_f64(double v) {
@@ -236,8 +248,7 @@ extern "C" {
 
 int64_t pn2_chamfer_nn_workspace_bytes(int B, int N, int M, int D) {
     if (B <= 0 || N <= 0 || M <= 0 || D <= 0 || D > kMaxD) return 0;
-    const Plan p = make_plan(B, N, M);
-    return partial_bytes(p) + (p.splits > 1 ? (int64_t)B * N * p.splits * 8 : 0);
+    return chamfer_work(make_plan(B, N, M), B, N, nullptr).bytes;
 }
 
 int pn2_chamfer_nn(const float *p1, const float *p2, int B, int N, int M, int D, float *dist, int64_t *idx, float *sum,
@@ -246,15 +257,13 @@ int pn2_chamfer_nn(const float *p1, const float *p2, int B, int N, int M, int D,
     PN2_CHECK_ARG((int64_t)B * N < (int64_t)1 << 31 && (int64_t)N * D < (int64_t)1 << 31 && (int64_t)M * D < (int64_t)1 << 31);
     if (D > kMaxD) return PN2_EUNSUPPORTED;
     const Plan p = make_plan(B, N, M);
-    double *partials = reinterpret_cast<double *>(workspace);
-    float *part_d2 = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + partial_bytes(p));
-    int *part_idx = reinterpret_cast<int *>(part_d2 + (size_t)B * N * p.splits);
-    double *want = sum ? partials : nullptr;
+    const Work w = chamfer_work(p, B, N, workspace);
+    double *want = sum ? w.partials : nullptr;
     hipStream_t s = pn2_s(stream);
 #define PN2_CHAMFER_CASE(DD)                                                                                              \
     case DD:                                                                                                              \
-        if (p.qpt == 4) launch_nn<DD, 4>(p, p1, p2, B, N, M, dist, idx, part_d2, part_idx, want, s);                      \
-        else launch_nn<DD, 1>(p, p1, p2, B, N, M, dist, idx, part_d2, part_idx, want, s);                                 \
+        if (p.qpt == 4) launch_nn<DD, 4>(p, p1, p2, B, N, M, dist, idx, w.part_d2, w.part_idx, want, s);                      \
+        else launch_nn<DD, 1>(p, p1, p2, B, N, M, dist, idx, w.part_d2, w.part_idx, want, s);                                 \
         break;
     switch (D) {
         PN2_CHAMFER_CASE(1) PN2_CHAMFER_CASE(2) PN2_CHAMFER_CASE(3) PN2_CHAMFER_CASE(4) PN2_CHAMFER_CASE(5) PN2_CHAMFER_CASE(6)
@@ -264,9 +273,9 @@ int pn2_chamfer_nn(const float *p1, const float *p2, int B, int N, int M, int D,
     }
 #undef PN2_CHAMFER_CASE
     if (p.splits > 1)
-        hipLaunchKernelGGL(chamfer_join_kernel, dim3((unsigned)p.partials), dim3(kThreads), 0, s, part_d2, part_idx, (int64_t)B * N,
+        hipLaunchKernelGGL(chamfer_join_kernel, dim3((unsigned)p.partials), dim3(kThreads), 0, s, w.part_d2, w.part_idx, (int64_t)B * N,
                            p.splits, dist, idx, want);
-    if (sum) hipLaunchKernelGGL(chamfer_sum_kernel, dim3(1), dim3(kThreads), 0, s, partials, p.partials, B, sum);
+    if (sum) hipLaunchKernelGGL(chamfer_sum_kernel, dim3(1), dim3(kThreads), 0, s, w.partials, p.partials, B, sum);
     return pn2_launch_status();
 }
 

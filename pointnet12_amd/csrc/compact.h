@@ -22,19 +22,18 @@ constexpr int kCompactSegments = kCompactRounds * kCompactWaves;    // 64-row se
 static_assert(kCompactTile % kCompactThreads == 0 && kCompactThreads % PN2_WAVE == 0, "a tile is a whole number of workgroup rounds");
 
 // The compaction's part of a workspace: a flag per row of every tile, a count and an offset per tile (each 16-byte aligned when
-// the base is).
+// the base is), taken from the caller's arena.
 struct Pn2Compact {
+    unsigned char *flags;
+    int *tile_count, *tile_offset;
     int tiles;                                                      // per cloud
-    int64_t flag_bytes, word_bytes;
-    Pn2Compact(int B, int64_t max_rows) : tiles(max_rows == 0 ? 1 : (int)pn2_cdiv(max_rows, kCompactTile)) {
-        flag_bytes = (int64_t)B * tiles * kCompactTile;
-        word_bytes = pn2_round16((int64_t)B * tiles * (int64_t)sizeof(int));
-    }
-    int64_t bytes() const { return flag_bytes + 2 * word_bytes; }
-    unsigned char *flags(void *base) const { return static_cast<unsigned char *>(base); }
-    int *tile_count(void *base) const { return reinterpret_cast<int *>(flags(base) + flag_bytes); }
-    int *tile_offset(void *base) const { return reinterpret_cast<int *>(flags(base) + flag_bytes + word_bytes); }
 };
+static inline int pn2_compact_tiles(int64_t max_rows) { return max_rows == 0 ? 1 : (int)pn2_cdiv(max_rows, kCompactTile); }
+static inline Pn2Compact pn2_compact_take(Pn2Arena &a, int B, int64_t max_rows) {
+    const int tiles = pn2_compact_tiles(max_rows);
+    const int64_t n = (int64_t)B * tiles;
+    return {a.take<unsigned char>(n * kCompactTile), a.take<int>(n), a.take<int>(n), tiles};
+}
 
 // How many of a tile's kCompactTile rows satisfy pred(i), i = round * kCompactThreads + thread: a ballot and a popcount per wave and
 // round, the wave totals summed through LDS, one store of the count.  Holds one barrier.

@@ -299,25 +299,15 @@ __global__ __launch_bounds__(kThreads) void corr_finish_kernel(int tiles, int fl
     for (int e = 0; e < 12; ++e) T[(int64_t)b * 12 + e] = R[e];
 }
 
-struct CorrWork {
+struct CorrWork {                   // (the refit's part comes first: where it lies does not depend on H)
     double *partial, *hyp;          // [B,row tiles,17]; [B,H,12]
     int32_t *score;                 // [B,score tiles,H]
     int64_t bytes;
 };
 
-// (the refit's part comes first: where it lies does not depend on H)
-CorrWork corr_carve(int B, int64_t N, int H, void *base) {
-    char *p = static_cast<char *>(base);
-    CorrWork w;
-    int64_t at = 0;
-    w.partial = reinterpret_cast<double *>(p + at);
-    at += pn2_round16((int64_t)B * pn2_cdiv(N, kSumTile) * kSums * (int64_t)sizeof(double));
-    w.hyp = reinterpret_cast<double *>(p + at);
-    at += pn2_round16((int64_t)B * H * 12 * (int64_t)sizeof(double));
-    w.score = reinterpret_cast<int32_t *>(p + at);
-    at += pn2_round16((int64_t)B * pn2_cdiv(N, kScoreTile) * H * (int64_t)sizeof(int32_t));
-    w.bytes = at;
-    return w;
+CorrWork corr_work(int B, int64_t N, int H, void *base) {
+    Pn2Arena a(base);
+    return {a.take<double>(B * pn2_cdiv(N, kSumTile) * kSums), a.take<double>((int64_t)B * H * 12), a.take<int32_t>(B * pn2_cdiv(N, kScoreTile) * H), a.bytes()};
 }
 
 bool corr_clouds_ok(const float *src, int lds, const float *tgt, int ldt, int B, int N, int M, const int64_t *pair_src, const int64_t *pair_tgt,
@@ -333,7 +323,7 @@ extern "C" {
 
 int64_t pn2_corr_workspace_bytes(int B, int N, int H) {
     if (!pn2_cloud_shape_ok(B, N) || H < 1 || H > 65536) return PN2_EINVAL;
-    return corr_carve(B, N, H, nullptr).bytes;
+    return corr_work(B, N, H, nullptr).bytes;
 }
 
 int pn2_corr_ransac(const float *src, int lds, const float *tgt, int ldt, int B, int N, int M, const int64_t *pair_src, const int64_t *pair_tgt,
@@ -343,7 +333,7 @@ int pn2_corr_ransac(const float *src, int lds, const float *tgt, int ldt, int B,
     PN2_CHECK_ARG(T && best_h && best_count && status && workspace && H >= 1 && H <= 65536 && edge_ratio >= 0.0 && edge_ratio <= 1.0);
     PN2_CHECK_ARG(pn2_aligned(T, 8) && pn2_aligned(hyp_T, 8) && pn2_aligned(hyp_count, 4) && pn2_aligned(best_h, 4) && pn2_aligned(best_count, 8) &&
                   pn2_aligned(status, 4) && pn2_aligned(err, 4) && pn2_aligned(workspace, 16));
-    const CorrWork w = corr_carve(B, N, H, workspace);
+    const CorrWork w = corr_work(B, N, H, workspace);
     double *hyp = hyp_T != nullptr ? hyp_T : w.hyp;
     const int tiles = (int)pn2_cdiv(N, kScoreTile), hblocks = (int)pn2_cdiv(H, kThreads);
     const hipStream_t s = pn2_s(stream);
@@ -363,7 +353,7 @@ int pn2_corr_refit(const float *src, int lds, const float *tgt, int ldt, int B, 
     PN2_CHECK_ARG(T && inliers && rmse && sums && status && workspace && (flags & ~PN2_CORR_EVAL_ONLY) == 0);
     PN2_CHECK_ARG(pn2_aligned(T, 8) && pn2_aligned(inliers, 8) && pn2_aligned(rmse, 8) && pn2_aligned(sums, 8) && pn2_aligned(status, 4) &&
                   pn2_aligned(workspace, 16));
-    const CorrWork w = corr_carve(B, N, 1, workspace);
+    const CorrWork w = corr_work(B, N, 1, workspace);
     const int tiles = (int)pn2_cdiv(N, kSumTile);
     const hipStream_t s = pn2_s(stream);
     hipLaunchKernelGGL(corr_accumulate_kernel, dim3((unsigned)tiles, (unsigned)B), dim3(kThreads), 0, s, src, lds, tgt, ldt, N, M, pair_src, pair_tgt,

@@ -168,19 +168,13 @@ __global__ __launch_bounds__(kCompactThreads) void match_write_kernel(const int6
 
 struct MatchWork {
     int64_t *rows;                  // [B]
-    void *compact;
+    Pn2Compact compact;
     int64_t bytes;
 };
 
-MatchWork match_carve(int B, int64_t N, void *base) {
-    char *p = static_cast<char *>(base);
-    MatchWork w;
-    w.rows = reinterpret_cast<int64_t *>(p);
-    int64_t at = pn2_round16((int64_t)B * (int64_t)sizeof(int64_t));
-    w.compact = p + at;
-    at += pn2_round16(Pn2Compact(B, N).bytes());
-    w.bytes = at;
-    return w;
+MatchWork match_work(int B, int64_t N, void *base) {
+    Pn2Arena a(base);
+    return {a.take<int64_t>(B), pn2_compact_take(a, B, N), a.bytes()};
 }
 
 }  // namespace
@@ -204,7 +198,7 @@ int pn2_feature_nn2(const float *query, int ldq, const float *cand, int ldc, int
 
 int64_t pn2_match_pairs_workspace_bytes(int B, int N) {
     if (!pn2_cloud_shape_ok(B, N)) return PN2_EINVAL;
-    return match_carve(B, N, nullptr).bytes;
+    return match_work(B, N, nullptr).bytes;
 }
 
 int pn2_match_pairs(const int64_t *idx, const float *dist, const int64_t *back, int B, int N, int M, float ratio2, const int64_t *n_query,
@@ -213,17 +207,17 @@ int pn2_match_pairs(const int64_t *idx, const float *dist, const int64_t *back, 
     PN2_CHECK_ARG(pn2_cloud_shape_ok(B, N) && pn2_cloud_shape_ok(B, M) && ratio2 >= 0.f);                  // (a NaN ratio2 fails the compare)
     PN2_CHECK_ARG(pn2_aligned(idx, 8) && pn2_aligned(dist, 4) && pn2_aligned(back, 8) && pn2_aligned(n_query, 8) && pn2_aligned(pair_src, 8) &&
                   pn2_aligned(pair_tgt, 8) && pn2_aligned(count, 8) && pn2_aligned(workspace, 16));
-    const MatchWork w = match_carve(B, N, workspace);
-    const Pn2Compact ws(B, N);
+    const MatchWork w = match_work(B, N, workspace);
+    const Pn2Compact &c = w.compact;
     const hipStream_t s = pn2_s(stream);
-    const dim3 grid((unsigned)ws.tiles, (unsigned)B);
+    const dim3 grid((unsigned)c.tiles, (unsigned)B);
     hipLaunchKernelGGL(match_rows_kernel, dim3((unsigned)pn2_cdiv(B, 256)), dim3(256), 0, s, n_query, B, N, w.rows);
-    hipLaunchKernelGGL(match_flag_kernel, grid, dim3(kCompactThreads), 0, s, idx, dist, back, N, M, ratio2, w.rows, ws.flags(w.compact),
-                       ws.tile_count(w.compact), ws.tiles);
-    hipLaunchKernelGGL(pn2_compact_offsets_kernel, dim3((unsigned)B), dim3(PN2_WAVE), 0, s, w.rows, N, ws.tile_count(w.compact),
-                       ws.tile_offset(w.compact), ws.tiles, count, (int *)nullptr, 0);
-    hipLaunchKernelGGL(match_write_kernel, grid, dim3(kCompactThreads), 0, s, idx, N, w.rows, ws.flags(w.compact), ws.tile_offset(w.compact),
-                       ws.tiles, pair_src, pair_tgt);
+    hipLaunchKernelGGL(match_flag_kernel, grid, dim3(kCompactThreads), 0, s, idx, dist, back, N, M, ratio2, w.rows, c.flags, c.tile_count,
+                       c.tiles);
+    hipLaunchKernelGGL(pn2_compact_offsets_kernel, dim3((unsigned)B), dim3(PN2_WAVE), 0, s, w.rows, N, c.tile_count, c.tile_offset, c.tiles,
+                       count, (int *)nullptr, 0);
+    hipLaunchKernelGGL(match_write_kernel, grid, dim3(kCompactThreads), 0, s, idx, N, w.rows, c.flags, c.tile_offset, c.tiles, pair_src,
+                       pair_tgt);
     return pn2_launch_status();
 }
 

@@ -169,7 +169,11 @@ int launch_grid_knn(const float *query, int ldq, int B, int N, int M, int K, flo
 
 extern "C" {
 
-int64_t pn2_grid_workspace_bytes(int B, int64_t M) { return grid_shape_ok(B, M) ? Carve(B, M).bytes() : PN2_EINVAL; }
+int64_t pn2_grid_workspace_bytes(int B, int64_t M) {
+    int64_t bytes = PN2_EINVAL;
+    if (grid_shape_ok(B, M)) grid_work(B, M, nullptr, &bytes);
+    return bytes;
+}
 
 int pn2_grid_build(const float *cand, int ldc, int B, int M, const int64_t *n_cand, const double *origin, const double *cell, int32_t *err,
                    void *workspace, pn2_stream_t stream) {
@@ -178,11 +182,10 @@ int pn2_grid_build(const float *cand, int ldc, int B, int M, const int64_t *n_ca
     PN2_CHECK_ARG(pn2_aligned(cand, 4) && pn2_aligned(workspace, 16));
     Grid grid;
     PN2_CHECK_ARG(pn2_grid_from(origin, cell, grid));
-    const Carve ws(B, M);
-    const Work w = carve(ws, workspace);
+    const Work w = grid_work(B, M, workspace);
     const hipStream_t s = pn2_s(stream);
     const dim3 by_row((unsigned)pn2_cdiv(M, kThreads), (unsigned)B), by_tile((unsigned)w.tiles, (unsigned)B);
-    hipLaunchKernelGGL(grid_clear_kernel, dim3(pn2_slot_clear_blocks(ws.cap), (unsigned)B), dim3(kThreads), 0, s, n_cand, M, w);
+    hipLaunchKernelGGL(grid_clear_kernel, dim3(pn2_slot_clear_blocks(w.cap), (unsigned)B), dim3(kThreads), 0, s, n_cand, M, w);
     hipLaunchKernelGGL(grid_count_kernel, by_row, dim3(kThreads), 0, s, cand, ldc, M, n_cand, grid, w, err);
     hipLaunchKernelGGL(grid_tile_kernel, by_tile, dim3(kThreads), 0, s, w);
     hipLaunchKernelGGL(grid_offsets_kernel, dim3((unsigned)B), dim3(PN2_WAVE), 0, s, w);
@@ -202,7 +205,7 @@ int pn2_grid_knn(const float *query, int ldq, int B, int N, int M, int K, float 
     Grid grid;
     PN2_CHECK_ARG(pn2_grid_from(origin, cell, grid));
     if (K > 32) return PN2_EUNSUPPORTED;
-    const Work w = carve(Carve(B, M), const_cast<void *>(workspace));      // (the query kernel only reads it)
+    const Work w = grid_work(B, M, const_cast<void *>(workspace));      // (the query kernel only reads it)
     const int sorted = query == nullptr && (flags & PN2_GRID_VISIT_SORTED) != 0;
     const hipStream_t s = pn2_s(stream);
     if (K <= 4) return launch_grid_knn<4>(query, ldq, B, N, M, K, max_d2, n_query, grid, w, sorted, idx, dist, count, err, s);

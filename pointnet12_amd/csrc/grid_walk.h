@@ -29,19 +29,6 @@ struct alignas(16) Head {                                           // per cloud
     int unused;
 };
 
-// The workspace: the tables, the records, a word per row, two words per tile of slots, a header per cloud.
-struct Carve {
-    int64_t cap, tiles, table_bytes, rec_bytes, row_bytes, tile_bytes, head_bytes;
-    Carve(int B, int64_t M) : cap(pn2_slot_capacity(M)), tiles(pn2_cdiv(pn2_slot_capacity(M), kTile)) {
-        table_bytes = (int64_t)B * cap * (int64_t)sizeof(Slot);
-        rec_bytes = (int64_t)B * M * (int64_t)sizeof(float4);
-        row_bytes = pn2_round16((int64_t)B * M * (int64_t)sizeof(int));
-        tile_bytes = pn2_round16((int64_t)B * tiles * (int64_t)sizeof(int));
-        head_bytes = (int64_t)B * (int64_t)sizeof(Head);
-    }
-    int64_t bytes() const { return table_bytes + rec_bytes + row_bytes + 2 * tile_bytes + head_bytes; }
-};
-
 struct Work {
     Slot *table;
     float4 *rec;
@@ -52,21 +39,13 @@ struct Work {
     int tiles;                                                      // per cloud
 };
 
-Work carve(const Carve &ws, void *workspace) {
-    Work w;
-    unsigned char *at = static_cast<unsigned char *>(workspace);
-    w.table = reinterpret_cast<Slot *>(at);
-    at += ws.table_bytes;
-    w.rec = reinterpret_cast<float4 *>(at);
-    at += ws.rec_bytes;
-    w.row_word = reinterpret_cast<int *>(at);
-    at += ws.row_bytes;
-    w.tile_sum = reinterpret_cast<int *>(at);
-    w.tile_start = reinterpret_cast<int *>(at + ws.tile_bytes);
-    at += 2 * ws.tile_bytes;
-    w.head = reinterpret_cast<Head *>(at);
-    w.cap = (unsigned)ws.cap;
-    w.tiles = (int)ws.tiles;
+// The workspace: the tables, the records, a word per row, two words per tile of slots, a header per cloud.
+Work grid_work(int B, int64_t M, void *base, int64_t *bytes = nullptr) {
+    Pn2Arena a(base);
+    const int64_t cap = pn2_slot_capacity(M), tiles = pn2_cdiv(cap, kTile);
+    const Work w{a.take<Slot>(B * cap),   a.take<float4>(B * M), a.take<int>(B * M), a.take<int>(B * tiles),
+                 a.take<int>(B * tiles), a.take<Head>(B),       (unsigned)cap,      (int)tiles};
+    if (bytes != nullptr) *bytes = a.bytes();
     return w;
 }
 

@@ -232,7 +232,7 @@ int pn2_icp_step(const float *src, int lds, int B, int N, const int64_t *n_src, 
     PN2_CHECK_ARG(pn2_aligned(n_src, 8) && pn2_aligned(status, 4) && pn2_aligned(iters, 4) && pn2_aligned(err, 4) && pn2_aligned(workspace, 8));
     Grid grid;
     PN2_CHECK_ARG(pn2_grid_from(origin, cell, grid));
-    const Work w = carve(Carve(B, M), const_cast<void *>(grid_workspace));         // (only read)
+    const Work w = grid_work(B, M, const_cast<void *>(grid_workspace));         // (only read)
     const int tiles = (int)pn2_cdiv(N, kSumTile);
     double *partial = static_cast<double *>(workspace);
     const hipStream_t s = pn2_s(stream);

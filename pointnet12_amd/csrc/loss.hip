@@ -367,6 +367,18 @@ void ce_launch_bwd(const CeArgs &a, const float *logsum, const float *grad_out, 
         }                                                                                                         \
     } while (0)
 
+// The workspace of a reduced forward (NLL and cross-entropy alike): the workgroups' fp64 partials, numerators then denominators
+// (gridDim.x <= kMaxBlocks of each), and the ticket word.
+struct LossWork {
+    double *partial;
+    unsigned *ticket;
+    int64_t bytes;
+};
+LossWork loss_work(void *base) {
+    Pn2Arena a(base);
+    return {a.take<double>(2 * kMaxBlocks), a.take<unsigned>(1), a.bytes()};
+}
+
 }  // namespace
 
 extern "C" {
@@ -387,18 +399,17 @@ int pn2_log_softmax_bwd(const float *grad_out, int ldg, const float *out, int ld
 
 int64_t pn2_nll_loss_workspace_bytes(int64_t R) {
     (void)R;
-    return (int64_t)(2 * 1024 * sizeof(double) + 16);
+    return loss_work(nullptr).bytes;
 }
 
 int pn2_nll_loss_fwd(const float *logp, int ld, const int64_t *target, const float *weight, int64_t R, int C,
                      int64_t ignore_index, void *workspace, float *loss, float *denom, pn2_stream_t stream) {
     PN2_CHECK_ARG(logp && target && workspace && loss && denom && R > 0 && C > 0 && ld >= C);
     int64_t blocks = pn2_cdiv(R, kThreads);
-    if (blocks > 1024) blocks = 1024;
-    double *ws = reinterpret_cast<double *>(workspace);
-    unsigned *ticket = reinterpret_cast<unsigned *>(ws + 2 * 1024);
+    if (blocks > kMaxBlocks) blocks = kMaxBlocks;
+    const LossWork w = loss_work(workspace);
     hipLaunchKernelGGL(nll_fwd_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, pn2_s(stream), logp, ld, target, weight, R, C,
-                       ignore_index, ws, ticket, loss, denom);
+                       ignore_index, w.partial, w.ticket, loss, denom);
     return pn2_launch_status();
 }
 
@@ -413,7 +424,7 @@ int pn2_nll_loss_bwd(const int64_t *target, const float *weight, int64_t R, int 
 
 int64_t pn2_cross_entropy_workspace_bytes(int64_t R) {
     if (R <= 0) return PN2_EINVAL;
-    return (int64_t)(2 * kMaxBlocks * sizeof(double) + 16);
+    return loss_work(nullptr).bytes;
 }
 
 int pn2_cross_entropy_fwd(const float *x, int ld, int64_t inner, const int64_t *target, const float *weight, int64_t R, int C,
@@ -423,10 +434,9 @@ int pn2_cross_entropy_fwd(const float *x, int ld, int64_t inner, const int64_t *
     PN2_CHECK_ARG(ce_check(a) == PN2_OK && logsum && loss && (reduction == kReduceNone || (workspace && denom)));
     int64_t blocks = pn2_cdiv(R, kThreads);
     if (blocks > kMaxBlocks) blocks = kMaxBlocks;
-    double *ws = reinterpret_cast<double *>(workspace);
-    unsigned *ticket = reinterpret_cast<unsigned *>(ws + 2 * kMaxBlocks);
+    const LossWork w = loss_work(workspace);                             // (null parts without a workspace: kReduceNone reads neither)
     const int mode = ce_mode(x, nullptr, ld, inner);
-    PN2_CE_DISPATCH(C, mode, ce_launch_fwd, a, (unsigned)blocks, ws, ticket, logsum, loss, denom, pn2_s(stream));
+    PN2_CE_DISPATCH(C, mode, ce_launch_fwd, a, (unsigned)blocks, w.partial, w.ticket, logsum, loss, denom, pn2_s(stream));
     return pn2_launch_status();
 }
 

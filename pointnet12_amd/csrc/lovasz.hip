@@ -31,24 +31,23 @@ constexpr int kMaxClasses = 64;
 constexpr unsigned kKeyAbsent = 0xFFFFFFFFu;      // a row that takes no part: after every real key (real keys are <= 0x7FFFFFFF)
 constexpr unsigned kFgBit = 0x80000000u, kNegBit = 0x40000000u, kRowMask = 0x3FFFFFFFu;
 
-struct Layout {                                   // the parts of the workspace, each 16-byte aligned when the base is
-    int64_t N, S, nt, key_bytes, hist_bytes, tot_bytes, tile_bytes, g_bytes, part_bytes, seg_bytes, bad_blocks, bad_bytes;
-    Layout(int64_t R, int C, int images) {
-        N = R / images;
-        S = (int64_t)images * C;
-        nt = pn2_cdiv(N, kCompactTile);
-        key_bytes = pn2_round16(S * N * 4);
-        hist_bytes = pn2_round16(S * kRadix * nt * 4);
-        tot_bytes = pn2_round16(S * kRadix * 4);
-        tile_bytes = pn2_round16(S * nt * 4);
-        g_bytes = pn2_round16(S * 4);
-        part_bytes = pn2_round16(S * nt * 8);
-        seg_bytes = pn2_round16(S * 8);
-        bad_blocks = pn2_cdiv(R, kThreads);
-        bad_bytes = pn2_round16(bad_blocks * 4);
-    }
-    int64_t bytes() const { return 4 * key_bytes + hist_bytes + tot_bytes + tile_bytes + g_bytes + part_bytes + seg_bytes + bad_bytes; }
+struct Work {                                     // the shape's counts and the parts of the workspace, each 16-byte aligned when the base is
+    int64_t N, S, nt, bad_blocks;                 // rows per image, segments, tiles per segment, workgroups of the key pass
+    unsigned *key[2], *pay[2];
+    int *hist, *totals, *tile_fg, *G;
+    double *partial, *seg_loss;
+    int *bad;
+    int64_t bytes;
 };
+
+Work lovasz_work(int64_t R, int C, int images, void *base) {
+    Pn2Arena a(base);
+    const int64_t N = R / images, S = (int64_t)images * C, nt = pn2_cdiv(N, kCompactTile), bad_blocks = pn2_cdiv(R, kThreads);
+    return {N, S, nt, bad_blocks,
+            {a.take<unsigned>(S * N), a.take<unsigned>(S * N)}, {a.take<unsigned>(S * N), a.take<unsigned>(S * N)},
+            a.take<int>(S * kRadix * nt), a.take<int>(S * kRadix), a.take<int>(S * nt), a.take<int>(S),
+            a.take<double>(S * nt), a.take<double>(S), a.take<int>(bad_blocks), a.bytes()};
+}
 
 // ------------------------------------------------------------------------------------------------------------------ key pass
 // p of a row exactly as pn2_cross_entropy_bwd recomputes it (softmax_row.h): expf((x - max) - logf(sum))
@@ -345,7 +344,7 @@ __global__ __launch_bounds__(kThreads) void bwd_kernel(const float *__restrict__
 int check_shape(int64_t R, int C, int images) {
     PN2_CHECK_ARG(R > 0 && C > 0 && C <= kMaxClasses && images > 0 && R % images == 0);
     PN2_CHECK_ARG(R / images <= (int64_t)kRowMask && R * C < (1LL << 36) && pn2_cdiv(R, kThreads) < (1LL << 31));
-    const Layout L(R, C, images);
+    const Work L = lovasz_work(R, C, images, nullptr);
     PN2_CHECK_ARG(L.S * L.nt < (1LL << 31) && L.S * kRadix < (1LL << 31));
     return PN2_OK;
 }
@@ -364,7 +363,7 @@ int pn2_lovasz_tile_rows(void) { return kCompactTile; }
 
 int64_t pn2_lovasz_workspace_bytes(int64_t R, int C, int images) {
     if (check_shape(R, C, images) != PN2_OK) return PN2_EINVAL;
-    return Layout(R, C, images).bytes();
+    return lovasz_work(R, C, images, nullptr).bytes;
 }
 
 int pn2_lovasz_fwd(const float *x, int ld, int64_t inner, const int64_t *target, int64_t R, int C, int images, int64_t ignore_index,
@@ -374,41 +373,27 @@ int pn2_lovasz_fwd(const float *x, int ld, int64_t inner, const int64_t *target,
     PN2_CHECK_ARG(pn2_aligned(workspace, 16) && pn2_aligned(x, 4) && pn2_aligned(dp, 4) && pn2_aligned(prob, 4) && pn2_aligned(loss, 4) &&
                   pn2_aligned(target, 8) && pn2_aligned(class_mask, 4));
     PN2_CHECK_ARG(images == 1 || inner == 0 || inner == R / images);     // class-strided: an image is one [C, inner] block
-    const Layout L(R, C, images);
+    const Work L = lovasz_work(R, C, images, workspace);
     hipStream_t s = pn2_s(stream);
-    char *at = static_cast<char *>(workspace);
-    auto take = [&at](int64_t bytes) { char *p = at; at += bytes; return p; };
-    unsigned *key[2], *pay[2];
-    key[0] = reinterpret_cast<unsigned *>(take(L.key_bytes));
-    key[1] = reinterpret_cast<unsigned *>(take(L.key_bytes));
-    pay[0] = reinterpret_cast<unsigned *>(take(L.key_bytes));
-    pay[1] = reinterpret_cast<unsigned *>(take(L.key_bytes));
-    int *hist = reinterpret_cast<int *>(take(L.hist_bytes));
-    int *totals = reinterpret_cast<int *>(take(L.tot_bytes));
-    int *tile_fg = reinterpret_cast<int *>(take(L.tile_bytes));
-    int *G = reinterpret_cast<int *>(take(L.g_bytes));
-    double *partial = reinterpret_cast<double *>(take(L.part_bytes));
-    double *seg_loss = reinterpret_cast<double *>(take(L.seg_bytes));
-    int *bad = reinterpret_cast<int *>(take(L.bad_bytes));
     const int nt = (int)L.nt;
     const dim3 rows((unsigned)L.bad_blocks), tiles((unsigned)(L.S * L.nt)), block(kThreads);
 #define PN2_LOVASZ_KEY(KC)                                                                                                          \
-    hipLaunchKernelGGL(key_kernel<KC>, rows, block, 0, s, x, ld, inner, target, R, C, L.N, ignore_index, from_logits, key[0], pay[0], prob, bad)
+    hipLaunchKernelGGL(key_kernel<KC>, rows, block, 0, s, x, ld, inner, target, R, C, L.N, ignore_index, from_logits, L.key[0], L.pay[0], prob, L.bad)
     if (C <= 16) PN2_LOVASZ_KEY(16);
     else if (C <= 32) PN2_LOVASZ_KEY(32);
     else PN2_LOVASZ_KEY(64);
 #undef PN2_LOVASZ_KEY
     for (int pass = 0; pass < 4; ++pass) {                               // 4 x 8 bits: the last pass leaves the result in key[0] / pay[0]
         const int in = pass & 1, out = in ^ 1, shift = 8 * pass;
-        hipLaunchKernelGGL(hist_kernel, tiles, block, 0, s, key[in], hist, L.N, nt, shift);
-        hipLaunchKernelGGL(row_scan_kernel, dim3((unsigned)pn2_cdiv(L.S * kRadix, kWaves)), block, 0, s, hist, totals, L.S * kRadix, nt);
-        hipLaunchKernelGGL(scatter_kernel, tiles, block, 0, s, key[in], pay[in], key[out], pay[out], hist, totals, L.N, nt, shift);
+        hipLaunchKernelGGL(hist_kernel, tiles, block, 0, s, L.key[in], L.hist, L.N, nt, shift);
+        hipLaunchKernelGGL(row_scan_kernel, dim3((unsigned)pn2_cdiv(L.S * kRadix, kWaves)), block, 0, s, L.hist, L.totals, L.S * kRadix, nt);
+        hipLaunchKernelGGL(scatter_kernel, tiles, block, 0, s, L.key[in], L.pay[in], L.key[out], L.pay[out], L.hist, L.totals, L.N, nt, shift);
     }
-    hipLaunchKernelGGL(fg_count_kernel, tiles, block, 0, s, pay[0], tile_fg, L.N, nt);
-    hipLaunchKernelGGL(row_scan_kernel, dim3((unsigned)pn2_cdiv(L.S, kWaves)), block, 0, s, tile_fg, G, L.S, nt);
-    hipLaunchKernelGGL(finalise_kernel, tiles, block, 0, s, key[0], pay[0], tile_fg, G, L.N, nt, C, images, class_mask, present_only, dp,
-                       partial);
-    hipLaunchKernelGGL(reduce_kernel, dim3(1), block, 0, s, partial, seg_loss, G, nt, C, images, class_mask, present_only, bad,
+    hipLaunchKernelGGL(fg_count_kernel, tiles, block, 0, s, L.pay[0], L.tile_fg, L.N, nt);
+    hipLaunchKernelGGL(row_scan_kernel, dim3((unsigned)pn2_cdiv(L.S, kWaves)), block, 0, s, L.tile_fg, L.G, L.S, nt);
+    hipLaunchKernelGGL(finalise_kernel, tiles, block, 0, s, L.key[0], L.pay[0], L.tile_fg, L.G, L.N, nt, C, images, class_mask, present_only, dp,
+                       L.partial);
+    hipLaunchKernelGGL(reduce_kernel, dim3(1), block, 0, s, L.partial, L.seg_loss, L.G, nt, C, images, class_mask, present_only, L.bad,
                        L.bad_blocks, loss);
     return pn2_launch_status();
 }

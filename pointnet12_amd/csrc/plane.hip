@@ -312,27 +312,18 @@ bool plane_axis(const double *axis, Axis &a) {
     return true;
 }
 
-struct PlaneWork {
-    double *partial, *hyp;          // [B,row tiles,10]; [B,H,4]
-    int32_t *rows, *score;          // [B,row tiles]; [B,score tiles,H]
+struct PlaneWork {                  // (the refit's and the classification's parts come first: where they lie does not depend on H)
+    double *partial;                // [B,row tiles,10]
+    int32_t *rows;                  // [B,row tiles]
+    double *hyp;                    // [B,H,4]
+    int32_t *score;                 // [B,score tiles,H]
     int64_t bytes;
 };
 
-// (the refit's and the classification's parts come first: where they lie does not depend on H)
-PlaneWork plane_carve(int B, int64_t N, int H, void *base) {
-    char *p = static_cast<char *>(base);
-    PlaneWork w;
-    int64_t at = 0;
-    w.partial = reinterpret_cast<double *>(p + at);
-    at += pn2_round16((int64_t)B * pn2_cdiv(N, kSumTile) * kSums * (int64_t)sizeof(double));
-    w.rows = reinterpret_cast<int32_t *>(p + at);
-    at += pn2_round16((int64_t)B * pn2_cdiv(N, kSumTile) * (int64_t)sizeof(int32_t));
-    w.hyp = reinterpret_cast<double *>(p + at);
-    at += pn2_round16((int64_t)B * H * 4 * (int64_t)sizeof(double));
-    w.score = reinterpret_cast<int32_t *>(p + at);
-    at += pn2_round16((int64_t)B * pn2_cdiv(N, kScoreTile) * H * (int64_t)sizeof(int32_t));
-    w.bytes = at;
-    return w;
+PlaneWork plane_work(int B, int64_t N, int H, void *base) {
+    Pn2Arena a(base);
+    const int64_t sum_tiles = B * pn2_cdiv(N, kSumTile), score_tiles = B * pn2_cdiv(N, kScoreTile);
+    return {a.take<double>(sum_tiles * kSums), a.take<int32_t>(sum_tiles), a.take<double>((int64_t)B * H * 4), a.take<int32_t>(score_tiles * H), a.bytes()};
 }
 
 }  // namespace
@@ -341,7 +332,7 @@ extern "C" {
 
 int64_t pn2_plane_workspace_bytes(int B, int N, int H) {
     if (!pn2_cloud_shape_ok(B, N) || H < 1 || H > 65536) return PN2_EINVAL;
-    return plane_carve(B, N, H, nullptr).bytes;
+    return plane_work(B, N, H, nullptr).bytes;
 }
 
 int pn2_plane_ransac(const float *pts, int ld, int B, int N, const int64_t *n_points, const int32_t *assign, int H, uint64_t seed,
@@ -354,7 +345,7 @@ int pn2_plane_ransac(const float *pts, int ld, int B, int N, const int64_t *n_po
     PN2_CHECK_ARG(plane_axis(axis, a));
     PN2_CHECK_ARG(pn2_aligned(pts, 4) && pn2_aligned(assign, 4) && pn2_aligned(n_points, 8) && pn2_aligned(plane, 8) && pn2_aligned(hyp_count, 4));
     PN2_CHECK_ARG(pn2_aligned(best_h, 4) && pn2_aligned(best_count, 8) && pn2_aligned(status, 4) && pn2_aligned(err, 4) && pn2_aligned(workspace, 16));
-    const PlaneWork w = plane_carve(B, N, H, workspace);
+    const PlaneWork w = plane_work(B, N, H, workspace);
     const int tiles = (int)pn2_cdiv(N, kScoreTile), hblocks = (int)pn2_cdiv(H, kThreads);
     PN2_CHECK_ARG(hblocks <= 65535);
     const hipStream_t s = pn2_s(stream);
@@ -376,7 +367,7 @@ int pn2_plane_refit(const float *pts, int ld, int B, int N, const int64_t *n_poi
     PN2_CHECK_ARG(plane_axis(axis, a));
     PN2_CHECK_ARG(pn2_aligned(pts, 4) && pn2_aligned(assign, 4) && pn2_aligned(n_points, 8) && pn2_aligned(plane, 8) && pn2_aligned(rmse, 8));
     PN2_CHECK_ARG(pn2_aligned(sums, 8) && pn2_aligned(status, 4) && pn2_aligned(workspace, 16));
-    const PlaneWork w = plane_carve(B, N, 1, workspace);
+    const PlaneWork w = plane_work(B, N, 1, workspace);
     const int tiles = (int)pn2_cdiv(N, kSumTile);
     const hipStream_t s = pn2_s(stream);
     hipLaunchKernelGGL(plane_accumulate_kernel, dim3((unsigned)tiles, (unsigned)B), dim3(kThreads), 0, s, pts, ld, N, n_points, assign, threshold,
@@ -393,7 +384,7 @@ int pn2_plane_classify(const float *pts, int ld, int B, int N, const int64_t *n_
     PN2_CHECK_ARG(std::isfinite(threshold) && threshold >= 0.0 && plane_id >= 0);
     PN2_CHECK_ARG(pn2_aligned(pts, 4) && pn2_aligned(assign, 4) && pn2_aligned(n_points, 8) && pn2_aligned(plane, 8) && pn2_aligned(status, 4));
     PN2_CHECK_ARG(pn2_aligned(dist, 4) && pn2_aligned(count, 8) && pn2_aligned(workspace, 16));
-    const PlaneWork w = plane_carve(B, N, 1, workspace);
+    const PlaneWork w = plane_work(B, N, 1, workspace);
     const int tiles = (int)pn2_cdiv(N, kSumTile);
     const hipStream_t s = pn2_s(stream);
     const dim3 by_tile((unsigned)tiles, (unsigned)B);

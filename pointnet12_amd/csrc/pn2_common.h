@@ -35,6 +35,23 @@ static inline int64_t pn2_round16(int64_t v) { return (v + 15) / 16 * 16; }
 // p lies on a multiple of `bytes` (a power of two; a null pointer counts as aligned)
 static inline bool pn2_aligned(const void *p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
 
+// A caller's workspace split into parts, host side: every part starts where the one before it ended, rounded up to `align` bytes.
+// ONE function per workspace takes its parts from an arena: the launcher runs it over the caller's pointer, the _workspace_bytes
+// entry point over a null base (every part comes back null, nothing is added to a null pointer) and reads bytes().  Those functions
+// fill their struct with one braced list, whose clauses are evaluated left to right: the members stand in workspace order.
+struct Pn2Arena {
+    unsigned char *base;
+    int64_t at = 0;
+    explicit Pn2Arena(void *workspace) : base(static_cast<unsigned char *>(workspace)) {}
+    template <class T>
+    T *take(int64_t count, int64_t align = 16) {
+        T *part = base != nullptr ? reinterpret_cast<T *>(base + at) : nullptr;
+        at += (count * (int64_t)sizeof(T) + align - 1) / align * align;
+        return part;
+    }
+    int64_t bytes() const { return at; }
+};
+
 // rows of cloud b a launch looks at: the device-side count[b] clamped to [0, max_rows] (a captured launch sized by max_rows
 // stays valid when the count changes)
 __device__ __forceinline__ int pn2_clamped_rows(const int64_t *count, int b, int max_rows) {

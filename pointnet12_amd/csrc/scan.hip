@@ -84,12 +84,22 @@ __global__ __launch_bounds__(kCompactThreads) void scan_write_kernel(const float
 
 inline bool shape_ok(int B, int64_t max_rows) { return B >= 1 && B <= 65535 && max_rows >= 0 && max_rows < (int64_t)1 << 31; }
 
+// the workspace: the compaction's part alone
+Pn2Compact scan_work(int B, int64_t max_rows, void *base, int64_t *bytes = nullptr) {
+    Pn2Arena a(base);
+    const Pn2Compact w = pn2_compact_take(a, B, max_rows);
+    if (bytes != nullptr) *bytes = a.bytes();
+    return w;
+}
+
 }  // namespace
 
 extern "C" {
 
 int64_t pn2_scan_filter_workspace_bytes(int B, int64_t max_rows) {
-    return shape_ok(B, max_rows) ? Pn2Compact(B, max_rows).bytes() : PN2_EINVAL;
+    int64_t bytes = PN2_EINVAL;
+    if (shape_ok(B, max_rows)) scan_work(B, max_rows, nullptr, &bytes);
+    return bytes;
 }
 
 int pn2_scan_filter(const float *raw, const uint32_t *raw_label, const int64_t *row_begin, const int64_t *row_count, int B,
@@ -109,15 +119,14 @@ int pn2_scan_filter(const float *raw, const uint32_t *raw_label, const int64_t *
         rule.has_box = 1;
         for (int k = 0; k < 8; ++k) rule.box[k] = box[k];
     }
-    const Pn2Compact ws(B, max_rows);
-    unsigned char *flags = ws.flags(workspace);
-    const dim3 grid((unsigned)ws.tiles, (unsigned)B);
+    const Pn2Compact w = scan_work(B, max_rows, workspace);
+    const dim3 grid((unsigned)w.tiles, (unsigned)B);
     hipLaunchKernelGGL(scan_flag_kernel, grid, dim3(kCompactThreads), 0, pn2_s(stream), reinterpret_cast<const float4 *>(raw), raw_label,
-                       row_begin, row_count, (int)max_rows, lut, lut_len, rule, flags, ws.tile_count(workspace), ws.tiles, err);
+                       row_begin, row_count, (int)max_rows, lut, lut_len, rule, w.flags, w.tile_count, w.tiles, err);
     hipLaunchKernelGGL(pn2_compact_offsets_kernel, dim3((unsigned)B), dim3(PN2_WAVE), 0, pn2_s(stream), row_count, (int)max_rows,
-                       ws.tile_count(workspace), ws.tile_offset(workspace), ws.tiles, out_count, err, PN2_SCAN_ERR_ROWS);
+                       w.tile_count, w.tile_offset, w.tiles, out_count, err, PN2_SCAN_ERR_ROWS);
     hipLaunchKernelGGL(scan_write_kernel, grid, dim3(kCompactThreads), 0, pn2_s(stream), reinterpret_cast<const float4 *>(raw), raw_label,
-                       row_begin, row_count, (int)max_rows, lut, flags, ws.tile_offset(workspace), ws.tiles, out_begin,
+                       row_begin, row_count, (int)max_rows, lut, w.flags, w.tile_offset, w.tiles, out_begin,
                        reinterpret_cast<float4 *>(out_points), out_labels, out_index);
     return pn2_launch_status();
 }

@@ -144,22 +144,26 @@ __global__ __launch_bounds__(kThreads) void voxel_inverse_kernel(const int64_t *
 }
 
 // the workspace: the tables, a slot number per row of every tile, then the compaction's part
-struct Carve {
+struct Work {
+    Slot *table;
+    int *row_slot;
     Pn2Compact compact;
-    int64_t cap, table_bytes, row_slot_bytes;
-    Carve(int B, int64_t max_rows) : compact(B, max_rows), cap(pn2_slot_capacity(max_rows)) {
-        table_bytes = (int64_t)B * cap * (int64_t)sizeof(Slot);
-        row_slot_bytes = compact.flag_bytes * (int64_t)sizeof(int);
-    }
-    int64_t bytes() const { return table_bytes + row_slot_bytes + compact.bytes(); }
+    int64_t cap;                                                    // slots of one cloud's table
+    int64_t bytes;
 };
+
+Work voxel_work(int B, int64_t max_rows, void *base) {
+    Pn2Arena a(base);
+    const int64_t cap = pn2_slot_capacity(max_rows);
+    return {a.take<Slot>(B * cap), a.take<int>((int64_t)B * pn2_compact_tiles(max_rows) * kCompactTile), pn2_compact_take(a, B, max_rows), cap, a.bytes()};
+}
 
 }  // namespace
 
 extern "C" {
 
 int64_t pn2_voxel_grid_workspace_bytes(int B, int64_t max_rows) {
-    return pn2_slot_shape_ok(B, max_rows) ? Carve(B, max_rows).bytes() : PN2_EINVAL;
+    return pn2_slot_shape_ok(B, max_rows) ? voxel_work(B, max_rows, nullptr).bytes : PN2_EINVAL;
 }
 
 int pn2_voxel_grid(const float *pts, int ld, const int32_t *labels_in, const int64_t *row_begin, const int64_t *row_count, int B,
@@ -171,15 +175,13 @@ int pn2_voxel_grid(const float *pts, int ld, const int32_t *labels_in, const int
     PN2_CHECK_ARG(pn2_aligned(pts, 4) && pn2_aligned(out_points, 4) && pn2_aligned(workspace, 16));
     Grid grid;
     PN2_CHECK_ARG(pn2_grid_from(origin, voxel, grid));
-    const Carve ws(B, max_rows);
-    const int tiles = ws.compact.tiles;
-    const int64_t cap = ws.cap, rows_pad = (int64_t)tiles * kCompactTile, slots = (int64_t)B * cap;
-    unsigned char *at = static_cast<unsigned char *>(workspace);
-    Slot *table = reinterpret_cast<Slot *>(at);
-    int *row_slot = reinterpret_cast<int *>(at + ws.table_bytes);
-    void *compact = at + ws.table_bytes + ws.row_slot_bytes;
-    unsigned char *flags = ws.compact.flags(compact);
-    int *tile_count = ws.compact.tile_count(compact), *tile_offset = ws.compact.tile_offset(compact);
+    const Work w = voxel_work(B, max_rows, workspace);
+    const int tiles = w.compact.tiles;
+    const int64_t cap = w.cap, rows_pad = (int64_t)tiles * kCompactTile, slots = (int64_t)B * cap;
+    Slot *table = w.table;
+    int *row_slot = w.row_slot;
+    unsigned char *flags = w.compact.flags;
+    int *tile_count = w.compact.tile_count, *tile_offset = w.compact.tile_offset;
     const bool vec4 = ld == 4 && pn2_aligned(pts, 16) && pn2_aligned(out_points, 16);
     const hipStream_t s = pn2_s(stream);
     const dim3 by_tile((unsigned)tiles, (unsigned)B), by_row((unsigned)(rows_pad / kThreads), (unsigned)B);

@@ -88,18 +88,6 @@ __device__ __forceinline__ bool unite(int *parent, int a, int b, int cap) {
     return false;
 }
 
-// The workspace: the tables; per voxel of every tile its key, parent, root and the two counters; then the compaction's part.
-struct Carve {
-    Pn2Compact compact;
-    int64_t cap, table_bytes, key_bytes, word_bytes;
-    Carve(int B, int64_t max_rows) : compact(B, max_rows), cap(pn2_slot_capacity(max_rows)) {
-        table_bytes = (int64_t)B * cap * (int64_t)sizeof(Slot);
-        key_bytes = compact.flag_bytes * (int64_t)sizeof(unsigned long long);
-        word_bytes = compact.flag_bytes * (int64_t)sizeof(int);
-    }
-    int64_t bytes() const { return table_bytes + key_bytes + 4 * word_bytes + compact.bytes(); }
-};
-
 struct Work {
     Slot *table;
     unsigned long long *key;                                        // per voxel: its cell key, EMPTY when it takes no part
@@ -110,6 +98,18 @@ struct Work {
     int tiles;
     int64_t pad;                                                    // entries per cloud of the per-voxel arrays
 };
+
+// The workspace: the tables; per voxel of every tile its key, parent, root and the two counters; then the compaction's part.
+Work cluster_work(int B, int64_t max_rows, void *base, int64_t *bytes = nullptr) {
+    Pn2Arena a(base);
+    const int64_t cap = pn2_slot_capacity(max_rows), pad = (int64_t)pn2_compact_tiles(max_rows) * kCompactTile, n = B * pad;
+    Slot *table = a.take<Slot>(B * cap);
+    unsigned long long *key = a.take<unsigned long long>(n);
+    int *parent = a.take<int>(n), *root = a.take<int>(n), *points = a.take<int>(n), *voxels = a.take<int>(n);
+    const Pn2Compact c = pn2_compact_take(a, B, max_rows);
+    if (bytes != nullptr) *bytes = a.bytes();
+    return {table, key, parent, root, points, voxels, c.flags, c.tile_count, c.tile_offset, (unsigned)cap, c.tiles, pad};
+}
 
 __global__ __launch_bounds__(kThreads) void cluster_clear_kernel(const int64_t *__restrict__ out_count, int max_rows, Work w) {
     const int b = blockIdx.y;
@@ -290,7 +290,9 @@ __global__ __launch_bounds__(kThreads) void cluster_assign_kernel(const int64_t 
 extern "C" {
 
 int64_t pn2_voxel_components_workspace_bytes(int B, int64_t max_rows) {
-    return pn2_slot_shape_ok(B, max_rows) ? Carve(B, max_rows).bytes() : PN2_EINVAL;
+    int64_t bytes = PN2_EINVAL;
+    if (pn2_slot_shape_ok(B, max_rows)) cluster_work(B, max_rows, nullptr, &bytes);
+    return bytes;
 }
 
 int pn2_voxel_components(const float *pts, int ld, const int64_t *row_begin, const int64_t *row_count, int B, int64_t max_rows,
@@ -311,33 +313,16 @@ int pn2_voxel_components(const float *pts, int ld, const int64_t *row_begin, con
     PN2_CHECK_ARG(pn2_aligned(pts, 4) && pn2_aligned(workspace, 16));
     Grid grid;
     PN2_CHECK_ARG(pn2_grid_from(origin, voxel, grid));
-    const Carve ws(B, max_rows);
     Rule rule;
     rule.half = connectivity == 6 ? 3 : (connectivity == 18 ? 9 : 13);
     rule.same_label = same_label != 0;
     rule.L = member != nullptr ? L : 0;
     rule.min_points = min_points;
     rule.min_voxels = min_voxels;
-    Work w;
-    unsigned char *at = static_cast<unsigned char *>(workspace);
-    w.table = reinterpret_cast<Slot *>(at);
-    at += ws.table_bytes;
-    w.key = reinterpret_cast<unsigned long long *>(at);
-    at += ws.key_bytes;
-    w.parent = reinterpret_cast<int *>(at);
-    w.root = reinterpret_cast<int *>(at + ws.word_bytes);
-    w.points = reinterpret_cast<int *>(at + 2 * ws.word_bytes);
-    w.voxels = reinterpret_cast<int *>(at + 3 * ws.word_bytes);
-    at += 4 * ws.word_bytes;
-    w.flags = ws.compact.flags(at);
-    w.tile_count = ws.compact.tile_count(at);
-    w.tile_offset = ws.compact.tile_offset(at);
-    w.cap = (unsigned)ws.cap;
-    w.tiles = ws.compact.tiles;
-    w.pad = (int64_t)w.tiles * kCompactTile;
+    const Work w = cluster_work(B, max_rows, workspace);
     const hipStream_t s = pn2_s(stream);
     const dim3 by_tile((unsigned)w.tiles, (unsigned)B), by_row((unsigned)(w.pad / kThreads), (unsigned)B);
-    const dim3 by_slot((unsigned)pn2_cdiv(ws.cap > w.pad ? ws.cap : w.pad, kThreads), (unsigned)B);
+    const dim3 by_slot((unsigned)pn2_cdiv((int64_t)w.cap > w.pad ? (int64_t)w.cap : w.pad, kThreads), (unsigned)B);
     const dim3 by_pair((unsigned)(w.pad / kThreads), (unsigned)B, (unsigned)rule.half);
     hipLaunchKernelGGL(cluster_clear_kernel, by_slot, dim3(kThreads), 0, s, out_count, (int)max_rows, w);
     hipLaunchKernelGGL(cluster_insert_kernel, by_row, dim3(kThreads), 0, s, pts, ld, row_begin, row_count, out_begin, out_count, (int)max_rows,

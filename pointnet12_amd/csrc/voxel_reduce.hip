@@ -319,12 +319,28 @@ __global__ __launch_bounds__(kThreads) void mode_decode_kernel(const int64_t *__
     if (votes != nullptr) votes[o] = (int32_t)(w >> 32);
 }
 
-inline int64_t mean_bytes(int B, int64_t max_rows, int C) {
-    const int64_t words = (int64_t)B * max_rows * C;
-    return pn2_round16(words * 8) + pn2_round16(words * 4) + pn2_round16((int64_t)B * max_rows * 4);
+// the workspace of the mean: a sum and a maximum per (segment, column), a row count per segment
+struct MeanWork {
+    long long *S;
+    int *K, *rows_of;
+    int64_t bytes;
+};
+MeanWork mean_work(int B, int64_t max_rows, int C, void *base) {
+    Pn2Arena a(base);
+    const int64_t n = (int64_t)B * max_rows;
+    return {a.take<long long>(n * C), a.take<int>(n * C), a.take<int>(n), a.bytes()};
 }
-inline int64_t mode_bytes(int B, int64_t max_rows) {
-    return (int64_t)B * pn2_slot_capacity(max_rows) * (int64_t)sizeof(Pair) + pn2_round16((int64_t)B * max_rows * 8);
+
+// the workspace of the mode: the (segment, label) tables, a winner word per segment
+struct ModeWork {
+    Pair *table;
+    unsigned long long *winner;
+    int64_t cap, bytes;                                             // cap: slots of one cloud's table
+};
+ModeWork mode_work(int B, int64_t max_rows, void *base) {
+    Pn2Arena a(base);
+    const int64_t cap = pn2_slot_capacity(max_rows);
+    return {a.take<Pair>(B * cap), a.take<unsigned long long>((int64_t)B * max_rows), cap, a.bytes()};
 }
 
 }  // namespace
@@ -333,7 +349,7 @@ extern "C" {
 
 int64_t pn2_segment_reduce_workspace_bytes(int B, int64_t max_rows, int C) {
     if (!pn2_slot_shape_ok(B, max_rows) || C < 1 || C > PN2_SEGMENT_MAX_COLS) return PN2_EINVAL;
-    const int64_t mean = mean_bytes(B, max_rows, C), mode = mode_bytes(B, max_rows);
+    const int64_t mean = mean_work(B, max_rows, C, nullptr).bytes, mode = mode_work(B, max_rows, nullptr).bytes;
     return mean > mode ? mean : mode;
 }
 
@@ -343,31 +359,25 @@ int pn2_segment_mean(const float *values, int ld, int C, const int32_t *seg, con
     PN2_CHECK_ARG(values && seg && row_begin && row_count && out_begin && out_count && out && workspace);
     PN2_CHECK_ARG(pn2_slot_shape_ok(B, max_rows) && C >= 1 && C <= PN2_SEGMENT_MAX_COLS && ld >= C && ld_out >= C);
     PN2_CHECK_ARG(pn2_aligned(values, 4) && pn2_aligned(out, 4) && pn2_aligned(seg, 4) && pn2_aligned(workspace, 16));
-    const int64_t words = (int64_t)B * max_rows * C;
-    unsigned char *at = static_cast<unsigned char *>(workspace);
-    long long *S = reinterpret_cast<long long *>(at);
-    at += pn2_round16(words * 8);
-    int *K = reinterpret_cast<int *>(at);
-    at += pn2_round16(words * 4);
-    int *rows_of = reinterpret_cast<int *>(at);
+    const MeanWork w = mean_work(B, max_rows, C, workspace);
     const bool row_per_lane = pn2_opt(PN2_OPT_SEGRED_LANES) == 0;   // (A/B: one row per lane, its columns in a loop)
     const int R = row_per_lane ? PN2_WAVE : PN2_WAVE / C;           // rows per wave of the two row passes
     const hipStream_t s = pn2_s(stream);
     const dim3 by_word(pn2_slot_blocks(max_rows * C), (unsigned)B), by_row(pn2_slot_blocks(pn2_cdiv(max_rows, kWaves * R) * kThreads), (unsigned)B);
-    int *count_here = n_points == nullptr ? rows_of : nullptr;
-    hipLaunchKernelGGL(mean_clear_kernel, by_word, dim3(kThreads), 0, s, out_count, (int)max_rows, C, K, S, rows_of);
+    int *count_here = n_points == nullptr ? w.rows_of : nullptr;
+    hipLaunchKernelGGL(mean_clear_kernel, by_word, dim3(kThreads), 0, s, out_count, (int)max_rows, C, w.K, w.S, w.rows_of);
     if (pn2_opt(PN2_OPT_SEGRED_COMBINE)) {
         hipLaunchKernelGGL(mean_max_kernel<true>, by_row, dim3(kThreads), 0, s, values, ld, C, R, seg, row_begin, row_count, (int)max_rows,
-                           out_count, K, count_here, err, row_per_lane);
+                           out_count, w.K, count_here, err, row_per_lane);
         hipLaunchKernelGGL(mean_add_kernel<true>, by_row, dim3(kThreads), 0, s, values, ld, C, R, seg, row_begin, row_count, (int)max_rows,
-                           out_count, K, S, row_per_lane);
+                           out_count, w.K, w.S, row_per_lane);
     } else {
         hipLaunchKernelGGL(mean_max_kernel<false>, by_row, dim3(kThreads), 0, s, values, ld, C, R, seg, row_begin, row_count, (int)max_rows,
-                           out_count, K, count_here, err, row_per_lane);
+                           out_count, w.K, count_here, err, row_per_lane);
         hipLaunchKernelGGL(mean_add_kernel<false>, by_row, dim3(kThreads), 0, s, values, ld, C, R, seg, row_begin, row_count, (int)max_rows,
-                           out_count, K, S, row_per_lane);
+                           out_count, w.K, w.S, row_per_lane);
     }
-    hipLaunchKernelGGL(mean_final_kernel, by_word, dim3(kThreads), 0, s, out_begin, out_count, (int)max_rows, C, K, S, rows_of, n_points, out,
+    hipLaunchKernelGGL(mean_final_kernel, by_word, dim3(kThreads), 0, s, out_begin, out_count, (int)max_rows, C, w.K, w.S, w.rows_of, n_points, out,
                        ld_out, n_out, err);
     return pn2_launch_status();
 }
@@ -388,22 +398,21 @@ int pn2_segment_mode(const int32_t *labels, const int32_t *seg, const int64_t *r
                      void *workspace, pn2_stream_t stream) {
     PN2_CHECK_ARG(labels && seg && row_begin && row_count && out_begin && out_count && workspace && (out_labels || votes));
     PN2_CHECK_ARG(pn2_slot_shape_ok(B, max_rows) && pn2_aligned(labels, 4) && pn2_aligned(seg, 4) && pn2_aligned(workspace, 16));
-    const int64_t cap = pn2_slot_capacity(max_rows);
-    Pair *table = static_cast<Pair *>(workspace);
-    unsigned long long *winner = reinterpret_cast<unsigned long long *>(static_cast<unsigned char *>(workspace) + (int64_t)B * cap * (int64_t)sizeof(Pair));
+    const ModeWork w = mode_work(B, max_rows, workspace);
+    const int64_t cap = w.cap;
     const hipStream_t s = pn2_s(stream);
     const dim3 by_row(pn2_slot_blocks(max_rows), (unsigned)B);
     hipLaunchKernelGGL(mode_clear_kernel, dim3(pn2_slot_clear_blocks(cap), (unsigned)B), dim3(kThreads), 0, s, row_count, out_count, (int)max_rows,
-                       reinterpret_cast<uint4 *>(table), cap, winner);
+                       reinterpret_cast<uint4 *>(w.table), cap, w.winner);
     if (pn2_opt(PN2_OPT_SEGRED_COMBINE))
         hipLaunchKernelGGL(mode_insert_kernel<true>, by_row, dim3(kThreads), 0, s, labels, seg, row_begin, row_count, (int)max_rows,
-                           out_count, table, cap, err);
+                           out_count, w.table, cap, err);
     else
         hipLaunchKernelGGL(mode_insert_kernel<false>, by_row, dim3(kThreads), 0, s, labels, seg, row_begin, row_count, (int)max_rows,
-                           out_count, table, cap, err);
-    hipLaunchKernelGGL(mode_vote_kernel, dim3(pn2_slot_blocks(cap), (unsigned)B), dim3(kThreads), 0, s, row_count, out_count, (int)max_rows, table,
-                       cap, winner);
-    hipLaunchKernelGGL(mode_decode_kernel, by_row, dim3(kThreads), 0, s, out_begin, out_count, (int)max_rows, winner, fill, out_labels, votes);
+                           out_count, w.table, cap, err);
+    hipLaunchKernelGGL(mode_vote_kernel, dim3(pn2_slot_blocks(cap), (unsigned)B), dim3(kThreads), 0, s, row_count, out_count, (int)max_rows, w.table,
+                       cap, w.winner);
+    hipLaunchKernelGGL(mode_decode_kernel, by_row, dim3(kThreads), 0, s, out_begin, out_count, (int)max_rows, w.winner, fill, out_labels, votes);
     return pn2_launch_status();
 }
 

@@ -216,10 +216,8 @@ Matches = collections.namedtuple("Matches", "pair_src pair_tgt count idx dist")
 
 def match_workspace_bytes(N, B=1):
     """Bytes of ``pn2_match_pairs``' workspace for ``B`` clouds of up to ``N`` source rows (host-only call)."""
-    n = _lib.load().pn2_match_pairs_workspace_bytes(int(B), int(N))
-    if n < 0:
-        raise ValueError("match_features: B = %d clouds of N = %d rows are not supported" % (B, N))
-    return int(n)
+    return _lib.workspace_bytes("pn2_match_pairs_workspace_bytes", (int(B), int(N)), ValueError,
+                                "match_features: B = %d clouds of N = %d rows are not supported" % (B, N))
 
 
 class MatchBuffers:

@@ -102,9 +102,8 @@ class ScanBuffers:
     ``labels`` / ``index`` int32 ``[rows]``, ``count`` int64 ``[B]`` and the kernel's ``workspace``."""
 
     def __init__(self, rows, B, max_rows, device):
-        nbytes = _lib.load().pn2_scan_filter_workspace_bytes(int(B), int(max_rows))
-        if nbytes < 0:
-            raise _lib.Pn2Error("ScanBuffers: B = %d, max_rows = %d are not supported" % (B, max_rows))
+        nbytes = _lib.workspace_bytes("pn2_scan_filter_workspace_bytes", (int(B), int(max_rows)), _lib.Pn2Error,
+                                      "ScanBuffers: B = %d, max_rows = %d are not supported" % (B, max_rows))
         self.rows, self.B, self.max_rows = int(rows), int(B), int(max_rows)
         self.points = torch.empty(self.rows, 4, device=device, dtype=torch.float32)
         self.labels = torch.empty(self.rows, device=device, dtype=torch.int32)

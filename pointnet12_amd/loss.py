@@ -212,9 +212,8 @@ class _LovaszSoftmax(torch.autograd.Function):
         lib, st = _lib.load(), _lib.stream()
         R, ld, inner = layout
         C = x.shape[1]
-        nbytes = int(lib.pn2_lovasz_workspace_bytes(R, C, images))
-        if nbytes < 0:
-            raise _lib.Pn2Error("lovasz_softmax: %d rows of %d classes in %d images are beyond the kernels' index range" % (R, C, images))
+        nbytes = _lib.workspace_bytes("pn2_lovasz_workspace_bytes", (R, C, images), _lib.Pn2Error,
+                                      "lovasz_softmax: %d rows of %d classes in %d images are beyond the kernels' index range" % (R, C, images))
         ws = _lovasz_workspace(nbytes, x.device)
         dp = torch.empty(R, C, device=x.device, dtype=torch.float32)
         loss = torch.empty((), device=x.device, dtype=torch.float32)

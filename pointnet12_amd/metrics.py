@@ -378,9 +378,8 @@ def _class_mask(mask, C, device, what):
 
 def panoptic_workspace(B, max_rows, device="cuda"):
     """The ``work=`` buffer of ``panoptic_counts`` for calls of ``B`` clouds of at most ``max_rows`` rows each."""
-    nbytes = _lib.load().pn2_panoptic_workspace_bytes(int(B), int(max_rows))
-    if nbytes < 0:
-        raise _lib.Pn2Error("panoptic_workspace: B = %d, max_rows = %d are not supported" % (B, max_rows))
+    nbytes = _lib.workspace_bytes("pn2_panoptic_workspace_bytes", (int(B), int(max_rows)), _lib.Pn2Error,
+                                  "panoptic_workspace: B = %d, max_rows = %d are not supported" % (B, max_rows))
     return torch.empty(max(int(nbytes), 16), device=device, dtype=torch.uint8)
 
 
@@ -448,9 +447,8 @@ def panoptic_counts(pred_sem, pred_inst, gt_sem, gt_inst, num_classes, include=N
     if err is not None and (err.dtype != torch.int32 or err.device != dev or err.numel() < 1):
         raise ValueError("panoptic_counts: err must be an int32 device tensor")
     lib = _lib.load()
-    need = lib.pn2_panoptic_workspace_bytes(B, max_rows)
-    if need < 0:
-        raise _lib.Pn2Error("panoptic_counts: B = %d, max_rows = %d are not supported" % (B, max_rows))
+    need = _lib.workspace_bytes("pn2_panoptic_workspace_bytes", (B, max_rows), _lib.Pn2Error,
+                                "panoptic_counts: B = %d, max_rows = %d are not supported" % (B, max_rows))
     if work is None:
         work = panoptic_workspace(B, max_rows, dev)
     elif work.dtype != torch.uint8 or work.device != dev or work.numel() < need or not work.is_contiguous():
@@ -528,9 +526,8 @@ class PanopticEvaluator:
             B, bound = int(gt_sem.shape[0]), int(gt_sem.shape[1])
         else:
             B, bound = 1, int(gt_sem.numel())
-        need = _lib.load().pn2_panoptic_workspace_bytes(B, bound)
-        if need < 0:
-            raise _lib.Pn2Error("PanopticEvaluator.update: B = %d, max_rows = %d are not supported" % (B, bound))
+        need = _lib.workspace_bytes("pn2_panoptic_workspace_bytes", (B, bound), _lib.Pn2Error,
+                                    "PanopticEvaluator.update: B = %d, max_rows = %d are not supported" % (B, bound))
         if self._work is None or self._work.numel() < need:
             self._work = panoptic_workspace(B, bound, self.device)
         slot = self._reserve(B) if self.per_cloud else self._tape[0]

@@ -54,10 +54,8 @@ def _triple(v, what):
 
 def workspace_bytes(M, B=1):
     """Bytes of the workspace ``pn2_grid_build`` fills for ``B`` clouds of up to ``M`` candidates (host-only call)."""
-    n = _lib.load().pn2_grid_workspace_bytes(int(B), int(M))
-    if n < 0:
-        raise ValueError("GridIndex: B = %d clouds of M = %d rows are not supported" % (B, M))
-    return int(n)
+    return _lib.workspace_bytes("pn2_grid_workspace_bytes", (int(B), int(M)), ValueError,
+                                "GridIndex: B = %d clouds of M = %d rows are not supported" % (B, M))
 
 
 class GridBuffers:

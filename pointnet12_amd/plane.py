@@ -27,10 +27,8 @@ PlaneSegments = collections.namedtuple("PlaneSegments", "planes counts assign st
 
 def workspace_bytes(N, B=1, iterations=256):
     """Bytes of the plane entry points' workspace for ``B`` clouds of up to ``N`` rows and ``iterations`` hypotheses (host-only call)."""
-    n = _lib.load().pn2_plane_workspace_bytes(int(B), int(N), int(iterations))
-    if n < 0:
-        raise ValueError("plane: B = %d clouds of N = %d rows with %d hypotheses are not supported" % (B, N, iterations))
-    return int(n)
+    return _lib.workspace_bytes("pn2_plane_workspace_bytes", (int(B), int(N), int(iterations)), ValueError,
+                                "plane: B = %d clouds of N = %d rows with %d hypotheses are not supported" % (B, N, iterations))
 
 
 class PlaneBuffers:

@@ -34,10 +34,8 @@ NORMAL_K = 16            # neighbours of the default target normals (estimate_no
 
 def workspace_bytes(N, B=1):
     """Bytes of ``pn2_icp_step``'s workspace for ``B`` clouds of up to ``N`` source rows (host-only call)."""
-    n = _lib.load().pn2_icp_workspace_bytes(int(B), int(N))
-    if n < 0:
-        raise ValueError("icp: B = %d clouds of N = %d rows are not supported" % (B, N))
-    return int(n)
+    return _lib.workspace_bytes("pn2_icp_workspace_bytes", (int(B), int(N)), ValueError,
+                                "icp: B = %d clouds of N = %d rows are not supported" % (B, N))
 
 
 class IcpBuffers:
@@ -252,10 +250,8 @@ GLOBAL_THRESHOLD = 0.3   # register_global's default inlier distance as a multip
 def corr_workspace_bytes(N, B=1, iterations=1024):
     """Bytes of ``pn2_corr_ransac`` / ``pn2_corr_refit``'s workspace for ``B`` pair lists of up to ``N`` pairs and ``iterations``
     hypotheses (host-only call)."""
-    n = _lib.load().pn2_corr_workspace_bytes(int(B), int(N), int(iterations))
-    if n < 0:
-        raise ValueError("ransac_correspondences: B = %d lists of N = %d pairs with %d hypotheses are not supported" % (B, N, iterations))
-    return int(n)
+    return _lib.workspace_bytes("pn2_corr_workspace_bytes", (int(B), int(N), int(iterations)), ValueError,
+                                "ransac_correspondences: B = %d lists of N = %d pairs with %d hypotheses are not supported" % (B, N, iterations))
 
 
 class CorrBuffers:

@@ -46,9 +46,8 @@ class VoxelBuffers:
     reductions' workspace, and ``votes`` int32 ``[rows]``; both are None otherwise."""
 
     def __init__(self, rows, B, max_rows, ld, device, reduce=False):
-        nbytes = _lib.load().pn2_voxel_grid_workspace_bytes(int(B), int(max_rows))
-        if nbytes < 0:
-            raise _lib.Pn2Error("VoxelBuffers: B = %d, max_rows = %d are not supported" % (B, max_rows))
+        nbytes = _lib.workspace_bytes("pn2_voxel_grid_workspace_bytes", (int(B), int(max_rows)), _lib.Pn2Error,
+                                      "VoxelBuffers: B = %d, max_rows = %d are not supported" % (B, max_rows))
         self.rows, self.B, self.max_rows, self.ld = int(rows), int(B), int(max_rows), int(ld)
         i32 = lambda: torch.empty(self.rows, device=device, dtype=torch.int32)
         self.points = torch.empty(self.rows, self.ld, device=device, dtype=torch.float32)
@@ -57,9 +56,8 @@ class VoxelBuffers:
         self.workspace = torch.empty(nbytes, device=device, dtype=torch.uint8)
         self.reduce_workspace = self.votes = None
         if reduce:
-            nbytes = _lib.load().pn2_segment_reduce_workspace_bytes(self.B, self.max_rows, self.ld)
-            if nbytes < 0:
-                raise _lib.Pn2Error("VoxelBuffers: B = %d, max_rows = %d, ld = %d are not supported" % (B, max_rows, ld))
+            nbytes = _lib.workspace_bytes("pn2_segment_reduce_workspace_bytes", (self.B, self.max_rows, self.ld), _lib.Pn2Error,
+                                          "VoxelBuffers: B = %d, max_rows = %d, ld = %d are not supported" % (B, max_rows, ld))
             self.reduce_workspace = torch.empty(nbytes, device=device, dtype=torch.uint8)
             self.votes = i32()
 
@@ -76,9 +74,8 @@ class ComponentBuffers:
     ``workspace``."""
 
     def __init__(self, rows, B, max_rows, device):
-        nbytes = _lib.load().pn2_voxel_components_workspace_bytes(int(B), int(max_rows))
-        if nbytes < 0:
-            raise _lib.Pn2Error("ComponentBuffers: B = %d, max_rows = %d are not supported" % (B, max_rows))
+        nbytes = _lib.workspace_bytes("pn2_voxel_components_workspace_bytes", (int(B), int(max_rows)), _lib.Pn2Error,
+                                      "ComponentBuffers: B = %d, max_rows = %d are not supported" % (B, max_rows))
         self.rows, self.B, self.max_rows = int(rows), int(B), int(max_rows)
         i32 = lambda: torch.full((self.rows,), -1, device=device, dtype=torch.int32)
         self.row_component, self.voxel_component = i32(), i32()
@@ -363,9 +360,8 @@ def _values_2d(what, values):
 
 
 def _workspace(workspace, B, max_rows, C, dev):
-    nbytes = _lib.load().pn2_segment_reduce_workspace_bytes(B, max_rows, C)
-    if nbytes < 0:
-        raise _lib.Pn2Error("segment reduction: B = %d, max_rows = %d, C = %d are not supported" % (B, max_rows, C))
+    nbytes = _lib.workspace_bytes("pn2_segment_reduce_workspace_bytes", (B, max_rows, C), _lib.Pn2Error,
+                                  "segment reduction: B = %d, max_rows = %d, C = %d are not supported" % (B, max_rows, C))
     if workspace is None:
         return torch.empty(nbytes, device=dev, dtype=torch.uint8)
     if not workspace.is_cuda or workspace.dtype != torch.uint8 or workspace.numel() < nbytes:

@@ -111,3 +111,28 @@ def test_host_build_exports_the_geometry_symbols_and_matches_golden():
     assert host.pn2_square_distance(p(np.ascontiguousarray(g3["new_xyz"])), p(np.ascontiguousarray(g3["xyz"])), 1, d.shape[1], d.shape[2],
                                     p(d), None) == 0
     assert (d.view(np.uint32)[0, ::16, :] == g3["sample_bits"]).all()
+
+
+# the entry points _lib._Timed hands out WITHOUT event brackets, as the hand-kept tuple listed them before the set was derived
+# from SIGNATURES (a copy, on purpose: a new host-only entry point has to be added here by hand, and the rule has to agree)
+HOST_ONLY = (
+    "pn2_version", "pn2_error_string", "pn2_set_option", "pn2_get_option", "pn2_option_name", "pn2_fps_workspace_bytes",
+    "pn2_nll_loss_workspace_bytes", "pn2_cross_entropy_workspace_bytes", "pn2_res_supported", "pn2_bwd_res_supported",
+    "pn2_conv1x1_wgrad_workspace_bytes", "pn2_conv1x1_wgrad_cf_scratch_bytes", "pn2_conv1x1_bwd_cf_supported",
+    "pn2_conv1x1_bwd_first_supported", "pn2_conv1x1_bwd_cf_scratch_bytes", "pn2_last_kernel", "pn2_clear_last_kernel",
+    "pn2_ball_query_workspace_bytes", "pn2_point_transform_workspace_bytes", "pn2_group_colsum_workspace_bytes",
+    "pn2_chamfer_nn_workspace_bytes", "pn2_scan_filter_workspace_bytes", "pn2_voxel_grid_workspace_bytes",
+    "pn2_segment_reduce_workspace_bytes", "pn2_voxel_components_workspace_bytes", "pn2_panoptic_workspace_bytes",
+    "pn2_lovasz_workspace_bytes", "pn2_lovasz_tile_rows", "pn2_grid_workspace_bytes", "pn2_icp_workspace_bytes",
+    "pn2_plane_workspace_bytes", "pn2_match_pairs_workspace_bytes", "pn2_corr_workspace_bytes", "pn2_segment_boxes_workspace_bytes",
+)
+
+
+def test_host_only_entry_points_are_derived_from_the_signatures():
+    assert len(HOST_ONLY) == 34 and len(set(HOST_ONLY)) == 34
+    assert _lib.HOST_ONLY == frozenset(HOST_ONLY)
+    assert _lib.LAUNCHES == frozenset(_lib.SIGNATURES) - frozenset(HOST_ONLY)
+    for name in _lib.LAUNCHES:                                  # what _Timed reads as the stream handle is a pointer argument
+        res, args = _lib.SIGNATURES[name]
+        assert res is ctypes.c_int and args[-1] is ctypes.c_void_p, name
+    assert all(name in _lib.HOST_ONLY for name in _lib.SIGNATURES if name.endswith("_workspace_bytes"))
