@@ -324,9 +324,21 @@ def options(lib=None):
         i += 1
 
 
+_option_hooks = []
+
+
+def on_option_change(hook):
+    """Register ``hook()``, called after every successful ``set_option``: Python-side state that was derived from what the
+    library answered under the old options (which route a shape takes) is dropped there."""
+    _option_hooks.append(hook)
+    return hook
+
+
 def set_option(name, value):
     """pn2_set_option; raises on an unknown name."""
     check(load().pn2_set_option(name.encode(), int(value)), "pn2_set_option(%s)" % name)
+    for hook in _option_hooks:
+        hook()
 
 
 def forward_env_options(lib):

@@ -688,6 +688,12 @@ _REPL = 8                         # PN2_STAT_REPLICAS of include/pn2.h
 _PAIR_RUNS_SPLIT = set()          # (P, C_out, C_in, pooled, masked) shapes pn2_conv1x1_bwd_pair answered with PN2_OK_SPLIT
 
 
+@_lib.on_option_change
+def _forget_pair_splits():
+    """The answers were given under the old options (BWD_PAIR, TN_CFG, the row thresholds): every shape asks again."""
+    _PAIR_RUNS_SPLIT.clear()
+
+
 def set_direct_grad_accumulation(enabled):
     """When enabled, the MLP backward adds weight / BatchNorm gradients straight into existing ``param.grad`` tensors
     (the wgrad kernel's atomics and the BN-coefficient kernel write there) and returns None for them, instead of
